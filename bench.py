@@ -6,6 +6,10 @@
     (RANK / LOCAL_RANK / WORLD_SIZE come from the launcher) or plainly as `python bench.py --gpus N`, which re-executes
     itself under that launcher on 127.0.0.1.  The communicator size must equal --gpus (checked; printed as `rccl_ranks`).
     --dry-run: launcher / sharding / barrier / JSON plumbing on CPU (gloo), no HIP work: what the CPU tests exercise.
+    --full: everything past the headline - the repeated regions, the sustained leg, the host-buffer legs, the per-launch kernel profile and roofline
+    (with live rocprofv3 traffic passes), the CPU baseline and the other BASELINE configs (extra.configs).  Without it a run sets up, warms up, times
+    the K steps and prints the line; those fields are then null.  The --no-* options below switch parts of a --full run off.
+    --dump-outputs DIR: after the timed steps, the frame the last step computed -> DIR/*.npy (float32; see dump_outputs()).
 
 One "step" = one frame pair (two resident u8 RGB frames -> one interpolated frame) through
 `rife_hip_process_device`, per rank.  Frame pairs shard embarrassingly (the reference runs one RIFE replica
@@ -147,6 +151,26 @@ def percentiles(xs):
     return {"n": n, "median": round(pick(0.5), 3), "p10": round(pick(0.1), 3), "p90": round(pick(0.9), 3), "min": round(xs[0], 3), "max": round(xs[-1], 3)}
 
 
+DUMP_MAX_BYTES = 64 * 10**6       # --dump-outputs: float32 bytes written in all
+DUMP_SAMPLE_PIXELS = 1 << 21      # pixels of the sample written where the whole frame would exceed DUMP_MAX_BYTES (25.2 MB)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(outdir, frame):
+    """--dump-outputs: `frame` (u8 h x w x 3, what the caller of rife_hip_process_device receives) as float32.  It is written whole as
+    DIR/interpolated_frame.npy if that fits in DUMP_MAX_BYTES (1080p: 24.9 MB), else (3840x2160: 99.5 MB) as DIR/interpolated_frame_sample.npy:
+    the DUMP_SAMPLE_PIXELS pixels at the sorted flat indices np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False),
+    shape (DUMP_SAMPLE_PIXELS, 3) - the same pixels in every run at that size."""
+    os.makedirs(outdir, exist_ok=True)
+    h, w, c = frame.shape
+    if frame.size * 4 <= DUMP_MAX_BYTES:
+        name, out = "interpolated_frame", frame
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+        name, out = "interpolated_frame_sample", frame.reshape(h * w, c)[idx]
+    np.save(os.path.join(outdir, name + ".npy"), out.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -168,9 +192,15 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the short legs of the other BASELINE configs (extra.configs: 1080p, v23-1080p, 4k-tta) that the default call appends")
     ap.add_argument("--no-sustained", action="store_true", help="skip the ~ 4 s sustained leg with socket power / shader clock sampling (extra.sustained)")
     ap.add_argument("--dry-run", action="store_true", help="CPU plumbing check (gloo): launcher, sharding, barrier, MAX over ranks, JSON; no HIP work")
+    ap.add_argument("--full", action="store_true", help="also run everything past the headline (repeated regions, sustained leg, host-buffer legs, kernel profile / "
+                    "roofline, CPU baseline, extra.configs); off: set-up, warm-up, the K timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame of the last timed step to DIR/*.npy (float32; a fixed, seeded "
+                    "sample of its pixels where the whole frame would exceed %d MB)" % (DUMP_MAX_BYTES // 10**6))
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, rendezvous on 127.0.0.1)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -291,6 +321,29 @@ def main():
     # 4K and 20 % at 1080p, so they are kept out of it) ...
     elapsed = sh.timed_steps(lambda i: run_steps(i, args.steps), 1, first_index=args.warmup, dist=dist, device_sync=torch.cuda.synchronize,
                              make_tensor=lambda v, dtype: torch.tensor(v, dtype=dtype, device=coll_dev))
+    # what the last timed step (index W + K - 1) returned, read before any later region reuses its stream's output buffer
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[(args.warmup + args.steps - 1) % len(streams)].cpu().numpy())
+    f32_mode = os.environ.get("RIFE_HIP_TRUNK", "") == "f32"
+    fps = world * args.steps / elapsed
+    line = {
+        "metric": "interpolated frames/sec (%s, %dx%d%s)" % (family, w, h, " -x -z" if tta else ""), "value": round(fps, 3), "unit": "frames/s",
+        "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if f32_mode else "f16x2-split MFMA + f32 accumulate (fp32-equivalent; activations stored f32 or as {hi, lo} f16 pairs)", "data": "synthetic",
+        "config": {"workload": "%s %dx%d%s frame pairs resident in HBM, timestep sweep %s, synthetic seeded weights" % (family, w, h, " -x -z (TTA)" if tta else "", timesteps),
+                   "pairs_in_flight_per_gpu": nstreams,
+                   "cu_partition": "none (ordinary streams)" if cu_parts <= 1 else "every stream owns 1 / %d of the compute units (rife_hip_stream_create)" % cu_parts,
+                   "frames": frame_kind, "untimed_setup_pairs": SETUP, "parallelism": "frame pairs sharded over ranks, no data-path collective" + (" [--share-gpu TEST MODE: all ranks on ONE device over gloo - not a scaling measurement]" if args.share_gpu else "")},
+        "roofline": None, "roofline_in_timed_region": None, "cpu_baseline": None, "extra": None,     # --full
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # the same K-step region repeated (>= 50 pairs, median / p10 / p90): `value` stays the FIRST region, exactly K steps
     reps = max(3, -(-150 // max(1, args.steps)))
     region_fps = [world * args.steps / elapsed]
@@ -413,7 +466,6 @@ def main():
         streams[:] = saved
     if rank == 0:
         # dominant kernel: the block-3 trunk conv of the IFNet (one shape per class, so flops per launch are well defined)
-        f32_mode = os.environ.get("RIFE_HIP_TRUNK", "") == "f32"
         dom = prof.get(DOMINANT[family][0], dict(ms=0.0, launches=0, flops=0.0))
         pclean = prof1 or prof
         conv_ms = sum(v["ms"] for k, v in pclean.items() if v["flops"] > 0)
@@ -440,7 +492,6 @@ def main():
         cpu = None
         if not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(modeldir, family, w * h, 16 if tta and tta_temporal else 1, (w, h))
-        fps = world * args.steps / elapsed
         # roofline.e2e_frac: the whole pair against the fused-minimum HBM roofline of SURVEY 8(d) / App. E-3 (every tensor of the graph read and written once
         # at fp16, 0.701 ms per 4K pair at 8 TB/s) - roofline time / measured time per pair PER GPU, in the timed region (4 pairs in flight): the one number
         # that compares across rounds
@@ -459,15 +510,7 @@ def main():
             kbest = max((k for k in host if isinstance(host[k], float)), key=lambda k: host[k])
             boundary = {"value": host[kbest], "unit": "frames/s", "leg": kbest,
                         "note": "best PCIe-inclusive figure of this run: host frames in, host frame out through RIFE::process / rife_hip_process_batch (the boundary the reference exposes); never `value`"}
-        line = {
-            "metric": "interpolated frames/sec (%s, %dx%d%s)" % (family, w, h, " -x -z" if tta else ""), "value": round(fps, 3), "unit": "frames/s",
-            "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32" if f32_mode else "f16x2-split MFMA + f32 accumulate (fp32-equivalent; activations stored f32 or as {hi, lo} f16 pairs)", "data": "synthetic",
-            "config": {"workload": "%s %dx%d%s frame pairs resident in HBM, timestep sweep %s, synthetic seeded weights" % (family, w, h, " -x -z (TTA)" if tta else "", timesteps),
-                       "pairs_in_flight_per_gpu": nstreams,
-                       "cu_partition": "none (ordinary streams)" if cu_parts <= 1 else "every stream owns 1 / %d of the compute units (rife_hip_stream_create)" % cu_parts,
-                       "frames": frame_kind, "untimed_setup_pairs": SETUP, "parallelism": "frame pairs sharded over ranks, no data-path collective" + (" [--share-gpu TEST MODE: all ranks on ONE device over gloo - not a scaling measurement]" if args.share_gpu else "")},
+        line.update({
             "roofline": roof,
             "roofline_in_timed_region": roof_timed if prof1 is not None else None,
             "cpu_baseline": cpu,
@@ -484,7 +527,7 @@ def main():
                       "per_class_ms_per_pair": {k: round(v["ms"] / args.steps, 4) for k, v in sorted((prof1 or prof).items(), key=lambda kv: -kv[1]["ms"])},
                       "frames_per_s_process_boundary": boundary,
                       "configs": configs},
-        }
+        })
         print(json.dumps(line))
     if dist is not None:
         dist.barrier()

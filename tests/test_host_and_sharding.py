@@ -355,12 +355,32 @@ def test_live_traffic_degrades_to_a_reason_without_rocprofv3(monkeypatch):
     assert tb is None and "rocprofv3" in why
 
 
+def test_bench_dump_outputs_is_float32_within_budget_and_samples_fixed_pixels(tmp_path):
+    """`bench.py --dump-outputs DIR`: a 1080p frame is written whole; a 4K frame (99.5 MB as float32) as the same seeded sample of whole pixels in
+    every run, so that two builds can be compared file for file; everything float32 and within bench.DUMP_MAX_BYTES."""
+    import bench
+    rng = np.random.default_rng(5)
+    small = rng.integers(0, 256, (1080, 1920, 3), dtype=np.uint8)
+    big = rng.integers(0, 256, (2160, 3840, 3), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(str(tmp_path / "a" / "interpolated_frame.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+        assert os.listdir(str(tmp_path / d)) == ["interpolated_frame_sample.npy"]
+        assert os.path.getsize(str(tmp_path / d / "interpolated_frame_sample.npy")) <= bench.DUMP_MAX_BYTES
+    s1, s2 = (np.load(str(tmp_path / d / "interpolated_frame_sample.npy")) for d in ("b", "c"))
+    assert s1.dtype == np.float32 and s1.shape == (bench.DUMP_SAMPLE_PIXELS, 3) and np.array_equal(s1, s2)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(2160 * 3840, bench.DUMP_SAMPLE_PIXELS, replace=False))
+    assert np.array_equal(s1, big.reshape(-1, 3)[idx])
+
+
 @pytest.mark.gpu
 def test_bench_two_ranks_on_one_gpu_exercise_the_all_ranks_host_leg():
     """`bench.py --gpus 2 --share-gpu`: the N-rank code paths on real HIP work (both ranks on device 0, gloo rendezvous): sharding, barriers, the
     all-ranks host-buffer leg with NUMA pinning from sysfs.  A plumbing check - the line says so - not a scaling measurement."""
     import json
-    r = _bench("--gpus", "2", "--share-gpu", "--workload", "1080p", "--steps", "6", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic", "--no-extra")
+    r = _bench("--gpus", "2", "--share-gpu", "--full", "--workload", "1080p", "--steps", "6", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic", "--no-extra")
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and "TEST MODE" in d["config"]["parallelism"]

@@ -46,7 +46,7 @@ timeout 300 python tools/stem_rs_bench.py > $OUT/stem_rs_bench.txt 2>&1
 timeout 300 python tools/tail_rs_bench.py > $OUT/tail_rs_bench.txt 2>&1
 
 for wl in 4k 1080p v23-1080p 4k-tta; do
-    timeout 900 python bench.py --workload $wl --steps 50 > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
+    timeout 900 python bench.py --full --workload $wl --steps 50 > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
 done
 timeout 300 python tools/host_path_bench2.py > $OUT/host_path.txt 2>&1
 python tools/pmc_tables.py $OUT $OUT/tables 3 4k > $OUT/tables.log 2>&1
