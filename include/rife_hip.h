@@ -96,6 +96,32 @@ int rife_hip_process_frames(const rife_hip_t* r, const rife_hip_frame_t* frame0,
                             uint8_t* out_rgb);
 void rife_hip_frame_release(rife_hip_frame_t* frame);
 
+/* ---- deep colour: 10-bit RGB in and out (absent in the reference, whose frames are 8-bit, src/main.cpp:187) ------------------------------
+ * The network's inputs are fp32 planes in [0, 1] (src/rife.cpp:4167), so nothing but the pre-processing, the frame taps and the quantising
+ * epilogues knows the depth.  Resident frames stay one dword per pixel (10:10:10 instead of 8:8:8:x): a 10-bit pair moves the bytes an 8-bit pair moves.
+ *   input plane  = code * (1 / 1023.f), zero-padded to 32n like the 8-bit plane;
+ *   output code  = min(max((int)(v * 1023.f + 0.5f), 0), 1023), cropped with the padded pitch;
+ *   timestep 0 / 1 return the first / second frame's codes (clamped to 1023, alpha bits 3).
+ * Input and output of a call have the same format, and the two 10-bit formats give the same codes.  With RIFE_HIP_PIX_RGB8 every _px call IS the
+ * call without the suffix (same code path, same bytes, every model family and mode).
+ * Scope of the 10-bit formats: model family rife-v4.6, plain mode, every frame size the 8-bit path serves.  Any other family (rife-v4, v2.x, v3.x, v1) or mode
+ * (TTA -x, temporal TTA -z, UHD -u) returns -RIFE_HIP_ENOSYS with a message that names it and leaves the output untouched; the opt-in graph replay
+ * (RIFE_HIP_GRAPH=1) does not apply to 10-bit calls.  Out of scope: rife_hip_process_batch (the host batch with internal workers) at depth 10, 12- and
+ * 16-bit samples (a second dword per pixel, i.e. different gather kernels), YUV. */
+#define RIFE_HIP_PIX_RGB8         0   /* u8 HWC, 3 B / pixel: what rife_hip_process() takes */
+#define RIFE_HIP_PIX_RGB10_U16    1   /* u16 HWC, native byte order, 6 B / pixel, codes 0..1023; a larger value is read as 1023 */
+#define RIFE_HIP_PIX_A2B10G10R10  2   /* one little-endian dword / pixel: R bits 0-9, G 10-19, B 20-29; bits 30-31 ignored on input, written as 3 */
+
+size_t rife_hip_frame_bytes(int w, int h, int pixfmt);      /* 0 for an unknown format or w, h <= 0 */
+int rife_hip_process_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt);
+int rife_hip_process_device_px(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt,
+                               void* hip_stream);
+int rife_hip_process_device_batch_px(const rife_hip_t* r, int n, const void* const* d_in0, const void* const* d_in1, const float* timestep,
+                                     void* const* d_out, int w, int h, int pixfmt, void* hip_stream);
+/* A frame carries its format: rife_hip_process_frames writes the format its two frames were uploaded in (-RIFE_HIP_EINVAL if they differ), and its
+ * out_rgb then points at rife_hip_frame_bytes() bytes. */
+int rife_hip_frame_upload_px(const rife_hip_t* r, const void* pixels, int w, int h, int pixfmt, rife_hip_frame_t** frame);
+
 const char* rife_hip_last_error(void);
 
 /* ---- measurement hooks (bench.py / profiles) ---------------------------------------------------------------

@@ -32,6 +32,12 @@ int rife_hip_v4_tap(const rife_hip_t* r, const uint8_t* in0_rgb, const uint8_t* 
  * rife_hip_process.  out_rgb: w x h u8 RGB. */
 int rife_hip_v4_process_injected(const rife_hip_t* r, const uint8_t* in0_rgb, const uint8_t* in1_rgb, int w, int h, float timestep,
                                  const float* const* inject, int n_inject, uint8_t* out_rgb);
+/* The first two taps on frames of format `pixfmt` (include/rife_hip.h RIFE_HIP_PIX_*; rife-v4.6 for the 10-bit formats): the 10-bit gather code under the
+ * checks of the 8-bit one.  pixfmt = RIFE_HIP_PIX_RGB8: the calls above. */
+int rife_hip_v4_extract_flow_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, int fi, const float* const* inject,
+                                int n_inject, float* out6chw, int pixfmt);
+int rife_hip_v4_tap_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, int what, int b, const float* const* inject,
+                       int n_inject, float* out_chw, int pixfmt);
 
 /* ---- single-kernel entry points for per-kernel parity tests (host arrays, planar CHW fp32 like ncnn::Mat) --- */
 /* 3x3 conv, pad 1, stride 1|2, + bias, optional residual add (same shape as output), per-channel negative slope

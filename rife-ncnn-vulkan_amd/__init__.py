@@ -31,9 +31,13 @@ C_ABI_SYMBOLS = [
     "rife_hip_last_error", "rife_hip_profile_enable", "rife_hip_profile_read",
     "rife_hip_host_alloc", "rife_hip_host_free", "rife_hip_host_register", "rife_hip_host_unregister",
     "rife_hip_graph_check", "rife_hip_param_hash",
+    "rife_hip_frame_bytes", "rife_hip_process_px", "rife_hip_process_device_px", "rife_hip_process_device_batch_px", "rife_hip_frame_upload_px",
 ]
+# pixel formats at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*)
+PIX_RGB8, PIX_RGB10_U16, PIX_A2B10G10R10 = 0, 1, 2
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
-TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state"]
+TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
+                    "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px"]
 
 
 def build(force=False):
@@ -81,6 +85,12 @@ def _load(path, with_test_surface):
     L.rife_hip_host_free.argtypes = [vp]
     L.rife_hip_host_register.argtypes = [vp, ctypes.c_size_t]
     L.rife_hip_host_unregister.argtypes = [vp]
+    L.rife_hip_frame_bytes.restype = ctypes.c_size_t
+    L.rife_hip_frame_bytes.argtypes = [ci, ci, ci]
+    L.rife_hip_process_px.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci]
+    L.rife_hip_process_device_px.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, vp]
+    L.rife_hip_process_device_batch_px.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
+    L.rife_hip_frame_upload_px.argtypes = [vp, vp, ci, ci, ci, vp]
     if with_test_surface:
         L.rife_hip_v4_extract_flow.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp]
         L.rife_hip_v4_flow_dims.argtypes = [vp, ci, ci, ci, vp, vp, vp]
@@ -90,6 +100,8 @@ def _load(path, with_test_surface):
         L.rife_hip_op_deconv4x4.argtypes = [ci, vp, ci, ci, ci, vp, vp, ci, vp, vp]
         L.rife_hip_op_warp.argtypes = [ci, vp, vp, ci, ci, ci, vp]
         L.rife_hip_pool_state.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        L.rife_hip_v4_extract_flow_px.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp, ci]
+        L.rife_hip_v4_tap_px.argtypes = [vp, vp, vp, ci, ci, cf, ci, ci, vp, ci, vp, ci]
     return L
 
 
@@ -153,6 +165,18 @@ def graph_check(param_base):
     _check(lib().rife_hip_graph_check(param_base.encode()), "graph_check")
 
 
+def pack_a2b10g10r10(rgb10):
+    """(h, w, 3) uint16 codes -> (h, w) uint32 A2B10G10R10 (alpha 3); codes above 1023 are clamped like the engine reads them."""
+    c = np.minimum(np.asarray(rgb10, np.uint32), 1023)
+    return (c[..., 0] | (c[..., 1] << 10) | (c[..., 2] << 20) | np.uint32(0xc0000000)).astype(np.uint32)
+
+
+def unpack_a2b10g10r10(packed):
+    """(h, w) uint32 A2B10G10R10 -> (h, w, 3) uint16 codes."""
+    p = np.asarray(packed, np.uint32)
+    return np.stack([p & 1023, (p >> 10) & 1023, (p >> 20) & 1023], axis=-1).astype(np.uint16)
+
+
 def device_count():
     return lib().rife_hip_device_count()
 
@@ -180,11 +204,38 @@ def pinned_empty(shape, dtype=np.uint8):
     return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
 
 
+def frame_bytes(w, h, pixfmt=PIX_RGB8):
+    """rife_hip_frame_bytes: size of one w x h frame in `pixfmt` (0 for an unknown format)."""
+    return int(lib().rife_hip_frame_bytes(int(w), int(h), int(pixfmt)))
+
+
+_PIX_LAYOUT = {PIX_RGB8: (np.uint8, 3), PIX_RGB10_U16: (np.uint16, 3), PIX_A2B10G10R10: (np.uint32, 2)}      # dtype, ndim
+
+
+def _pix_of(image, pixfmt=None):
+    """The pixel format of a frame array: a uint16 (h, w, 3) array is RGB10_U16, a uint32 (h, w) array A2B10G10R10; None = neither (the 8-bit path, which
+    converts whatever it is given to uint8 as it always did).  An explicit `pixfmt` must match the array exactly.  Raises before any library call."""
+    a = image
+    if pixfmt is None:
+        if not isinstance(a, np.ndarray) or a.dtype not in (np.uint16, np.uint32):
+            return None
+        pixfmt = PIX_RGB10_U16 if a.dtype == np.uint16 else PIX_A2B10G10R10
+    if pixfmt not in _PIX_LAYOUT:
+        raise ValueError("unknown pixfmt %r" % (pixfmt,))
+    if pixfmt == PIX_RGB8:
+        return None
+    dt, nd = _PIX_LAYOUT[pixfmt]
+    if not isinstance(a, np.ndarray) or a.dtype != dt or a.ndim != nd or (nd == 3 and a.shape[2] != 3) or a.size == 0:
+        raise ValueError("a %s frame is a %s array of shape %s" % ("RGB10_U16" if pixfmt == PIX_RGB10_U16 else "A2B10G10R10", np.dtype(dt).name,
+                                                                   "(h, w, 3)" if nd == 3 else "(h, w)"))
+    return pixfmt
+
+
 class Frame:
     """A frame resident in device memory (rife_hip_frame_t): upload once, use as either side of any number of pairs."""
 
-    def __init__(self, handle, w, h, L=None):
-        self._f, self.w, self.h, self._L = handle, w, h, L or lib()
+    def __init__(self, handle, w, h, L=None, pixfmt=PIX_RGB8):
+        self._f, self.w, self.h, self._L, self.pixfmt = handle, w, h, L or lib(), pixfmt
 
     def release(self):
         if getattr(self, "_f", None) and getattr(self, "_L", None) is not None:
@@ -218,8 +269,21 @@ class RIFE:
         _check(self._L.rife_hip_load(self._h, os.fspath(modeldir).encode()), "load", self._L)
         return 0
 
-    def process(self, in0image, in1image, timestep, outimage=None):
-        """in0image / in1image: (h, w, 3) uint8 RGB arrays (the ncnn::Mat the CLI builds, src/main.cpp:187)."""
+    def process(self, in0image, in1image, timestep, outimage=None, pixfmt=None):
+        """in0image / in1image: (h, w, 3) uint8 RGB arrays (the ncnn::Mat the CLI builds, src/main.cpp:187).
+        Deep colour (rife-v4.6, plain mode): (h, w, 3) uint16 arrays of codes 0..1023 (RGB10_U16) or (h, w) uint32 arrays (A2B10G10R10), selected by the
+        arrays' dtype or by pixfmt=; the result has the inputs' format."""
+        px = _pix_of(in0image, pixfmt)
+        if px is not None:
+            if _pix_of(in1image, px) != px or in1image.shape != in0image.shape:
+                raise ValueError("both frames must have the same pixel format and size")
+            a = np.ascontiguousarray(in0image); b = np.ascontiguousarray(in1image)
+            h, w = a.shape[:2]
+            out = outimage if outimage is not None else np.empty_like(a)
+            if not isinstance(out, np.ndarray) or out.shape != a.shape or out.dtype != a.dtype or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError("outimage must be a writable contiguous array of the frames' dtype and shape")
+            _check(self._L.rife_hip_process_px(self._h, _p(a), _p(b), w, h, float(timestep), _p(out), px), "process_px", self._L)
+            return out
         a = np.ascontiguousarray(in0image, dtype=np.uint8)
         b = np.ascontiguousarray(in1image, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] != 3 or a.shape != b.shape:
@@ -231,8 +295,15 @@ class RIFE:
         _check(self._L.rife_hip_process(self._h, _p(a), _p(b), w, h, float(timestep), _p(out)), "process", self._L)
         return out
 
-    def upload(self, image):
-        """Stream mode: copy one (h, w, 3) uint8 frame to the device and keep it there."""
+    def upload(self, image, pixfmt=None):
+        """Stream mode: copy one (h, w, 3) uint8 frame to the device and keep it there (deep colour: a uint16 (h, w, 3) or uint32 (h, w)
+        array, see process())."""
+        px = _pix_of(image, pixfmt)
+        if px is not None:
+            a = np.ascontiguousarray(image)
+            f = ctypes.c_void_p()
+            _check(self._L.rife_hip_frame_upload_px(self._h, _p(a), a.shape[1], a.shape[0], px, ctypes.byref(f)), "frame_upload_px", self._L)
+            return Frame(f, a.shape[1], a.shape[0], self._L, px)
         a = np.ascontiguousarray(image, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("frame must be an (h, w, 3) uint8 array")
@@ -244,14 +315,29 @@ class RIFE:
         """process() between two resident frames; same pixels as process() on the host arrays they were uploaded from."""
         if frame0._f is None or frame1._f is None:
             raise ValueError("frame was released")
+        if frame0.pixfmt != frame1.pixfmt:
+            raise ValueError("the two frames differ in pixel format")
+        if frame0.pixfmt != PIX_RGB8:      # the result has the format the frames were uploaded in
+            dt, nd = _PIX_LAYOUT[frame0.pixfmt]
+            shape = (frame0.h, frame0.w, 3) if nd == 3 else (frame0.h, frame0.w)
+            out = outimage if outimage is not None else np.empty(shape, dt)
+            if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dt or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError("outimage must be a writable contiguous array of the frames' format and size")
+            _check(self._L.rife_hip_process_frames(self._h, frame0._f, frame1._f, float(timestep), _p(out)), "process_frames", self._L)
+            return out
         out = outimage if outimage is not None else np.empty((frame0.h, frame0.w, 3), np.uint8)
         if out.shape != (frame0.h, frame0.w, 3) or out.dtype != np.uint8 or not out.flags.c_contiguous:
             raise ValueError("outimage must be a contiguous (h, w, 3) uint8 array of the frames' size")
         _check(self._L.rife_hip_process_frames(self._h, frame0._f, frame1._f, float(timestep), _p(out)), "process_frames", self._L)
         return out
 
-    def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None):
-        """Device pointers (ints) to tightly packed u8 HWC RGB frames; enqueues on `stream` (hipStream_t as int)."""
+    def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
+        """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
+        if pixfmt not in _PIX_LAYOUT:
+            raise ValueError("unknown pixfmt %r" % (pixfmt,))
+        if pixfmt != PIX_RGB8:
+            _check(self._L.rife_hip_process_device_px(self._h, d_in0, d_in1, w, h, float(timestep), d_out, pixfmt, stream), "process_device_px", self._L)
+            return
         _check(self._L.rife_hip_process_device(self._h, d_in0, d_in1, w, h, float(timestep), d_out, stream), "process_device", self._L)
 
     def stream_create(self, part, nparts):
@@ -263,8 +349,10 @@ class RIFE:
     def stream_destroy(self, stream):
         _check(self._L.rife_hip_stream_destroy(self._h, stream), "stream_destroy", self._L)
 
-    def process_device_batch(self, d_in0, d_in1, w, h, timesteps, d_out, stream=None):
+    def process_device_batch(self, d_in0, d_in1, w, h, timesteps, d_out, stream=None, pixfmt=PIX_RGB8):
         """n resident pairs in one call (rife_hip_process_device_batch): lists of device pointers; enqueued relative to `stream`."""
+        if pixfmt not in _PIX_LAYOUT:
+            raise ValueError("unknown pixfmt %r" % (pixfmt,))
         n = len(d_in0)
         if len(d_in1) != n or len(d_out) != n or len(timesteps) != n:
             raise ValueError("one in1 / out / timestep per pair")
@@ -272,6 +360,9 @@ class RIFE:
         pb = (ctypes.c_void_p * n)(*[int(x) for x in d_in1])
         po = (ctypes.c_void_p * n)(*[int(x) for x in d_out])
         ts = (ctypes.c_float * n)(*[float(t) for t in timesteps])
+        if pixfmt != PIX_RGB8:
+            _check(self._L.rife_hip_process_device_batch_px(self._h, n, pa, pb, ts, po, w, h, pixfmt, stream), "process_device_batch_px", self._L)
+            return
         _check(self._L.rife_hip_process_device_batch(self._h, n, pa, pb, ts, po, w, h, stream), "process_device_batch", self._L)
 
     # ---- measurement / parity taps ----
@@ -317,31 +408,49 @@ class RIFE:
         _check(self._L.rife_hip_pool_state(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "pool_state", self._L)
         return a.value, b.value, c.value
 
-    def v4_extract_flow(self, in0image, in1image, timestep, fi, inject=()):
+    def v4_extract_flow(self, in0image, in1image, timestep, fi, inject=(), pixfmt=None):
         self._need_taps()
-        a = np.ascontiguousarray(in0image, dtype=np.uint8); b = np.ascontiguousarray(in1image, dtype=np.uint8)
-        h, w, _ = a.shape
+        px = _pix_of(in0image, pixfmt)
+        if px is not None and _pix_of(in1image, px) != px:
+            raise ValueError("both frames must have the same pixel format")
+        if px is not None:
+            a = np.ascontiguousarray(in0image); b = np.ascontiguousarray(in1image)
+        else:
+            a = np.ascontiguousarray(in0image, dtype=np.uint8); b = np.ascontiguousarray(in1image, dtype=np.uint8)
+        h, w = a.shape[:2]
         nc, fh, fw = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _check(self._L.rife_hip_v4_flow_dims(self._h, w, h, fi, ctypes.byref(nc), ctypes.byref(fh), ctypes.byref(fw)), "v4_flow_dims", self._L)
         out = np.empty((nc.value, fh.value, fw.value), np.float32)
         inj = [np.ascontiguousarray(f, dtype=np.float32) for f in inject]
         arr = (ctypes.c_void_p * max(1, len(inj)))(*[f.ctypes.data for f in inj])
+        if px is not None:
+            _check(self._L.rife_hip_v4_extract_flow_px(self._h, _p(a), _p(b), w, h, float(timestep), fi, arr, len(inj), _p(out), px), "v4_extract_flow_px", self._L)
+            return out
         _check(self._L.rife_hip_v4_extract_flow(self._h, _p(a), _p(b), w, h, float(timestep), fi, arr, len(inj), _p(out)), "v4_extract_flow", self._L)
         return out
 
 
-    def v4_tap(self, in0image, in1image, timestep, what, b, inject):
+    def v4_tap(self, in0image, in1image, timestep, what, b, inject, pixfmt=None):
         """what 0 / 1: 12-channel input of IFBlock b (unfused kernel / through the fused stem kernel); 2: blob out0 before the postproc;
         4 / 3: F (4 channels) and M as block b's stem finds them, after k_flow_update / as written by the stem that applies the last update itself;
         5 (b = 3): the block input through the row-streaming stem kernel of the product."""
         self._need_taps()
-        a = np.ascontiguousarray(in0image, dtype=np.uint8); bb = np.ascontiguousarray(in1image, dtype=np.uint8)
-        h, w, _ = a.shape
+        px = _pix_of(in0image, pixfmt)
+        if px is not None and _pix_of(in1image, px) != px:
+            raise ValueError("both frames must have the same pixel format")
+        if px is not None:
+            a = np.ascontiguousarray(in0image); bb = np.ascontiguousarray(in1image)
+        else:
+            a = np.ascontiguousarray(in0image, dtype=np.uint8); bb = np.ascontiguousarray(in1image, dtype=np.uint8)
+        h, w = a.shape[:2]
         wp, hp = (w + 31) // 32 * 32, (h + 31) // 32 * 32
         s = {1: 4, 2: 2, 3: 1}.get(b, 1)
         out = np.empty((3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4) else (12, hp // s, wp // s), np.float32)
         inj = [np.ascontiguousarray(f, dtype=np.float32) for f in inject]
         arr = (ctypes.c_void_p * max(1, len(inj)))(*[f.ctypes.data for f in inj])
+        if px is not None:
+            _check(self._L.rife_hip_v4_tap_px(self._h, _p(a), _p(bb), w, h, float(timestep), int(what), int(b), arr, len(inj), _p(out), px), "v4_tap_px", self._L)
+            return out
         _check(self._L.rife_hip_v4_tap(self._h, _p(a), _p(bb), w, h, float(timestep), int(what), int(b), arr, len(inj), _p(out)), "v4_tap", self._L)
         return out
 

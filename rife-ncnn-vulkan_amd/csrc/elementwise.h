@@ -42,7 +42,68 @@ __global__ void k_preproc4(const uint8_t* __restrict__ rgb, int w, int h, uint32
     *reinterpret_cast<uint4*>(out + (size_t)y * wp + x4) = v;
 }
 
+// Deep colour (D = 10): the same dword holds 10:10:10 codes (R bits 0-9, G 10-19, B 20-29, the top two bits zero), value = code * (1 / 1023.f).  A tap stays
+// one dword for all three channels, so every gather kernel moves the bytes it moves at depth 8.  (12- / 16-bit samples need a second dword per pixel.)
+// ---- deep colour, include/rife_hip.h RIFE_HIP_PIX_RGB10_U16 / RIFE_HIP_PIX_A2B10G10R10 -> zero-padded 10:10:10 dwords.  A u16 sample above 1023 is read as
+// 1023 (its high bits would spill into the neighbouring channel); the alpha bits of a packed pixel are dropped. ----
+__device__ __forceinline__ uint32_t pack10(uint32_t r, uint32_t g, uint32_t b) { return min(r, 1023u) | (min(g, 1023u) << 10) | (min(b, 1023u) << 20); }
+__global__ void k_preproc10_u16(const uint16_t* __restrict__ rgb, int w, int h, uint32_t* __restrict__ out, int wp, int hp) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= wp) return;
+    uint32_t v = 0;
+    if (x < w && y < h) {
+        const uint16_t* p = rgb + ((size_t)y * w + x) * 3;
+        v = pack10(p[0], p[1], p[2]);
+    }
+    out[(size_t)y * wp + x] = v;
+}
+// four pixels per lane (w % 4 == 0 - a row is then a multiple of 24 bytes - and an 8-byte aligned frame): 24 contiguous bytes in, one 16-byte store out
+__global__ void k_preproc10_u16x4(const uint16_t* __restrict__ rgb, int w, int h, uint32_t* __restrict__ out, int wp, int hp) {
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
+    if (x4 >= wp) return;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (x4 < w && y < h) {
+        uint2 q[3];
+        __builtin_memcpy(q, __builtin_assume_aligned(rgb + ((size_t)y * w + x4) * 3, 8), 24);
+        v.x = pack10(q[0].x & 0xffffu, q[0].x >> 16, q[0].y & 0xffffu);
+        v.y = pack10(q[0].y >> 16, q[1].x & 0xffffu, q[1].x >> 16);
+        v.z = pack10(q[1].y & 0xffffu, q[1].y >> 16, q[2].x & 0xffffu);
+        v.w = pack10(q[2].x >> 16, q[2].y & 0xffffu, q[2].y >> 16);
+    }
+    *reinterpret_cast<uint4*>(out + (size_t)y * wp + x4) = v;
+}
+__global__ void k_preproc10_packed(const uint32_t* __restrict__ px, int w, int h, uint32_t* __restrict__ out, int wp, int hp) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= wp) return;
+    out[(size_t)y * wp + x] = (x < w && y < h) ? (px[(size_t)y * w + x] & 0x3fffffffu) : 0u;
+}
+// four pixels per lane (w % 4 == 0 and a 16-byte aligned frame): one 16-byte load, one 16-byte store
+__global__ void k_preproc10_packedx4(const uint32_t* __restrict__ px, int w, int h, uint32_t* __restrict__ out, int wp, int hp) {
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
+    if (x4 >= wp) return;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (x4 < w && y < h) {
+        v = *reinterpret_cast<const uint4*>(px + (size_t)y * w + x4);
+        v.x &= 0x3fffffffu; v.y &= 0x3fffffffu; v.z &= 0x3fffffffu; v.w &= 0x3fffffffu;
+    }
+    *reinterpret_cast<uint4*>(out + (size_t)y * wp + x4) = v;
+}
+// timestep 0 / 1 at depth 10: the frame itself in canonical form (samples clamped to 1023 / alpha bits 3); n = samples (u16) or pixels (packed)
+__global__ void k_canon10_u16(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (uint16_t)min((uint32_t)in[i], 1023u);
+}
+__global__ void k_canon10_packed(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = in[i] | 0xc0000000u;
+}
+
+template <int D = 8>
 __device__ __forceinline__ float3 unpack_rgb(uint32_t v) {
+    if (D == 10) {
+        const float k10 = 1 / 1023.f;
+        return make_float3((float)(v & 0x3ff) * k10, (float)((v >> 10) & 0x3ff) * k10, (float)((v >> 20) & 0x3ff) * k10);
+    }
     const float k = 1 / 255.f;
     return make_float3((float)(v & 0xff) * k, (float)((v >> 8) & 0xff) * k, (float)((v >> 16) & 0xff) * k);
 }
@@ -100,12 +161,14 @@ __device__ __forceinline__ WarpLoads warp_issue(const uint32_t* __restrict__ img
     t.l0 = x0 == xb; t.l1 = x1 == xb;
     return t;
 }
+template <int D = 8>
 __device__ __forceinline__ float3 warp_finish(const WarpLoads& t) {
-    const float3 a = unpack_rgb(t.l0 ? t.r0.x : t.r0.y), b = unpack_rgb(t.l1 ? t.r0.x : t.r0.y), c = unpack_rgb(t.l0 ? t.r1.x : t.r1.y), d = unpack_rgb(t.l1 ? t.r1.x : t.r1.y);
+    const float3 a = unpack_rgb<D>(t.l0 ? t.r0.x : t.r0.y), b = unpack_rgb<D>(t.l1 ? t.r0.x : t.r0.y), c = unpack_rgb<D>(t.l0 ? t.r1.x : t.r1.y), d = unpack_rgb<D>(t.l1 ? t.r1.x : t.r1.y);
     return make_float3(warp_lerp(a.x, b.x, c.x, d.x, t.alpha, t.beta), warp_lerp(a.y, b.y, c.y, d.y, t.alpha, t.beta), warp_lerp(a.z, b.z, c.z, d.z, t.alpha, t.beta));
 }
+template <int D = 8>
 __device__ __forceinline__ float3 warp_rgbx(const uint32_t* __restrict__ img, int x, int y, float fx, float fy, int w, int h) {
-    return warp_finish(warp_issue(img, x, y, fx, fy, w, h));
+    return warp_finish<D>(warp_issue(img, x, y, fx, fy, w, h));
 }
 
 // generic rife.Warp on planar CHW fp32 (per-kernel parity test entry point; v2.3 context features)
@@ -130,16 +193,17 @@ __device__ __forceinline__ float down4(float v00, float v01, float v10, float v1
 
 // Block-0 input: x = Interp(1/8)(Concat(in0, in1, in2)) -> NHWC8 {in0.rgb, in1.rgb, t, 0}   (flownet.param:9-10)
 // `tsp` != null: the timestep is read from device memory (hipGraph replays need launch parameters that never change)
-__global__ void k_assemble0(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep_arg, const float* __restrict__ tsp,
-                            float* __restrict__ X, int wp, int hp) {
+template <int D>
+__device__ __forceinline__ void assemble0_body(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep_arg, const float* __restrict__ tsp,
+                                               float* __restrict__ X, int wp, int hp) {
     const float timestep = tsp ? *tsp : timestep_arg;
     const int Wb = wp / 8, Hb = hp / 8;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= Wb || y >= Hb) return;
     const int sx = 8 * x + 3, sy = 8 * y + 3;
     const size_t i00 = (size_t)sy * wp + sx, i10 = i00 + wp;
-    const float3 a0 = unpack_rgb(img0[i00]), a1 = unpack_rgb(img0[i00 + 1]), a2 = unpack_rgb(img0[i10]), a3 = unpack_rgb(img0[i10 + 1]);
-    const float3 b0 = unpack_rgb(img1[i00]), b1 = unpack_rgb(img1[i00 + 1]), b2 = unpack_rgb(img1[i10]), b3 = unpack_rgb(img1[i10 + 1]);
+    const float3 a0 = unpack_rgb<D>(img0[i00]), a1 = unpack_rgb<D>(img0[i00 + 1]), a2 = unpack_rgb<D>(img0[i10]), a3 = unpack_rgb<D>(img0[i10 + 1]);
+    const float3 b0 = unpack_rgb<D>(img1[i00]), b1 = unpack_rgb<D>(img1[i00 + 1]), b2 = unpack_rgb<D>(img1[i10]), b3 = unpack_rgb<D>(img1[i10 + 1]);
     float4 o0, o1;
     o0.x = down4(a0.x, a1.x, a2.x, a3.x); o0.y = down4(a0.y, a1.y, a2.y, a3.y); o0.z = down4(a0.z, a1.z, a2.z, a3.z);
     o0.w = down4(b0.x, b1.x, b2.x, b3.x); o1.x = down4(b0.y, b1.y, b2.y, b3.y); o1.y = down4(b0.z, b1.z, b2.z, b3.z);
@@ -147,6 +211,14 @@ __global__ void k_assemble0(const uint32_t* __restrict__ img0, const uint32_t* _
     o1.w = 0.f;
     float4* dst = reinterpret_cast<float4*>(X + ((size_t)y * Wb + x) * 8);
     dst[0] = o0; dst[1] = o1;
+}
+__global__ void k_assemble0(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep_arg, const float* __restrict__ tsp,
+                            float* __restrict__ X, int wp, int hp) {
+    assemble0_body<8>(img0, img1, timestep_arg, tsp, X, wp, hp);
+}
+__global__ void k_assemble0_d10(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep_arg, const float* __restrict__ tsp,
+                                float* __restrict__ X, int wp, int hp) {
+    assemble0_body<10>(img0, img1, timestep_arg, tsp, X, wp, hp);
 }
 
 // ncnn linear_coeffs for an upscale by S (power of two): fx = (dx + 0.5) / S - 0.5 is exact in fp32 here
@@ -214,7 +286,7 @@ struct FlowPending {
 // UPD = 2 (round 5; block 1): F, M do not exist yet - they are what k_flow_update<2 S, FIRST> would have written from the first flow, computed here for the pixels
 // that are sampled (F = Interp(2 S)(flow0) * 2 S, M = its mask channel: flow0 is [hp / 8][wp / 8][8] fp32, L2-resident) and written nowhere; k_flow_update2
 // produces the full-resolution tensors after this block in one pass together with this block's own update.
-template <int S, int UPD = 0>
+template <int S, int UPD = 0, int D = 8>
 __device__ __forceinline__ void assemble_pixel(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep,
                                                const float4* __restrict__ F, const float* __restrict__ M, int wp, int hp, int x, int y, float o[12],
                                                const FlowPending& pend = FlowPending{}) {
@@ -229,8 +301,8 @@ __device__ __forceinline__ void assemble_pixel(const uint32_t* __restrict__ img0
             flow_accumulate<2 * S>(u, um, f, mk);
             pend.Fw[i] = f; pend.Mw[i] = mk;
         }
-        const float3 w0 = warp_rgbx(img0, x, y, f.x, f.y, wp, hp);
-        const float3 w1 = warp_rgbx(img1, x, y, f.z, f.w, wp, hp);
+        const float3 w0 = warp_rgbx<D>(img0, x, y, f.x, f.y, wp, hp);
+        const float3 w1 = warp_rgbx<D>(img1, x, y, f.z, f.w, wp, hp);
         o[0] = w0.x; o[1] = w0.y; o[2] = w0.z; o[3] = w1.x; o[4] = w1.y; o[5] = w1.z; o[6] = timestep; o[7] = mk;
         o[8] = f.x; o[9] = f.y; o[10] = f.z; o[11] = f.w;
     } else {
@@ -249,8 +321,8 @@ __device__ __forceinline__ void assemble_pixel(const uint32_t* __restrict__ img0
                 flow_accumulate<2 * S>(u, um, f, mk);
                 pend.Fw[i] = f; pend.Mw[i] = mk;
             }
-            const float3 w0 = warp_rgbx(img0, px, py, f.x, f.y, wp, hp);
-            const float3 w1 = warp_rgbx(img1, px, py, f.z, f.w, wp, hp);
+            const float3 w0 = warp_rgbx<D>(img0, px, py, f.x, f.y, wp, hp);
+            const float3 w1 = warp_rgbx<D>(img1, px, py, f.z, f.w, wp, hp);
             v[k][0] = w0.x; v[k][1] = w0.y; v[k][2] = w0.z; v[k][3] = w1.x; v[k][4] = w1.y; v[k][5] = w1.z;
             v[k][6] = timestep; v[k][7] = mk;
             v[k][8] = f.x; v[k][9] = f.y; v[k][10] = f.z; v[k][11] = f.w;
@@ -262,7 +334,7 @@ __device__ __forceinline__ void assemble_pixel(const uint32_t* __restrict__ img0
     }
 }
 
-template <int S>
+template <int S, int D = 8>
 __global__ void k_assemble(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep_arg, const float* __restrict__ tsp,
                            const float4* __restrict__ F, const float* __restrict__ M, float* __restrict__ X, int wp, int hp) {
     const float timestep = tsp ? *tsp : timestep_arg;
@@ -270,7 +342,7 @@ __global__ void k_assemble(const uint32_t* __restrict__ img0, const uint32_t* __
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= Wb || y >= Hb) return;
     float o[12];
-    assemble_pixel<S>(img0, img1, timestep, F, M, wp, hp, x, y, o);
+    assemble_pixel<S, 0, D>(img0, img1, timestep, F, M, wp, hp, x, y, o);
     float4* dst = reinterpret_cast<float4*>(X + ((size_t)y * Wb + x) * 16);
     dst[0] = make_float4(o[0], o[1], o[2], o[3]);
     dst[1] = make_float4(o[4], o[5], o[6], o[7]);
@@ -322,8 +394,25 @@ __global__ void k_flow_update2(const float* __restrict__ flow0, const float* __r
 // Tail of the graph + postproc (flownet.param:202-217, rife.cpp:4373-4397 / rife_postproc.comp:39-62):
 //   F += flow3[0:4]; M += flow3[4]; m = sigmoid(M); out = warp(in0,F.xy)*m + warp(in1,F.zw)*(1-m);
 //   u8 = clamp((int)(out*255 + 0.5), 0, 255), cropped to w x h, HWC RGB.
-__global__ void k_final(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
-                        const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
+// PX (include/rife_hip.h RIFE_HIP_PIX_*): 0 = u8 RGB; 1 = three u16 codes 0..1023 per pixel; 2 = one A2B10G10R10 dword per pixel (alpha written as 3).
+// The 10-bit forms read 10:10:10 frames and quantise as min(max((int)(v * 1023.f + 0.5f), 0), 1023), straight into the caller's format.
+__device__ __forceinline__ uint32_t quant10(float r, float g, float b) {
+    return (uint32_t)min(max((int)(r * 1023.f + 0.5f), 0), 1023) | ((uint32_t)min(max((int)(g * 1023.f + 0.5f), 0), 1023) << 10) |
+           ((uint32_t)min(max((int)(b * 1023.f + 0.5f), 0), 1023) << 20);
+}
+// one pixel of a 10-bit output frame: pk = 10:10:10 codes; `out` is the frame, i the pixel index (y * w + x)
+template <int PX>
+__device__ __forceinline__ void store_px10(uint8_t* __restrict__ out, size_t i, uint32_t pk) {
+    if (PX == 2) reinterpret_cast<uint32_t*>(out)[i] = pk | 0xc0000000u;
+    else {
+        uint16_t* o = reinterpret_cast<uint16_t*>(out) + i * 3;
+        o[0] = (uint16_t)(pk & 0x3ffu); o[1] = (uint16_t)((pk >> 10) & 0x3ffu); o[2] = (uint16_t)((pk >> 20) & 0x3ffu);
+    }
+}
+template <int PX>
+__device__ __forceinline__ void final_body(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                                           const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
+    constexpr int D = PX ? 10 : 8;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * wp + x;
@@ -334,13 +423,23 @@ __global__ void k_final(const uint32_t* __restrict__ img0, const uint32_t* __res
     const float mm = M[i] + fl[4];
     const float m = 1.f / (1.f + expf(-mm));
     const float rm = 1.0f - m;
-    const float3 w1 = warp_rgbx(img1, x, y, f.z, f.w, wp, hp);
-    const float3 w0 = warp_rgbx(img0, x, y, f.x, f.y, wp, hp);
+    const float3 w1 = warp_rgbx<D>(img1, x, y, f.z, f.w, wp, hp);
+    const float3 w0 = warp_rgbx<D>(img0, x, y, f.x, f.y, wp, hp);
     const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
+    if (PX) { store_px10<PX>(out, (size_t)y * w + x, quant10(r, g, b)); return; }
     uint8_t* o = out + ((size_t)y * w + x) * 3;
     o[0] = (uint8_t)min(max((int)(r * 255.f + 0.5f), 0), 255);
     o[1] = (uint8_t)min(max((int)(g * 255.f + 0.5f), 0), 255);
     o[2] = (uint8_t)min(max((int)(b * 255.f + 0.5f), 0), 255);
+}
+__global__ void k_final(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                        const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
+    final_body<0>(img0, img1, F, M, flow3, out, w, h, wp, hp);
+}
+template <int PX>
+__global__ void k_final_px(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                           const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
+    final_body<PX>(img0, img1, F, M, flow3, out, w, h, wp, hp);
 }
 
 // rife-v4 (4.0) tail (models/rife-v4/flownet.param:154-168): F and M are final after the block-3 flow update;
@@ -506,8 +605,9 @@ __global__ void k_v4_consensus(Ptr8x2 fl, int W, int H) {
 }
 
 // tail of the graph without postproc: out0 (3 x hp x wp) kept as float4 per padded pixel, for the TTA averaging
-__global__ void k_final_float(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
-                              const float* __restrict__ M, const float* __restrict__ flow3, float4* __restrict__ out, int wp, int hp) {
+template <int D>
+__device__ __forceinline__ void final_float_body(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                                                 const float* __restrict__ M, const float* __restrict__ flow3, float4* __restrict__ out, int wp, int hp) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= wp) return;
     const size_t i = (size_t)y * wp + x;
@@ -518,9 +618,17 @@ __global__ void k_final_float(const uint32_t* __restrict__ img0, const uint32_t*
     const float mm = M[i] + fl[4];
     const float m = 1.f / (1.f + expf(-mm));
     const float rm = 1.0f - m;
-    const float3 w1 = warp_rgbx(img1, x, y, f.z, f.w, wp, hp);
-    const float3 w0 = warp_rgbx(img0, x, y, f.x, f.y, wp, hp);
+    const float3 w1 = warp_rgbx<D>(img1, x, y, f.z, f.w, wp, hp);
+    const float3 w0 = warp_rgbx<D>(img0, x, y, f.x, f.y, wp, hp);
     out[i] = make_float4(w0.x * m + w1.x * rm, w0.y * m + w1.y * rm, w0.z * m + w1.z * rm, 0.f);
+}
+__global__ void k_final_float(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                              const float* __restrict__ M, const float* __restrict__ flow3, float4* __restrict__ out, int wp, int hp) {
+    final_float_body<8>(img0, img1, F, M, flow3, out, wp, hp);
+}
+__global__ void k_final_float_d10(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                                  const float* __restrict__ M, const float* __restrict__ flow3, float4* __restrict__ out, int wp, int hp) {
+    final_float_body<10>(img0, img1, F, M, flow3, out, wp, hp);
 }
 
 // gather nori (1 | 8) orientations x ntemp (1 | 2) directions of out0 back to the base frame, average, postproc.

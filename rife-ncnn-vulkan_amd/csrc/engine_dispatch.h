@@ -119,6 +119,10 @@ static int launch_conv(const ConvLayer& L, TensorView x, int H, int W, TensorVie
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_DECONV_SIG>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_DECONV_PS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
                 hdone[dev] = true;
             }
@@ -127,7 +131,14 @@ static int launch_conv(const ConvLayer& L, TensorView x, int H, int W, TensorVie
         if (L.epi == EPI_DECONV_PS && (L.cout != 24 || y.ld != 8 || y.coff != 0))
             return fail(RIFE_HIP_EINVAL, "the PixelShuffle head kernel writes the 6-channel flow tensor [4H][4W][8] only");
         if (s16_pitch > 0 && L.epi != EPI_DECONV_PS) return fail(RIFE_HIP_EINVAL, "no S16 variant of this head");
-        if (s16_pitch > 0 && fin) hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, true>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
+        if (fin && fin->pixfmt && L.epi == EPI_DECONV_PS) {      // deep colour: 10:10:10 frames in, the caller's 10-bit format out
+            const bool u16 = fin->pixfmt == RIFE_HIP_PIX_RGB10_U16;
+            if (s16_pitch > 0 && u16) hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, true, 1>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
+            else if (s16_pitch > 0) hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, true, 2>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
+            else if (u16) hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, false, 1>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
+            else hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, false, 2>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
+        }
+        else if (s16_pitch > 0 && fin) hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, true>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
         else if (s16_pitch > 0) hipLaunchKernelGGL((head_h2_kernel<EPI_DECONV_PS, true>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, FinalArgs{});
         else if (fin && L.epi == EPI_DECONV_PS) hipLaunchKernelGGL(head_h2_kernel<EPI_FINAL>, dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
         else if (L.epi == EPI_DECONV_PS) hipLaunchKernelGGL(head_h2_kernel<EPI_DECONV_PS>, dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, FinalArgs{});

@@ -14,8 +14,9 @@ static std::atomic<bool> g_fuse_flow_buffers{false};                 // some eng
 // (Re)allocate a workspace for frames of w x h (padded wp x hp).  `scratch` != null: borrow the big per-layer
 // scratch tensors (block input, stem output, trunk ping/pong) from another context of the same pixel count —
 // the TTA passes run one after another on one stream, only flows / F / M / images must persist per pass.
-static int ensure_ctx_dims_impl(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch, bool own_images, bool want_outf) {
-    if (!c.v2 && c.wp == wp && c.hp == hp && c.w == w && c.h == h && (!want_outf || c.outf)) return 0;
+static int ensure_ctx_dims_impl(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch, bool own_images, bool want_outf, int bpp) {
+    if (!c.v2 && c.wp == wp && c.hp == hp && c.w == w && c.h == h && (!want_outf || c.outf) && (scratch || c.stage_bpp >= bpp)) return 0;
+    c.stage_bpp = bpp;
     c.v2 = false;
     if (c.gexec) { (void)hipGraphExecDestroy(c.gexec); c.gexec = nullptr; }
     c.g_warm = false; c.d_ts = nullptr;
@@ -32,9 +33,9 @@ static int ensure_ctx_dims_impl(Ctx& c, int w, int h, int wp, int hp, const Ctx*
     }
     if (scratch) { c.X = scratch->X; c.S1 = scratch->S1; c.T0 = scratch->T0; c.T1 = scratch->T1; c.T2 = scratch->T2; }
     else {
-        if ((rc = dalloc(c, c.d_in0, (size_t)w * h * 3))) return rc;
-        if ((rc = dalloc(c, c.d_in1, (size_t)w * h * 3))) return rc;
-        if ((rc = dalloc(c, c.d_out, (size_t)w * h * 3))) return rc;
+        if ((rc = dalloc(c, c.d_in0, (size_t)w * h * bpp))) return rc;
+        if ((rc = dalloc(c, c.d_in1, (size_t)w * h * bpp))) return rc;
+        if ((rc = dalloc(c, c.d_out, (size_t)w * h * bpp))) return rc;
         if ((rc = dalloc(c, c.X, P * 16))) return rc;                  // block 3: full res x 16 ch
         if ((rc = dalloc(c, c.S1, P / 4 * 32))) return rc;             // block 3 stem-0 output: (hp/2 x wp/2) x 32
         if ((rc = dalloc(c, c.T0, P / 16 * 64))) return rc;            // block 3 trunk: (hp/4 x wp/4) x 64 (the largest trunk)
@@ -68,16 +69,21 @@ static void reset_ctx(Ctx& c) {
     if (c.gexec) { (void)hipGraphExecDestroy(c.gexec); c.gexec = nullptr; }
     for (void* p : c.allocs) (void)hipFree(p);
     c.allocs.clear();
-    c.w = c.h = c.wp = c.hp = 0; c.v2 = false; c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.d_ts = nullptr; c.g_warm = false; for (auto& pb : c.P) pb[0] = pb[1] = nullptr;
+    c.w = c.h = c.wp = c.hp = 0; c.stage_bpp = 0; c.v2 = false; c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.d_ts = nullptr; c.g_warm = false; for (auto& pb : c.P) pb[0] = pb[1] = nullptr;
 }
-static int ensure_ctx_dims(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch = nullptr, bool own_images = true, bool want_outf = false) {
-    const int rc = ensure_ctx_dims_impl(c, w, h, wp, hp, scratch, own_images, want_outf);
+static int ensure_ctx_dims(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch = nullptr, bool own_images = true, bool want_outf = false, int bpp = 3) {
+    const int rc = ensure_ctx_dims_impl(c, w, h, wp, hp, scratch, own_images, want_outf, bpp);
     if (rc) reset_ctx(c);
     return rc;
 }
 
-static int ensure_ctx(Ctx& c, int w, int h) {
-    return ensure_ctx_dims(c, w, h, (w + 31) / 32 * 32, (h + 31) / 32 * 32);   // pad to 32n, rife.cpp:2499-2500
+// bytes per pixel of a frame at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*); 0 = unknown format
+static inline int pix_bpp(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB8 ? 3 : pixfmt == RIFE_HIP_PIX_RGB10_U16 ? 6 : pixfmt == RIFE_HIP_PIX_A2B10G10R10 ? 4 : 0; }
+// the workspace serves frames of `pixfmt` from here on: staging buffers of that size, c.pixfmt for every launch site that reads or writes a frame
+static int ensure_ctx(Ctx& c, int w, int h, int pixfmt = RIFE_HIP_PIX_RGB8) {
+    const int rc = ensure_ctx_dims(c, w, h, (w + 31) / 32 * 32, (h + 31) / 32 * 32, nullptr, true, false, pix_bpp(pixfmt));   // pad to 32n, rife.cpp:2499-2500
+    if (!rc) c.pixfmt = pixfmt;
+    return rc;
 }
 
 struct Timed {
@@ -92,7 +98,19 @@ static inline dim3 grid2d(int w, int h) { return dim3((w + 255) / 256, h); }
 static inline dim3 tta_block(int elem_bytes) { return elem_bytes >= 16 ? dim3(8, 32) : dim3(16, 16); }
 static inline dim3 tta_grid(int w, int h, int elem_bytes) { const dim3 b = tta_block(elem_bytes); return dim3((w + b.x - 1) / b.x, (h + b.y - 1) / b.y); }
 // rife_preproc.comp: u8 HWC RGB -> zero-padded RGBX; four pixels per lane when the frame allows 4-byte loads
-static inline void launch_preproc(hipStream_t st, const uint8_t* rgb, int w, int h, uint32_t* out, int wp, int hp) {
+static inline void launch_preproc(hipStream_t st, const uint8_t* rgb, int w, int h, uint32_t* out, int wp, int hp, int pixfmt = RIFE_HIP_PIX_RGB8) {
+    if (pixfmt == RIFE_HIP_PIX_RGB10_U16) {
+        const uint16_t* p = reinterpret_cast<const uint16_t*>(rgb);
+        if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 7) == 0) hipLaunchKernelGGL(k_preproc10_u16x4, dim3((wp / 4 + 255) / 256, hp), dim3(256), 0, st, p, w, h, out, wp, hp);
+        else hipLaunchKernelGGL(k_preproc10_u16, grid2d(wp, hp), dim3(256), 0, st, p, w, h, out, wp, hp);
+        return;
+    }
+    if (pixfmt == RIFE_HIP_PIX_A2B10G10R10) {
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(rgb);
+        if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 15) == 0) hipLaunchKernelGGL(k_preproc10_packedx4, dim3((wp / 4 + 255) / 256, hp), dim3(256), 0, st, p, w, h, out, wp, hp);
+        else hipLaunchKernelGGL(k_preproc10_packed, grid2d(wp, hp), dim3(256), 0, st, p, w, h, out, wp, hp);
+        return;
+    }
     if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 3) == 0) hipLaunchKernelGGL(k_preproc4, dim3((wp / 4 + 255) / 256, hp), dim3(256), 0, st, rgb, w, h, out, wp, hp);
     else hipLaunchKernelGGL(k_preproc, grid2d(wp, hp), dim3(256), 0, st, rgb, w, h, out, wp, hp);
 }
@@ -106,7 +124,13 @@ static int run_assemble(const rife_hip& E, Ctx& c, int b, float timestep, const 
     Timed t(E.prof, "assemble", 0, st);
     const int s = E.blk[b].scale;
     dim3 g = grid2d(c.wp / s, c.hp / s);
-    if (b == 0) hipLaunchKernelGGL(k_assemble0, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.X, c.wp, c.hp);
+    if (c.pixfmt) {
+        if (b == 0) hipLaunchKernelGGL(k_assemble0_d10, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.X, c.wp, c.hp);
+        else if (s == 4) hipLaunchKernelGGL((k_assemble<4, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+        else if (s == 2) hipLaunchKernelGGL((k_assemble<2, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+        else hipLaunchKernelGGL((k_assemble<1, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+    }
+    else if (b == 0) hipLaunchKernelGGL(k_assemble0, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.X, c.wp, c.hp);
     else if (s == 4) hipLaunchKernelGGL(k_assemble<4>, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
     else if (s == 2) hipLaunchKernelGGL(k_assemble<2>, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
     else hipLaunchKernelGGL(k_assemble<1>, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
@@ -122,6 +146,7 @@ static int launch_stem_rs(const rife_hip& E, Ctx& c, const rife_hip::Block& B, u
         std::lock_guard<std::mutex> g(mu);
         if (!done[dev]) {
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_rs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, SRS_LDS));
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_rs_kernel<0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, SRS_LDS));
             done[dev] = true;
         }
     }
@@ -133,7 +158,8 @@ static int launch_stem_rs(const rife_hip& E, Ctx& c, const rife_hip::Block& B, u
     a.out = out; a.timestep = timestep; a.tsp = tsp; a.wp = c.wp; a.hp = c.hp; a.Hq = Hq; a.Wq = Wq; a.pitch = G.pitch; a.plane = G.plane();
     a.nunits = ((Wq + SRS_SW - 1) / SRS_SW) * Hq;
     const int nwg = std::min(2 * device_cus(), a.nunits);
-    hipLaunchKernelGGL((stem_rs_kernel<0>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
+    if (c.pixfmt) hipLaunchKernelGGL((stem_rs_kernel<0, 10>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
+    else hipLaunchKernelGGL((stem_rs_kernel<0>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("stem_rs launch: ") + hipGetErrorString(e));
     return 0;
@@ -146,6 +172,8 @@ static int launch_tail_rs(const rife_hip::Block& B, const unsigned char* in, int
         std::lock_guard<std::mutex> g(mu);
         if (!done[dev]) {
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
             done[dev] = true;
         }
     }
@@ -155,7 +183,9 @@ static int launch_tail_rs(const rife_hip::Block& B, const unsigned char* in, int
     a.w_ = fin.w; a.h_ = fin.h; a.wp = fin.wp; a.hp = fin.hp; a.Hq = Hq; a.Wq = Wq; a.pitch = G.pitch; a.plane = G.plane();
     a.nunits = ((Wq + 31) / 32) * Hq;
     const int nwg = std::min(2 * device_cus(), a.nunits);
-    hipLaunchKernelGGL((tail_rs_kernel<0>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
+    if (fin.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL((tail_rs_kernel<0, 1>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
+    else if (fin.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL((tail_rs_kernel<0, 2>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
+    else hipLaunchKernelGGL((tail_rs_kernel<0>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("tail_rs launch: ") + hipGetErrorString(e));
     return 0;
@@ -254,19 +284,30 @@ static int run_block_convs(const rife_hip& E, Ctx& c, int b, float timestep, con
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0, 0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, 0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, 1, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0, 2, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
                 fdone[dev] = true;
             }
         }
         if (upd_flow) {
             if (s > 2 || !c.F2) return fail(RIFE_HIP_EINVAL, "no fused flow update for this block");
             fa.pend.flow = upd_flow; fa.pend.Fw = c.F2; fa.pend.Mw = c.M2;
-            if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, true>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            if (c.pixfmt && s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 1, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (c.pixfmt) hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 1, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
+            else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, true>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
             else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, true>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
             std::swap(c.F, c.F2); std::swap(c.M, c.M2);
         } else if (first_flow) {      // block 1 right after block 0: F, M are not materialised yet, the stem samples the first update itself (first_flow_merged)
             if (s != 4) return fail(RIFE_HIP_EINVAL, "the first flow update is sampled by the scale-4 stem only");
             fa.pend.flow = first_flow;
-            hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            if (c.pixfmt) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 2, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+        } else if (c.pixfmt) {
+            if (s == 4) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 0, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
         } else if (s == 4) hipLaunchKernelGGL((stem0_fused_kernel<4, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
         else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
         else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);      // 64-byte swizzled records, three workgroups per CU
@@ -380,12 +421,13 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
     int rc;
     {
         Timed t(E.prof, "preproc", 0, st);
-        launch_preproc(st, d_in0, c.w, c.h, c.img0, c.wp, c.hp);
-        launch_preproc(st, d_in1, c.w, c.h, c.img1, c.wp, c.hp);
+        launch_preproc(st, d_in0, c.w, c.h, c.img0, c.wp, c.hp, c.pixfmt);
+        launch_preproc(st, d_in1, c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt);
         HIPCHK(hipGetLastError());
     }
+    if (c.pixfmt && E.v40) return fail(RIFE_HIP_ENOSYS, "10-bit frames are served for model family rife-v4.6 only, not rife-v4");
     const bool fuse_tail = !E.v40 && trunk_h2() && g_head_h2 && g_fuse_tail && E.blk[3].head.d_wh != nullptr;
-    FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out, c.w, c.h, c.wp, c.hp};
+    FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out, c.w, c.h, c.wp, c.hp, c.pixfmt};
     const float* pending = nullptr;                                      // flow whose update of F, M the next block's stem applies
     // The update after block 0 never reaches HBM on its own (round 5): block 1's scale-4 stem samples it from flow0 (assemble_pixel UPD = 2) and ONE pass after
     // block 1 writes F, M with both updates applied (k_flow_update2) - bit for bit the tensors of the two-kernel sequence, one launch and 20 B / pixel of writes +
@@ -412,7 +454,9 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         HIPCHK(hipGetLastError());
     } else if (!fuse_tail) {
         Timed t(E.prof, "final", 0, st);
-        hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        if (c.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        else if (c.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         HIPCHK(hipGetLastError());
     }
     return 0;
@@ -430,8 +474,8 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
         Ctx& c = *cs[g];
         if (!c.ev_group) HIPCHK(hipEventCreateWithFlags(&c.ev_group, hipEventDisableTiming));
         Timed t(E.prof, "preproc", 0, c.stream);
-        launch_preproc(c.stream, d_in0[g], c.w, c.h, c.img0, c.wp, c.hp);
-        launch_preproc(c.stream, d_in1[g], c.w, c.h, c.img1, c.wp, c.hp);
+        launch_preproc(c.stream, d_in0[g], c.w, c.h, c.img0, c.wp, c.hp, c.pixfmt);
+        launch_preproc(c.stream, d_in1[g], c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt);
         HIPCHK(hipGetLastError());
     }
     const bool fuse_tail = trunk_h2() && g_head_h2 && g_fuse_tail && E.blk[3].head.d_wh != nullptr;
@@ -445,7 +489,7 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
         const bool batched = G >= 2 && block_on_row_kernel(E, *cs[0], b) && block_on_s16(E, *cs[0], b);
         for (int g = 0; g < G; g++) {
             Ctx& c = *cs[g];
-            FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out[g], c.w, c.h, c.wp, c.hp};
+            FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out[g], c.w, c.h, c.wp, c.hp, c.pixfmt};
             if (!batched) {
                 if ((rc = run_block_convs(E, c, b, ts[g], (b == 3 && fuse_tail) ? &fin : nullptr, nullptr, PH_ALL, pend[g]))) return rc;
                 pend[g] = nullptr;
@@ -481,7 +525,9 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
     for (int g = 0; g < G; g++)
         if (!fuse_tail) {
             Ctx& c = *cs[g];
-            hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
+            if (c.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
+            else if (c.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
+            else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
             HIPCHK(hipGetLastError());
         }
     return 0;
@@ -495,7 +541,8 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
 static inline bool use_graph() { return process_switches().use_graph; }
 
 static int run_v4_replay(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t* d_in1, float timestep, uint8_t* d_out) {
-    const bool eligible = use_graph() && !E.prof.on && c.d_ts && (size_t)c.wp * c.hp <= (size_t)1920 * 1088;
+    const bool eligible = use_graph() && !E.prof.on && c.d_ts && c.pixfmt == RIFE_HIP_PIX_RGB8 &&      // the replay's staging copies and captured graph are the 8-bit pass
+                          (size_t)c.wp * c.hp <= (size_t)1920 * 1088;
     if (!eligible) return run_v4(E, c, d_in0, d_in1, timestep, d_out);
     hipStream_t st = c.stream;
     const size_t nbytes = (size_t)c.w * c.h * 3;

@@ -65,7 +65,8 @@ static int paeth(int a, int b, int c) {
 }
 
 // PNG (every colour type, bit depth and interlace mode stb_image reads) -> tightly packed 8-bit RGB
-static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb) {
+// `wide` != null (-b 10): a 16-bit file also leaves its full samples there (w x h x 3, host order); it stays empty for every other depth
+static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb, std::vector<uint16_t>* wide = nullptr) {
     static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     if (d.size() < 33 || memcmp(d.data(), sig, 8)) return false;
     size_t pos = 8;
@@ -108,6 +109,8 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
     uLongf rawlen = (uLongf)raw.size();
     if (uncompress(raw.data(), &rawlen, idat.data(), (uLong)idat.size()) != Z_OK || rawlen != raw.size()) return false;
     rgb.assign((size_t)w * h * 3, 0);
+    if (wide) wide->clear();
+    if (wide && depth == 16) wide->assign((size_t)w * h * 3, 0);
     const int gscale = depth == 1 ? 255 : depth == 2 ? 85 : depth == 4 ? 17 : 1;
     size_t off = 0;
     for (int p = 0; p < npass; p++) {
@@ -149,6 +152,13 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
                 };
                 const int ox = interlace ? X0[p] + x * DX[p] : x, oy = interlace ? Y0[p] + y * DY[p] : y;
                 unsigned char* o = &rgb[((size_t)oy * w + ox) * 3];
+                if (wide && depth == 16) {                  // grey / grey + alpha / rgb / rgb + alpha: big-endian samples
+                    uint16_t* o16 = &(*wide)[((size_t)oy * w + ox) * 3];
+                    for (int c = 0; c < 3; c++) {
+                        const unsigned char* s16 = &row[((size_t)x * ch + (ch >= 3 ? c : 0)) * 2];
+                        o16[c] = (uint16_t)((s16[0] << 8) | s16[1]);
+                    }
+                }
                 if (ctype == 2 || ctype == 6) { o[0] = (unsigned char)sample(0); o[1] = (unsigned char)sample(1); o[2] = (unsigned char)sample(2); }
                 else if (ctype == 0 || ctype == 4) { o[0] = o[1] = o[2] = (unsigned char)(sample(0) * (depth < 8 ? gscale : 1)); }
                 else {
@@ -222,8 +232,7 @@ static int g_png_helpers = 0;
 // One band of rows: filter "up" (cheap and effective on video frames; the first row of the image has no row above) and raw deflate.
 // Every band but the last ends with a sync flush, i.e. on a byte boundary, so the bands concatenate into one valid deflate stream -
 // the bands share no history, which costs a little ratio and lets them run on separate cores.
-static bool png_deflate_band(const unsigned char* rgb, int w, int y0, int y1, bool last, std::vector<unsigned char>& comp, uLong& adler) {
-    const size_t stride = (size_t)w * 3;
+static bool png_deflate_band(const unsigned char* rgb, size_t stride, int y0, int y1, bool last, std::vector<unsigned char>& comp, uLong& adler) {
     std::vector<unsigned char> raw((stride + 1) * (size_t)(y1 - y0));
     for (int y = y0; y < y1; y++) {
         unsigned char* dst = &raw[(stride + 1) * (size_t)(y - y0)];
@@ -247,8 +256,9 @@ static bool png_deflate_band(const unsigned char* rgb, int w, int y0, int y1, bo
     return ok;
 }
 
-static bool encode_png(const std::string& path, int w, int h, const unsigned char* rgb) {
-    const size_t stride = (size_t)w * 3;
+// depth 8: rgb = w x h x 3 bytes; depth 16 (-b 10): w x h x 3 big-endian 16-bit samples
+static bool encode_png(const std::string& path, int w, int h, const unsigned char* rgb, int depth = 8) {
+    const size_t stride = (size_t)w * 3 * (depth / 8);
     // bands of about 1 MB of pixels, at most 64 (a band must stay below the 4 GB zlib counts in any case)
     int nband = (int)std::min<size_t>(64, std::max<size_t>(1, stride * h >> 20));
     nband = std::min(nband, h);
@@ -261,7 +271,7 @@ static bool encode_png(const std::string& path, int w, int h, const unsigned cha
         for (int b; (b = next.fetch_add(1)) < nband;) {
             const int y0 = (int)((long long)h * b / nband), y1 = (int)((long long)h * (b + 1) / nband);
             rawlen[b] = (stride + 1) * (size_t)(y1 - y0);
-            good[b] = png_deflate_band(rgb, w, y0, y1, b == nband - 1, comp[b], adler[b]);
+            good[b] = png_deflate_band(rgb, stride, y0, y1, b == nband - 1, comp[b], adler[b]);
         }
     };
     std::vector<std::thread> helpers;
@@ -280,7 +290,7 @@ static bool encode_png(const std::string& path, int w, int h, const unsigned cha
     const size_t clen = zs.size();
     std::vector<unsigned char> out = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     unsigned char ihdr[13] = {(unsigned char)(w >> 24), (unsigned char)(w >> 16), (unsigned char)(w >> 8), (unsigned char)w,
-                              (unsigned char)(h >> 24), (unsigned char)(h >> 16), (unsigned char)(h >> 8), (unsigned char)h, 8, 2, 0, 0, 0};
+                              (unsigned char)(h >> 24), (unsigned char)(h >> 16), (unsigned char)(h >> 8), (unsigned char)h, (unsigned char)depth, 2, 0, 0, 0};
     put_chunk(out, "IHDR", ihdr, 13);
     put_chunk(out, "IDAT", comp_data, clen);
     put_chunk(out, "IEND", nullptr, 0);
@@ -291,7 +301,10 @@ static bool encode_png(const std::string& path, int w, int h, const unsigned cha
     return ok;
 }
 
-static bool decode_ppm(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb) {
+// `wide` != null (-b 10): files with maxval 1023 or 65535 (two bytes per sample, big-endian) are read too, their samples go to *wide (host order) and
+// *maxval says which; a maxval-255 file is read as always and leaves *wide empty
+static bool decode_ppm(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb, std::vector<uint16_t>* wide = nullptr, int* maxval = nullptr) {
+    if (wide) wide->clear();
     if (d.size() < 7 || d[0] != 'P' || (d[1] != '6' && d[1] != '5')) return false;      // P6 = rgb, P5 = grey (stb_image's pnm reader takes both)
     const bool grey = d[1] == '5';
     size_t pos = 2;
@@ -303,7 +316,21 @@ static bool decode_ppm(const std::vector<unsigned char>& d, int& w, int& h, std:
         if (!any) return false;
         vals[n++] = v;
     }
-    if (n != 3 || vals[2] != 255 || pos >= d.size()) return false;
+    if (n != 3 || pos >= d.size()) return false;
+    if (wide && !grey && (vals[2] == 1023 || vals[2] == 65535)) {
+        pos++;
+        w = vals[0]; h = vals[1];
+        if (w <= 0 || h <= 0 || (size_t)w * h > ((size_t)1 << 28) || d.size() - pos < (size_t)w * h * 6) return false;
+        wide->resize((size_t)w * h * 3);
+        for (size_t i = 0; i < wide->size(); i++) {
+            const unsigned v = ((unsigned)d[pos + 2 * i] << 8) | d[pos + 2 * i + 1];
+            if (v > (unsigned)vals[2]) return false;                     // a sample above maxval: not a valid file
+            (*wide)[i] = (uint16_t)v;
+        }
+        if (maxval) *maxval = vals[2];
+        return true;
+    }
+    if (vals[2] != 255) return false;
     pos++;                                       // the single whitespace after maxval
     w = vals[0]; h = vals[1];
     if (w <= 0 || h <= 0 || d.size() - pos < (size_t)w * h * (grey ? 1 : 3)) return false;
@@ -318,6 +345,18 @@ static bool encode_ppm(const std::string& path, int w, int h, const unsigned cha
     if (!f) return false;
     fprintf(f, "P6\n%d %d\n255\n", w, h);
     const bool ok = fwrite(rgb, 1, (size_t)w * h * 3, f) == (size_t)w * h * 3;
+    fclose(f);
+    return ok;
+}
+
+// -b 10: P6 with maxval 1023, two bytes per sample, most significant first (Netpbm)
+static bool encode_ppm10(const std::string& path, int w, int h, const uint16_t* codes) {
+    std::vector<unsigned char> be((size_t)w * h * 6);
+    for (size_t i = 0; i < (size_t)w * h * 3; i++) { const unsigned c = std::min<unsigned>(codes[i], 1023u); be[2 * i] = (unsigned char)(c >> 8); be[2 * i + 1] = (unsigned char)c; }
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "P6\n%d %d\n1023\n", w, h);
+    const bool ok = fwrite(be.data(), 1, be.size(), f) == be.size();
     fclose(f);
     return ok;
 }
@@ -380,6 +419,43 @@ static bool encode_image(const std::string& path, int w, int h, const unsigned c
     return encode_png(path, w, h, rgb);
 }
 
+// ---- -b 10: frames as 10-bit codes (u16 x 3 per pixel, 0..1023; include/rife_hip.h RIFE_HIP_PIX_RGB10_U16) ----
+// a 16-bit PNG or a PPM with maxval 65535: code = v >> 6; a PPM with maxval 1023: its codes; every 8-bit file: (v << 2) | (v >> 6)
+static bool decode_image10(const std::string& path, int& w, int& h, std::vector<uint16_t>& codes) {
+    std::vector<unsigned char> d, rgb;
+    if (!read_file(path, d)) return false;
+    std::vector<uint16_t> wide;
+    int maxval = 0;
+    if (decode_png(d, w, h, rgb, &wide)) {
+        if (!wide.empty()) { codes.resize(wide.size()); for (size_t i = 0; i < wide.size(); i++) codes[i] = (uint16_t)(wide[i] >> 6); return true; }
+    } else if (decode_ppm(d, w, h, rgb, &wide, &maxval)) {
+        if (!wide.empty()) { codes.resize(wide.size()); for (size_t i = 0; i < wide.size(); i++) codes[i] = (uint16_t)(maxval == 1023 ? wide[i] : wide[i] >> 6); return true; }
+    } else if (!(decode_webp(d, w, h, rgb) || decode_bmp(d, w, h, rgb))) {
+        std::string why;
+        if (!jpeg::decode(d, w, h, rgb, &why)) {
+            if (d.size() > 2 && d[0] == 0xFF && d[1] == 0xD8) fprintf(stderr, "%s: %s\n", path.c_str(), why.c_str());
+            return false;
+        }
+    }
+    codes.resize(rgb.size());
+    for (size_t i = 0; i < rgb.size(); i++) codes[i] = (uint16_t)((rgb[i] << 2) | (rgb[i] >> 6));
+    return true;
+}
+
+// .png: 16-bit RGB, v = (code << 6) | (code >> 4) - the code's bits repeated into the low six, so that full scale maps to full scale and reading the file back
+// with -b 10 (v >> 6) returns the codes; .ppm: P6 with maxval 1023
+static bool encode_image10(const std::string& path, int w, int h, const uint16_t* codes) {
+    const std::string e = ext_of(path);
+    if (e == "ppm") return encode_ppm10(path, w, h, codes);
+    if (e == "webp" || e == "jpg" || e == "jpeg") return false;          // 8-bit containers (refused at start-up)
+    std::vector<unsigned char> be((size_t)w * h * 6);
+    for (size_t i = 0; i < (size_t)w * h * 3; i++) {
+        const unsigned c = std::min<unsigned>(codes[i], 1023u), v = (c << 6) | (c >> 4);
+        be[2 * i] = (unsigned char)(v >> 8); be[2 * i + 1] = (unsigned char)v;
+    }
+    return encode_png(path, w, h, be.data(), 16);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // tasks and queues (src/main.cpp:231-295)
 // ---------------------------------------------------------------------------------------------------------------
@@ -389,10 +465,12 @@ static bool encode_image(const std::string& path, int w, int h, const unsigned c
 struct SharedFrame {
     int w = 0, h = 0;
     std::vector<unsigned char> px;
+    std::vector<uint16_t> px10;                                       // -b 10: the frame as 10-bit codes instead of px
     const rife_hip_frame* on(const RIFE* r) {
         std::lock_guard<std::mutex> g(mu);
         for (auto& e : resident) if (e.first == r) return e.second;
-        rife_hip_frame* f = r->upload(ncnn::Mat(w, h, (void*)px.data(), (size_t)3, 3));
+        rife_hip_frame* f = px10.empty() ? r->upload(ncnn::Mat(w, h, (void*)px.data(), (size_t)3, 3))
+                                         : r->upload(ncnn::Mat(w, h, (void*)px10.data(), (size_t)6, 3));      // elemsize 6, elempack 3 = RGB10_U16 (rife.cpp)
         if (f) resident.emplace_back(r, f);
         return f;
     }
@@ -408,6 +486,7 @@ struct Task {
     std::string in0path, in1path, outpath;
     std::shared_ptr<SharedFrame> fr0, fr1;                            // decoded frames are shared between the tasks that use them
     std::vector<unsigned char> out;
+    std::vector<uint16_t> out10;                                      // -b 10
     int w = 0, h = 0;
 };
 
@@ -417,6 +496,7 @@ struct Task {
 class FrameCache {
 public:
     typedef std::shared_ptr<SharedFrame> Frame;
+    // decode(path, frame) fills the frame's size and pixels
     template <class Decode>
     bool get(const std::string& path, Frame& f, Decode decode) {
         {
@@ -424,7 +504,7 @@ public:
             for (auto& e : entries) if (e.first == path) { f = e.second; return true; }
         }
         Frame n = std::make_shared<SharedFrame>();
-        if (!decode(path, n->w, n->h, n->px)) return false;
+        if (!decode(path, *n)) return false;
         std::lock_guard<std::mutex> g(mu);
         for (auto& e : entries) if (e.first == path) { f = e.second; return true; }     // another loader decoded it meanwhile: keep one copy
         entries.emplace_back(path, n);
@@ -478,6 +558,7 @@ static void print_usage() {
     fprintf(stderr, "  -z                   enable temporal tta mode\n");
     fprintf(stderr, "  -u                   enable UHD mode\n");
     fprintf(stderr, "  -f pattern-format    output image filename pattern format (%%08d.jpg/png/webp/ppm, default=ext/%%08d.png)\n");
+    fprintf(stderr, "  -b bit-depth         bits per sample, 8 or 10 (default=8); 10: rife-v4.6 only, 16-bit png / maxval-1023 ppm output\n");
 }
 
 static bool is_dir(const std::string& p) { struct stat s; return stat(p.c_str(), &s) == 0 && S_ISDIR(s.st_mode); }
@@ -519,15 +600,26 @@ int main(int argc, char** argv) {
         if (!ok) { fprintf(stderr, "encode image %s failed\n", argv[3]); return 1; }
         return 0;
     }
+    // the same for the 10-bit codecs:  rife-hip --transcode10 in.(png|ppm|...) out.(png|ppm)
+    if (argc == 4 && std::string(argv[1]) == "--transcode10") {
+        int w = 0, h = 0;
+        std::vector<uint16_t> codes;
+        g_png_helpers = std::max(0, std::min(15, (int)std::thread::hardware_concurrency() - 1));
+        if (!decode_image10(argv[2], w, h, codes)) { fprintf(stderr, "decode image %s failed\n", argv[2]); return 1; }
+        const std::string e = ext_of(argv[3]);
+        if (e != "png" && e != "ppm") { fprintf(stderr, "10-bit frames are written as png (16-bit) or ppm (maxval 1023) only\n"); return 1; }
+        if (!encode_image10(argv[3], w, h, codes.data())) { fprintf(stderr, "encode image %s failed\n", argv[3]); return 1; }
+        return 0;
+    }
     std::string input0, input1, inputpath, outputpath, model = "rife-v2.3", pattern_format = "%08d.png";
     int numframe = 0;
     float timestep = 0.5f;
     std::vector<int> gpuid, jobs_proc;
-    int jobs_load = 1, jobs_save = 2;
+    int jobs_load = 1, jobs_save = 2, bits = 8;
     bool verbose = false, tta = false, tta_temporal = false, uhd = false;
 
     int opt;
-    while ((opt = getopt(argc, argv, "0:1:i:o:n:s:m:g:j:f:vxzuh")) != -1) {
+    while ((opt = getopt(argc, argv, "0:1:i:o:n:s:m:g:j:f:b:vxzuh")) != -1) {
         switch (opt) {
             case '0': input0 = optarg; break;
             case '1': input1 = optarg; break;
@@ -547,6 +639,7 @@ int main(int argc, char** argv) {
                 break;
             }
             case 'f': pattern_format = optarg; break;
+            case 'b': bits = atoi(optarg); break;
             case 'v': verbose = true; break;
             case 'x': tta = true; break;
             case 'z': tta_temporal = true; break;
@@ -563,6 +656,8 @@ int main(int argc, char** argv) {
     if (jobs_load < 1 || jobs_save < 1) { fprintf(stderr, "invalid thread count argument\n"); return -1; }
     if (!jobs_proc.empty() && jobs_proc.size() != (gpuid.empty() ? 1 : gpuid.size())) { fprintf(stderr, "invalid jobs_proc thread count argument\n"); return -1; }
     for (int j : jobs_proc) if (j < 1) { fprintf(stderr, "invalid jobs_proc thread count argument\n"); return -1; }
+    if (bits != 8 && bits != 10) { fprintf(stderr, "invalid bit depth argument, must be 8 or 10\n"); return -1; }
+    const bool deep = bits == 10;
 
     std::string pattern = pattern_format, format;
     {
@@ -580,6 +675,7 @@ int main(int argc, char** argv) {
         else { fprintf(stderr, "invalid outputpath extension type\n"); return -1; }
     }
     if (format != "png" && format != "ppm" && format != "webp" && format != "jpg") { fprintf(stderr, "invalid format argument\n"); return -1; }
+    if (deep && format != "png" && format != "ppm") { fprintf(stderr, "10-bit frames (-b 10) are written as png (16-bit) or ppm (maxval 1023) only, not %s\n", format.c_str()); return -1; }
 #ifndef RIFE_HIP_WITH_WEBP
     if (format == "webp") { fprintf(stderr, "this rife-hip was built without libwebp\n"); return -1; }
 #endif
@@ -640,6 +736,12 @@ int main(int argc, char** argv) {
     for (int g : gpuid) {
         RIFE* r = new RIFE(g, tta, tta_temporal, uhd, 1, rife_v2, rife_v4);
         if (r->load(model) != 0) { fprintf(stderr, "loading %s failed: %s\n", model.c_str(), rife_hip_last_error()); return -1; }
+        if (deep) {      // the engine refuses 10-bit frames for every family but rife-v4.6 and for -x / -z / -u: ask it now, with one pixel, not at the first pair
+            uint16_t one[3] = {0, 0, 0};
+            rife_hip_frame* f = r->upload(ncnn::Mat(1, 1, (void*)one, (size_t)6, 3));
+            if (!f) { fprintf(stderr, "-b 10 is not available: %s\n", rife_hip_last_error()); return -1; }
+            RIFE::release(f);
+        }
         rife.push_back(r);
     }
 
@@ -655,7 +757,8 @@ int main(int argc, char** argv) {
             { std::lock_guard<std::mutex> g(next_mu); if (next_task >= tasks.size()) return; k = next_task++; }
             Task t = std::move(tasks[k]);
             FrameCache::Frame f0, f1;
-            if (!cache.get(t.in0path, f0, decode_image) || !cache.get(t.in1path, f1, decode_image)) { fprintf(stderr, "decode image %s or %s failed\n", t.in0path.c_str(), t.in1path.c_str()); continue; }
+            auto decode = [&](const std::string& p, SharedFrame& fr) { return deep ? decode_image10(p, fr.w, fr.h, fr.px10) : decode_image(p, fr.w, fr.h, fr.px); };
+            if (!cache.get(t.in0path, f0, decode) || !cache.get(t.in1path, f1, decode)) { fprintf(stderr, "decode image %s or %s failed\n", t.in0path.c_str(), t.in1path.c_str()); continue; }
             if (f1->w != f0->w || f1->h != f0->h) { fprintf(stderr, "%s and %s differ in size\n", t.in0path.c_str(), t.in1path.c_str()); continue; }
             t.w = f0->w; t.h = f0->h; t.fr0 = f0; t.fr1 = f1;
             toproc.put(std::move(t));
@@ -670,8 +773,15 @@ int main(int argc, char** argv) {
             Task t = toproc.get();
             if (t.id == -233) return;                                          // end marker, like the reference
             replica_tasks[me]++;
-            if (t.timestep == 0.f || t.timestep == 1.f) t.out = (t.timestep == 0.f ? t.fr0 : t.fr1)->px;      // rife.cpp:2470-2480: an input frame, unchanged
-            else {
+            if (deep && (t.timestep == 0.f || t.timestep == 1.f)) t.out10 = (t.timestep == 0.f ? t.fr0 : t.fr1)->px10;
+            else if (t.timestep == 0.f || t.timestep == 1.f) t.out = (t.timestep == 0.f ? t.fr0 : t.fr1)->px;      // rife.cpp:2470-2480: an input frame, unchanged
+            else if (deep) {
+                const rife_hip_frame* d0 = t.fr0->on(r);
+                const rife_hip_frame* d1 = t.fr1->on(r);
+                t.out10.resize((size_t)t.w * t.h * 3);
+                ncnn::Mat out(t.w, t.h, (void*)t.out10.data(), (size_t)6, 3);
+                if (!d0 || !d1 || r->process(d0, d1, t.timestep, out) != 0) { fprintf(stderr, "process %s failed: %s\n", t.outpath.c_str(), rife_hip_last_error()); continue; }
+            } else {
                 const rife_hip_frame* d0 = t.fr0->on(r);
                 const rife_hip_frame* d1 = t.fr1->on(r);
                 t.out.resize((size_t)t.w * t.h * 3);
@@ -686,7 +796,7 @@ int main(int argc, char** argv) {
         for (;;) {
             Task t = tosave.get();
             if (t.id == -233) return;
-            const bool ok = encode_image(t.outpath, t.w, t.h, t.out.data());
+            const bool ok = deep ? encode_image10(t.outpath, t.w, t.h, t.out10.data()) : encode_image(t.outpath, t.w, t.h, t.out.data());
             if (!ok) fprintf(stderr, "encode image %s failed\n", t.outpath.c_str());
             else if (verbose) fprintf(stderr, "%s %s %f -> %s done\n", t.in0path.c_str(), t.in1path.c_str(), t.timestep, t.outpath.c_str());
         }

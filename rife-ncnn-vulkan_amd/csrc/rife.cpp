@@ -8,6 +8,13 @@
 
 #include "../../include/rife_hip.h"
 
+// the pixel format of a Mat at this boundary: elemsize 6, elempack 3 = three u16 codes 0..1023 per pixel (RIFE_HIP_PIX_RGB10_U16); every other Mat is the
+// 8-bit RGB Mat the reference builds (src/main.cpp:187, 332)
+static int mat_pixfmt(const ncnn::Mat& m)
+{
+    return (m.elemsize == 6 && m.elempack == 3) ? RIFE_HIP_PIX_RGB10_U16 : RIFE_HIP_PIX_RGB8;
+}
+
 RIFE::RIFE(int gpuid_, bool tta_mode, bool tta_temporal_mode, bool uhd_mode, int num_threads, bool rife_v2, bool rife_v4_)
     : engine(0), gpuid(gpuid_), rife_v4(rife_v4_)
 {
@@ -32,6 +39,13 @@ int RIFE::load(const std::string& modeldir)
 
 int RIFE::process(const ncnn::Mat& in0image, const ncnn::Mat& in1image, float timestep, ncnn::Mat& outimage) const
 {
+    const int pixfmt = mat_pixfmt(in0image);
+    if (pixfmt != mat_pixfmt(in1image) || (outimage.data && mat_pixfmt(outimage) != pixfmt))
+    {
+        fprintf(stderr, "RIFE::process: the three images differ in pixel format (8-bit and 10-bit Mats mixed)\n");
+        return -RIFE_HIP_EINVAL;
+    }
+
     if (timestep == 0.f)
     {
         outimage = in0image;
@@ -51,7 +65,9 @@ int RIFE::process(const ncnn::Mat& in0image, const ncnn::Mat& in1image, float ti
         return -RIFE_HIP_EINVAL;
     }
 
-    int ret = rife_hip_process(engine, (const unsigned char*)in0image.data, (const unsigned char*)in1image.data, in0image.w, in0image.h, timestep, (unsigned char*)outimage.data);
+    int ret = pixfmt == RIFE_HIP_PIX_RGB8
+                  ? rife_hip_process(engine, (const unsigned char*)in0image.data, (const unsigned char*)in1image.data, in0image.w, in0image.h, timestep, (unsigned char*)outimage.data)
+                  : rife_hip_process_px(engine, in0image.data, in1image.data, in0image.w, in0image.h, timestep, outimage.data, pixfmt);
     if (ret) fprintf(stderr, "RIFE::process: %s\n", rife_hip_last_error());
     return ret;
 }
@@ -60,7 +76,9 @@ rife_hip_frame* RIFE::upload(const ncnn::Mat& image) const
 {
     if (!engine || !image.data) return 0;
     rife_hip_frame* f = 0;
-    if (rife_hip_frame_upload(engine, (const unsigned char*)image.data, image.w, image.h, &f))
+    const int pixfmt = mat_pixfmt(image);
+    if (pixfmt == RIFE_HIP_PIX_RGB8 ? rife_hip_frame_upload(engine, (const unsigned char*)image.data, image.w, image.h, &f)
+                                    : rife_hip_frame_upload_px(engine, image.data, image.w, image.h, pixfmt, &f))
         fprintf(stderr, "RIFE::upload: %s\n", rife_hip_last_error());
     return f;
 }

@@ -40,7 +40,8 @@ constexpr int stemf_lds_bytes() { return (9 * 65 + 1) * stemf_pixb<ABL>() + 9 * 
 // UPD: k_flow_update<2 S> of the block before (flownet.param:99-105, 152-158) happens here: the kernel visits every full-resolution pixel (S <= 2)
 // anyway, so F, M make one round trip less through HBM per block and the launch disappears; halo pixels shared by tiles are written twice with
 // the same value, into the other F, M buffer.
-template <int S, int NS, int ABL = 0, int UPD = 0>
+// D = 10: the frames are 10:10:10 dwords (elementwise.h unpack_rgb<10>); nothing else differs.
+template <int S, int NS, int ABL = 0, int UPD = 0, int D = 8>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu((ABL & 256) ? 6 : 4, (ABL & 256) ? 6 : 4))) void stem0_fused_kernel(StemFusedArgs a) {
     static_assert(UPD != 1 || S <= 2, "the scale-4 stem samples a quarter of the full-resolution pixels: it cannot write the updated tensors (UPD = 1), only sample the first update (UPD = 2)");
     constexpr int IH = 9, IW = 65, PIXB = stemf_pixb<ABL>(), NT = NS * 32;
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu((ABL & 256)
         const int py_ = p_ / IW, px_ = p_ - py_ * IW;                                                             \
         const int by_ = iy0 + py_, bx_ = ix0 + px_;                                                               \
         const bool in_ = by_ >= 0 && by_ < Hb && bx_ >= 0 && bx_ < Wb;                                            \
-        assemble_pixel<S, UPD>(a.img0, a.img1, timestep, a.F, a.M, a.wp, a.hp, min(max(bx_, 0), Wb - 1), min(max(by_, 0), Hb - 1), O, a.pend); \
+        assemble_pixel<S, UPD, D>(a.img0, a.img1, timestep, a.F, a.M, a.wp, a.hp, min(max(bx_, 0), Wb - 1), min(max(by_, 0), Hb - 1), O, a.pend); \
         _Pragma("unroll") for (int c = 0; c < 12; c++) O[c] = in_ ? O[c] : 0.f;                                   \
     }
 #define STEM_STAGE(P, O)                                                                                          \

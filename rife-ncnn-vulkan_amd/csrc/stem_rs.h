@@ -85,7 +85,8 @@ __device__ __forceinline__ void srs_store_b64(unsigned char* base, unsigned off,
     asm volatile("global_store_dwordx2 %0, %1, %2" :: "v"(off), "v"(d), "s"(base) : "memory");
 }
 
-template <int TAG>
+// D = 10: the frames are 10:10:10 dwords (elementwise.h unpack_rgb<10>); nothing else differs.
+template <int TAG, int D = 8>
 __global__ __launch_bounds__(SRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))) void stem_rs_kernel(StemRsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -165,9 +166,9 @@ __global__ __launch_bounds__(SRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
             if (wr) { *reinterpret_cast<f16x8*>(d + ((1 ^ gsw) << 4)) = h1; *reinterpret_cast<f16x8*>(d + SRS_A_HL + ((1 ^ gsw) << 4)) = l1; }
         }
         __builtin_amdgcn_sched_barrier(0);
-        const float3 w0 = warp_finish(t.a);
+        const float3 w0 = warp_finish<D>(t.a);
         __builtin_amdgcn_sched_barrier(0);
-        const float3 w1 = warp_finish(t.b);
+        const float3 w1 = warp_finish<D>(t.b);
         __builtin_amdgcn_sched_barrier(0);
         const float O[8] = {w0.x, w0.y, w0.z, w1.x, w1.y, w1.z, timestep, fm.m};
         f16x8 h0, l0;

@@ -59,7 +59,19 @@ __device__ __forceinline__ void trs_store_byte(uint8_t* base, unsigned off, uint
 
 #define TRS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-template <int TAG>
+__device__ __forceinline__ void trs_put_short(uint8_t* base, unsigned off, uint32_t v) {
+    asm volatile("global_store_short %0, %1, %2" :: "v"(off), "v"(v), "s"(base) : "memory");
+}
+// One finished pixel of a deep-colour frame (PX = 1: three u16 codes, 2: one A2B10G10R10 dword, alpha 3), pixel index i = oy * w + ox: the packed
+// format leaves as one aligned dword per lane - 256 contiguous bytes per wave - instead of depth 8's shuffled 48 dwords.
+template <int PX>
+__device__ __forceinline__ void trs_put_px10(uint8_t* base, unsigned i, uint32_t pk) {
+    if (PX == 2) trs_store_dword(base, i * 4u, pk | 0xc0000000u);
+    else { trs_put_short(base, i * 6u, pk & 0x3ffu); trs_put_short(base, i * 6u + 2u, (pk >> 10) & 0x3ffu); trs_put_short(base, i * 6u + 4u, (pk >> 20) & 0x3ffu); }
+}
+
+// PX (include/rife_hip.h RIFE_HIP_PIX_*): 0 = u8 frames; 1 / 2 = 10:10:10 frames in, RGB10_U16 / A2B10G10R10 out (k_final_px<PX>'s arithmetic)
+template <int TAG, int PX = 0>
 __global__ __launch_bounds__(TRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))) void tail_rs_kernel(TailRsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -233,9 +245,10 @@ __global__ __launch_bounds__(TRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
             const bool valid = ox < a.w_ && (!RIFE_ABL(TAG & TRS_NOSTORE) || mm == 123.456f);
             const float m = 1.f / (1.f + expf(-mm));
             const float rm = 1.0f - m;
-            const float3 w1 = warp_finish(tb);
-            const float3 w0 = warp_finish(ta);
+            const float3 w1 = warp_finish<PX ? 10 : 8>(tb);
+            const float3 w0 = warp_finish<PX ? 10 : 8>(ta);
             const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
+            if (PX) { if (valid) trs_put_px10<PX>(a.out, (unsigned)(oy * a.w_ + ox), quant10(r, g, b)); return; }
             const uint32_t pk = (uint32_t)min(max((int)(r * 255.f + 0.5f), 0), 255) | ((uint32_t)min(max((int)(g * 255.f + 0.5f), 0), 255) << 8) |
                                 ((uint32_t)min(max((int)(b * 255.f + 0.5f), 0), 255) << 16);
             const unsigned orow = (unsigned)(oy * a.w_ + oxb) * 3u;     // byte offset of the segment (frames stay below 4 GB)
@@ -275,9 +288,10 @@ __global__ __launch_bounds__(TRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
             const bool valid = ox < a.w_;
             const float m = 1.f / (1.f + expf(-mm_prev));
             const float rm = 1.0f - m;
-            const float3 w1 = warp_finish(wb);
-            const float3 w0 = warp_finish(wa);
+            const float3 w1 = warp_finish<PX ? 10 : 8>(wb);
+            const float3 w0 = warp_finish<PX ? 10 : 8>(wa);
             const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
+            if (PX) { if (valid) trs_put_px10<PX>(a.out, (unsigned)(oy * a.w_ + ox), quant10(r, g, b)); return; }
             const uint32_t pk = (uint32_t)min(max((int)(r * 255.f + 0.5f), 0), 255) | ((uint32_t)min(max((int)(g * 255.f + 0.5f), 0), 255) << 8) |
                                 ((uint32_t)min(max((int)(b * 255.f + 0.5f), 0), 255) << 16);
             const unsigned orow = (unsigned)(oy * a.w_ + oxb) * 3u;

@@ -17,6 +17,9 @@ echo "== 1. decoder corpus of tests/test_cli.py (truncated / bit-flipped / craft
 echo "   (a sanitizer report exits 99 / 98, which the tests' 'returncode in (0, 1)' assertions reject)"
 RIFE_HIP_BIN=$ASAN python -m pytest tests/test_cli.py -q -m "not gpu" -k "cpp_cli" 2>&1 | tail -4
 [ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
+echo "== 1b. the 10-bit codecs (--transcode10: 16-bit png, ppm with maxval 1023 / 65535, truncated and crafted files) of tests/test_cli_deep.py through the same binary"
+RIFE_HIP_BIN=$ASAN python -m pytest tests/test_cli_deep.py -q -m "not gpu" -k "cpp_cli" 2>&1 | tail -4
+[ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
 T=$(mktemp -d)
 python - $T <<'PY'
 import sys, os
@@ -74,6 +77,23 @@ o = np.asarray(Image.open(os.path.join(t, "out", sorted(os.listdir(os.path.join(
 want = (np.float32(0.4) * a.astype(np.float32) + np.float32(0.6) * b.astype(np.float32) + np.float32(0.5)).astype(np.uint8)      # -n 5 over 3 frames: output 2 = frames 0, 1 at timestep 0.6
 print("   band-written 1080p PNG decodes (PIL) to the stub's blend of its inputs:", bool(np.abs(o.astype(int) - want.astype(int)).max() <= 1))
 PY
+echo "== 3b. -b 10 (16-bit png in, 16-bit png / maxval-1023 ppm out; u16 frames through upload_px / process_frames of the stub) under both"
+python - $T <<'PY'
+import sys, os
+sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+import deep_ref
+from test_cli_deep import write_png, png_value
+t = sys.argv[1]
+os.makedirs(os.path.join(t, "in_deep"))
+for i in range(5):
+    write_png(os.path.join(t, "in_deep", "%03d.png" % i), png_value(deep_ref.deep_pair(333, 241, 70 + i)[i & 1]), 16)
+PY
+for fmt in png ppm; do
+    rm -rf $T/out; mkdir -p $T/out
+    run "asan -b 10 $fmt -g 0,1 -j 3:2,3:4" $ASAN -i $T/in_deep -o $T/out -m rife-v4.6 -n 13 -b 10 -f %08d.$fmt -g 0,1 -j 3:2,3:4
+    rm -rf $T/out; mkdir -p $T/out
+    run "tsan -b 10 $fmt -g 0,0 -j 2:1,2:3" $TSAN -i $T/in_deep -o $T/out -m rife-v4.6 -n 13 -b 10 -f %08d.$fmt -g 0,0 -j 2:1,2:3
+done
 echo "== 4. single-pair mode, error paths (missing file, size mismatch, bad extension) under ASan + UBSan"
 rm -rf $T/out; mkdir -p $T/out
 run "asan pair" $ASAN -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/o.png -m rife-v4.6 -s 0.3
