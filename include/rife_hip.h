@@ -111,6 +111,24 @@ void rife_hip_frame_release(rife_hip_frame_t* frame);
 #define RIFE_HIP_PIX_RGB8         0   /* u8 HWC, 3 B / pixel: what rife_hip_process() takes */
 #define RIFE_HIP_PIX_RGB10_U16    1   /* u16 HWC, native byte order, 6 B / pixel, codes 0..1023; a larger value is read as 1023 */
 #define RIFE_HIP_PIX_A2B10G10R10  2   /* one little-endian dword / pixel: R bits 0-9, G 10-19, B 20-29; bits 30-31 ignored on input, written as 3 */
+/* 3 is reserved (an unknown format today). */
+#define RIFE_HIP_PIX_RGBA8        4   /* u8 HWC, 4 B / pixel, R G B A: alpha carried through, see below */
+/* ---- alpha: RGBA frames in and out (absent in the reference, whose readers drop alpha) --------------------------------------------------------------
+ * Served where the 10-bit formats are served, through the same _px calls: model family rife-v4.6, plain mode, every frame size the RGB8 path serves;
+ * any other family or mode returns -RIFE_HIP_ENOSYS with a message that names it and leaves the output untouched; the opt-in graph replay does not apply.
+ *   colour  the R, G, B bytes of an RGBA call are BYTE FOR BYTE those of the RGB8 call on the same R, G, B.  Alpha never reaches the network: flows
+ *           and mask are estimated from the colour alone.
+ *   alpha   a fourth plane through the tail of the graph and nothing else: A = code * (1 / 255.f);
+ *           a = warp(A0, F.xy) * m + warp(A1, F.zw) * (1 - m), with the arithmetic of the colour channels (the reference's Warp, same operation order,
+ *           no contraction) and the same m = sigmoid(M);  code = min(max((int)(a * 255.f + 0.5f), 0), 255).
+ *           It is warped by the flow that was estimated from the colour it belongs to, so matte and colour cannot drift apart.
+ *   padding colour is zero-padded to 32n as the reference pads it; alpha is padded by EDGE REPLICATION (a pad pixel holds the alpha of the nearest frame
+ *           pixel): flows of a few pixels reach into the padding, and zero-padded alpha would turn an opaque frame transparent along its right and
+ *           bottom edge.  Opaque in gives 255 everywhere, clear in gives 0 everywhere.
+ *   timestep 0 / 1 return the first / second frame's four bytes unchanged.
+ *   Straight or premultiplied alpha: the four planes are interpolated as given (premultiplied input avoids fringes of whatever colour hides under
+ *   transparent pixels).
+ * Out of scope: alpha at depth 10 (A2B10G10R10 has two alpha bits), other families and modes, rife_hip_process_batch (the host batch). */
 
 size_t rife_hip_frame_bytes(int w, int h, int pixfmt);      /* 0 for an unknown format or w, h <= 0 */
 int rife_hip_process_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt);

@@ -32,8 +32,9 @@ int rife_hip_v4_tap(const rife_hip_t* r, const uint8_t* in0_rgb, const uint8_t* 
  * rife_hip_process.  out_rgb: w x h u8 RGB. */
 int rife_hip_v4_process_injected(const rife_hip_t* r, const uint8_t* in0_rgb, const uint8_t* in1_rgb, int w, int h, float timestep,
                                  const float* const* inject, int n_inject, uint8_t* out_rgb);
-/* The first two taps on frames of format `pixfmt` (include/rife_hip.h RIFE_HIP_PIX_*; rife-v4.6 for the 10-bit formats): the 10-bit gather code under the
- * checks of the 8-bit one.  pixfmt = RIFE_HIP_PIX_RGB8: the calls above. */
+/* The first two taps on frames of format `pixfmt` (include/rife_hip.h RIFE_HIP_PIX_*; rife-v4.6 for the 10-bit formats and RGBA8): the 10-bit gather code
+ * under the checks of the 8-bit one.  pixfmt = RIFE_HIP_PIX_RGB8: the calls above.  RIFE_HIP_PIX_RGBA8: the colour taps are those of the RGB8 frames (alpha
+ * reaches no stem), and tap what = 2 (the unfused tail before quantisation) returns FOUR planes, 4 x hp x wp: out0's three and the alpha plane. */
 int rife_hip_v4_extract_flow_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, int fi, const float* const* inject,
                                 int n_inject, float* out6chw, int pixfmt);
 int rife_hip_v4_tap_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, int what, int b, const float* const* inject,

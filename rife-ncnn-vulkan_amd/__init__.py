@@ -35,6 +35,7 @@ C_ABI_SYMBOLS = [
 ]
 # pixel formats at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*)
 PIX_RGB8, PIX_RGB10_U16, PIX_A2B10G10R10 = 0, 1, 2
+PIX_RGBA8 = 4      # 3 is reserved
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px"]
@@ -209,25 +210,34 @@ def frame_bytes(w, h, pixfmt=PIX_RGB8):
     return int(lib().rife_hip_frame_bytes(int(w), int(h), int(pixfmt)))
 
 
-_PIX_LAYOUT = {PIX_RGB8: (np.uint8, 3), PIX_RGB10_U16: (np.uint16, 3), PIX_A2B10G10R10: (np.uint32, 2)}      # dtype, ndim
+_PIX_LAYOUT = {PIX_RGB8: (np.uint8, 3), PIX_RGB10_U16: (np.uint16, 3), PIX_A2B10G10R10: (np.uint32, 2), PIX_RGBA8: (np.uint8, 3)}      # dtype, ndim
+_PIX_NAME = {PIX_RGB10_U16: "RGB10_U16", PIX_A2B10G10R10: "A2B10G10R10", PIX_RGBA8: "RGBA8"}
+
+
+def _pix_shape(pixfmt, h, w):
+    return (h, w) if pixfmt == PIX_A2B10G10R10 else (h, w, 4) if pixfmt == PIX_RGBA8 else (h, w, 3)
 
 
 def _pix_of(image, pixfmt=None):
-    """The pixel format of a frame array: a uint16 (h, w, 3) array is RGB10_U16, a uint32 (h, w) array A2B10G10R10; None = neither (the 8-bit path, which
-    converts whatever it is given to uint8 as it always did).  An explicit `pixfmt` must match the array exactly.  Raises before any library call."""
+    """The pixel format of a frame array: a uint16 (h, w, 3) array is RGB10_U16, a uint32 (h, w) array A2B10G10R10, a uint8 (h, w, 4) array RGBA8; None =
+    none of them (the 8-bit RGB path, which converts whatever it is given to uint8 as it always did).  An explicit `pixfmt` must match the array exactly.
+    Raises before any library call."""
     a = image
     if pixfmt is None:
-        if not isinstance(a, np.ndarray) or a.dtype not in (np.uint16, np.uint32):
+        if isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 4:
+            pixfmt = PIX_RGBA8
+        elif not isinstance(a, np.ndarray) or a.dtype not in (np.uint16, np.uint32):
             return None
-        pixfmt = PIX_RGB10_U16 if a.dtype == np.uint16 else PIX_A2B10G10R10
+        else:
+            pixfmt = PIX_RGB10_U16 if a.dtype == np.uint16 else PIX_A2B10G10R10
     if pixfmt not in _PIX_LAYOUT:
         raise ValueError("unknown pixfmt %r" % (pixfmt,))
     if pixfmt == PIX_RGB8:
         return None
     dt, nd = _PIX_LAYOUT[pixfmt]
-    if not isinstance(a, np.ndarray) or a.dtype != dt or a.ndim != nd or (nd == 3 and a.shape[2] != 3) or a.size == 0:
-        raise ValueError("a %s frame is a %s array of shape %s" % ("RGB10_U16" if pixfmt == PIX_RGB10_U16 else "A2B10G10R10", np.dtype(dt).name,
-                                                                   "(h, w, 3)" if nd == 3 else "(h, w)"))
+    nch = 4 if pixfmt == PIX_RGBA8 else 3
+    if not isinstance(a, np.ndarray) or a.dtype != dt or a.ndim != nd or (nd == 3 and a.shape[2] != nch) or a.size == 0:
+        raise ValueError("a %s frame is a %s array of shape %s" % (_PIX_NAME[pixfmt], np.dtype(dt).name, "(h, w, %d)" % nch if nd == 3 else "(h, w)"))
     return pixfmt
 
 
@@ -272,7 +282,8 @@ class RIFE:
     def process(self, in0image, in1image, timestep, outimage=None, pixfmt=None):
         """in0image / in1image: (h, w, 3) uint8 RGB arrays (the ncnn::Mat the CLI builds, src/main.cpp:187).
         Deep colour (rife-v4.6, plain mode): (h, w, 3) uint16 arrays of codes 0..1023 (RGB10_U16) or (h, w) uint32 arrays (A2B10G10R10), selected by the
-        arrays' dtype or by pixfmt=; the result has the inputs' format."""
+        arrays' dtype or by pixfmt=; the result has the inputs' format.
+        Alpha (rife-v4.6, plain mode): (h, w, 4) uint8 RGBA arrays (RGBA8); the colour bytes are those of the RGB call, alpha is warped and blended with it."""
         px = _pix_of(in0image, pixfmt)
         if px is not None:
             if _pix_of(in1image, px) != px or in1image.shape != in0image.shape:
@@ -319,7 +330,7 @@ class RIFE:
             raise ValueError("the two frames differ in pixel format")
         if frame0.pixfmt != PIX_RGB8:      # the result has the format the frames were uploaded in
             dt, nd = _PIX_LAYOUT[frame0.pixfmt]
-            shape = (frame0.h, frame0.w, 3) if nd == 3 else (frame0.h, frame0.w)
+            shape = _pix_shape(frame0.pixfmt, frame0.h, frame0.w)
             out = outimage if outimage is not None else np.empty(shape, dt)
             if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dt or not out.flags.c_contiguous or not out.flags.writeable:
                 raise ValueError("outimage must be a writable contiguous array of the frames' format and size")
@@ -445,7 +456,7 @@ class RIFE:
         h, w = a.shape[:2]
         wp, hp = (w + 31) // 32 * 32, (h + 31) // 32 * 32
         s = {1: 4, 2: 2, 3: 1}.get(b, 1)
-        out = np.empty((3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4) else (12, hp // s, wp // s), np.float32)
+        out = np.empty((4 if px == PIX_RGBA8 else 3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4) else (12, hp // s, wp // s), np.float32)
         inj = [np.ascontiguousarray(f, dtype=np.float32) for f in inject]
         arr = (ctypes.c_void_p * max(1, len(inj)))(*[f.ctypes.data for f in inj])
         if px is not None:

@@ -98,6 +98,37 @@ __global__ void k_canon10_packed(const uint32_t* __restrict__ in, uint32_t* __re
     if (i < n) out[i] = in[i] | 0xc0000000u;
 }
 
+// ---- alpha, include/rife_hip.h RIFE_HIP_PIX_RGBA8 (u8 HWC, R G B A): the resident depth-8 dword with alpha in its spare byte, R | G << 8 | B << 16 | A << 24.
+// unpack_rgb<8> masks that byte off, so everything that estimates flows and mask sees the colour alone; the quantising tails read it as a fourth plane
+// (unpack_a) from the taps they load anyway.  Padding: colour zero as everywhere, alpha REPLICATED from the nearest frame pixel - with zero-padded alpha
+// a flow of a few pixels into the padding turns an opaque matte transparent along the right and bottom edge. ----
+__global__ void k_preproc_rgba(const uint8_t* __restrict__ px, int w, int h, uint32_t* __restrict__ out, int wp, int hp) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= wp) return;
+    const uint8_t* p = px + ((size_t)min(y, h - 1) * w + min(x, w - 1)) * 4;      // byte loads: the frame may sit at any address
+    const uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    out[(size_t)y * wp + x] = (x < w && y < h) ? v : (v & 0xff000000u);
+}
+// four pixels per lane (w % 4 == 0 and a 16-byte aligned frame): one 16-byte load, one 16-byte store; lanes right of the frame load the row's last pixel
+__global__ void k_preproc_rgba4(const uint32_t* __restrict__ px, int w, int h, uint32_t* __restrict__ out, int wp, int hp) {
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
+    if (x4 >= wp) return;
+    const uint32_t* const row = px + (size_t)min(y, h - 1) * w;
+    uint4 v;
+    if (x4 < w) {
+        v = *reinterpret_cast<const uint4*>(row + x4);
+        if (y >= h) { v.x &= 0xff000000u; v.y &= 0xff000000u; v.z &= 0xff000000u; v.w &= 0xff000000u; }
+    } else {
+        const uint32_t e = row[w - 1] & 0xff000000u;
+        v = make_uint4(e, e, e, e);
+    }
+    *reinterpret_cast<uint4*>(out + (size_t)y * wp + x4) = v;
+}
+
+// depth of the resident frames a quantising kernel of pixel format PX (include/rife_hip.h RIFE_HIP_PIX_*) reads: 10:10:10 for the two 10-bit formats
+__host__ __device__ constexpr int px_depth(int PX) { return (PX == 1 || PX == 2) ? 10 : 8; }
+__host__ __device__ constexpr bool px_deep(int PX) { return PX == 1 || PX == 2; }
+
 template <int D = 8>
 __device__ __forceinline__ float3 unpack_rgb(uint32_t v) {
     if (D == 10) {
@@ -166,6 +197,12 @@ __device__ __forceinline__ float3 warp_finish(const WarpLoads& t) {
     const float3 a = unpack_rgb<D>(t.l0 ? t.r0.x : t.r0.y), b = unpack_rgb<D>(t.l1 ? t.r0.x : t.r0.y), c = unpack_rgb<D>(t.l0 ? t.r1.x : t.r1.y), d = unpack_rgb<D>(t.l1 ? t.r1.x : t.r1.y);
     return make_float3(warp_lerp(a.x, b.x, c.x, d.x, t.alpha, t.beta), warp_lerp(a.y, b.y, c.y, d.y, t.alpha, t.beta), warp_lerp(a.z, b.z, c.z, d.z, t.alpha, t.beta));
 }
+// RGBA8 frames: the fourth plane, A = code * (1 / 255.f) from byte 3 of the depth-8 dword, warped from the SAME loads as the colour (no extra traffic)
+__device__ __forceinline__ float unpack_a(uint32_t v) { return (float)(v >> 24) * (1 / 255.f); }
+__device__ __forceinline__ float warp_finish_a(const WarpLoads& t) {
+    return warp_lerp(unpack_a(t.l0 ? t.r0.x : t.r0.y), unpack_a(t.l1 ? t.r0.x : t.r0.y), unpack_a(t.l0 ? t.r1.x : t.r1.y), unpack_a(t.l1 ? t.r1.x : t.r1.y), t.alpha, t.beta);
+}
+__device__ __forceinline__ uint32_t quant8(float v) { return (uint32_t)min(max((int)(v * 255.f + 0.5f), 0), 255); }
 template <int D = 8>
 __device__ __forceinline__ float3 warp_rgbx(const uint32_t* __restrict__ img, int x, int y, float fx, float fy, int w, int h) {
     return warp_finish<D>(warp_issue(img, x, y, fx, fy, w, h));
@@ -394,7 +431,8 @@ __global__ void k_flow_update2(const float* __restrict__ flow0, const float* __r
 // Tail of the graph + postproc (flownet.param:202-217, rife.cpp:4373-4397 / rife_postproc.comp:39-62):
 //   F += flow3[0:4]; M += flow3[4]; m = sigmoid(M); out = warp(in0,F.xy)*m + warp(in1,F.zw)*(1-m);
 //   u8 = clamp((int)(out*255 + 0.5), 0, 255), cropped to w x h, HWC RGB.
-// PX (include/rife_hip.h RIFE_HIP_PIX_*): 0 = u8 RGB; 1 = three u16 codes 0..1023 per pixel; 2 = one A2B10G10R10 dword per pixel (alpha written as 3).
+// PX (include/rife_hip.h RIFE_HIP_PIX_*): 0 = u8 RGB; 1 = three u16 codes 0..1023 per pixel; 2 = one A2B10G10R10 dword per pixel (alpha written as 3);
+// 4 = u8 RGBA: depth-8 frames with alpha in byte 3, a = warp(A0) * m + warp(A1) * (1 - m) in the colour channels' arithmetic, quantised like them.
 // The 10-bit forms read 10:10:10 frames and quantise as min(max((int)(v * 1023.f + 0.5f), 0), 1023), straight into the caller's format.
 __device__ __forceinline__ uint32_t quant10(float r, float g, float b) {
     return (uint32_t)min(max((int)(r * 1023.f + 0.5f), 0), 1023) | ((uint32_t)min(max((int)(g * 1023.f + 0.5f), 0), 1023) << 10) |
@@ -412,7 +450,7 @@ __device__ __forceinline__ void store_px10(uint8_t* __restrict__ out, size_t i, 
 template <int PX>
 __device__ __forceinline__ void final_body(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
                                            const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
-    constexpr int D = PX ? 10 : 8;
+    constexpr int D = px_depth(PX);
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * wp + x;
@@ -423,10 +461,22 @@ __device__ __forceinline__ void final_body(const uint32_t* __restrict__ img0, co
     const float mm = M[i] + fl[4];
     const float m = 1.f / (1.f + expf(-mm));
     const float rm = 1.0f - m;
+    if (PX == 4) {      // RGBA8: alpha from the same taps as the colour
+        const WarpLoads t1 = warp_issue(img1, x, y, f.z, f.w, wp, hp);
+        const WarpLoads t0 = warp_issue(img0, x, y, f.x, f.y, wp, hp);
+        const float3 w1 = warp_finish<8>(t1);
+        const float3 w0 = warp_finish<8>(t0);
+        const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
+        const float al = warp_finish_a(t0) * m + warp_finish_a(t1) * rm;
+        const uint32_t pk = quant8(r) | (quant8(g) << 8) | (quant8(b) << 16) | (quant8(al) << 24);
+        uint8_t* o = out + ((size_t)y * w + x) * 4;      // byte stores: the frame may sit at any address
+        o[0] = (uint8_t)pk; o[1] = (uint8_t)(pk >> 8); o[2] = (uint8_t)(pk >> 16); o[3] = (uint8_t)(pk >> 24);
+        return;
+    }
     const float3 w1 = warp_rgbx<D>(img1, x, y, f.z, f.w, wp, hp);
     const float3 w0 = warp_rgbx<D>(img0, x, y, f.x, f.y, wp, hp);
     const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
-    if (PX) { store_px10<PX>(out, (size_t)y * w + x, quant10(r, g, b)); return; }
+    if (px_deep(PX)) { store_px10<PX>(out, (size_t)y * w + x, quant10(r, g, b)); return; }
     uint8_t* o = out + ((size_t)y * w + x) * 3;
     o[0] = (uint8_t)min(max((int)(r * 255.f + 0.5f), 0), 255);
     o[1] = (uint8_t)min(max((int)(g * 255.f + 0.5f), 0), 255);
@@ -625,6 +675,24 @@ __device__ __forceinline__ void final_float_body(const uint32_t* __restrict__ im
 __global__ void k_final_float(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
                               const float* __restrict__ M, const float* __restrict__ flow3, float4* __restrict__ out, int wp, int hp) {
     final_float_body<8>(img0, img1, F, M, flow3, out, wp, hp);
+}
+// RGBA8 frames: the alpha plane before quantisation in .w (test build's tap of the unfused tail)
+__global__ void k_final_float_a(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                                const float* __restrict__ M, const float* __restrict__ flow3, float4* __restrict__ out, int wp, int hp) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= wp) return;
+    const size_t i = (size_t)y * wp + x;
+    const float* fl = flow3 + i * 8;
+    float4 f = F[i];
+    f.x = f.x + fl[0]; f.y = f.y + fl[1]; f.z = f.z + fl[2]; f.w = f.w + fl[3];
+    const float mm = M[i] + fl[4];
+    const float m = 1.f / (1.f + expf(-mm));
+    const float rm = 1.0f - m;
+    const WarpLoads t1 = warp_issue(img1, x, y, f.z, f.w, wp, hp);
+    const WarpLoads t0 = warp_issue(img0, x, y, f.x, f.y, wp, hp);
+    const float3 w1 = warp_finish<8>(t1);
+    const float3 w0 = warp_finish<8>(t0);
+    out[i] = make_float4(w0.x * m + w1.x * rm, w0.y * m + w1.y * rm, w0.z * m + w1.z * rm, warp_finish_a(t0) * m + warp_finish_a(t1) * rm);
 }
 __global__ void k_final_float_d10(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
                                   const float* __restrict__ M, const float* __restrict__ flow3, float4* __restrict__ out, int wp, int hp) {

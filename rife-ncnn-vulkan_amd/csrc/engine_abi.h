@@ -149,14 +149,14 @@ static int process_common(const rife_hip* E, int w, int h, float timestep) {
     return 0;
 }
 
-// ---- deep colour (include/rife_hip.h RIFE_HIP_PIX_*) ----
-// The 10-bit formats are served by the plain rife-v4.6 schedule only; everything else is refused BEFORE anything is written or enqueued.
-static int deep_supported(const rife_hip* E, int pixfmt) {
+// ---- deep colour and alpha (include/rife_hip.h RIFE_HIP_PIX_*) ----
+// The 10-bit formats and RGBA8 are served by the plain rife-v4.6 schedule only; everything else is refused BEFORE anything is written or enqueued.
+static int pixfmt_supported(const rife_hip* E, int pixfmt) {
     if (pixfmt == RIFE_HIP_PIX_RGB8) return 0;
     const char* what = E->v1 ? "model family rife (v1: rife, rife-HD, rife-UHD, rife-anime)" : (!E->v4 && E->v3) ? "model family rife-v3.x" : !E->v4 ? "model family rife-v2.x"
                        : E->v40 ? "model family rife-v4 (4.0)" : E->tta ? "TTA mode (-x)" : E->tta_temporal ? "temporal TTA mode (-z)" : E->uhd ? "UHD mode (-u)" : nullptr;
     if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string("10-bit frames are served for model family rife-v4.6 in plain mode only, not for ") + what);
+    return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
 }
 // argument checks of the _px entry points that need no engine; then "no HIP device at all" before anything looks at the engine
 static int px_precheck(int pixfmt, bool ptrs_ok, int w, int h) {
@@ -183,7 +183,7 @@ static int copy_frame_device(hipStream_t st, const void* src, void* dst, int w, 
         hipLaunchKernelGGL(k_canon10_u16, dim3((unsigned)((npix * 3 + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), npix * 3);
     else if (pixfmt == RIFE_HIP_PIX_A2B10G10R10)
         hipLaunchKernelGGL(k_canon10_packed, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), npix);
-    else { HIPCHK(hipMemcpyAsync(dst, src, npix * 3, hipMemcpyDeviceToDevice, st)); return 0; }
+    else { HIPCHK(hipMemcpyAsync(dst, src, npix * pix_bpp(pixfmt), hipMemcpyDeviceToDevice, st)); return 0; }      // RGB8, RGBA8: the bytes unchanged
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -275,7 +275,7 @@ static void release_ctx(const rife_hip* E, std::unique_ptr<Ctx>& c) {
 
 // H2D of both frames, the whole pass and the D2H of the result, all enqueued on the workspace's stream (no host wait)
 static int enqueue_host_pair(const rife_hip* E, Ctx& c, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out) {
-    const size_t nbytes = (size_t)w * h * pix_bpp(c.pixfmt);      // c.pixfmt: set by lease_ctx (deep colour: rife-v4.6 plain pass only, deep_supported)
+    const size_t nbytes = (size_t)w * h * pix_bpp(c.pixfmt);      // c.pixfmt: set by lease_ctx (deep colour: rife-v4.6 plain pass only, pixfmt_supported)
     hipError_t e;
     {
         // Upload token (round 6, RIFE_HIP_H2D_TOKEN=0 in the test build: off): one caller uploads at a time and holds the token until its two frames have landed.
@@ -308,10 +308,10 @@ static int rife_hip_process_impl(const rife_hip_t* E, const uint8_t* in0, const 
     int rc;
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (!in0 || !in1 || !out) return fail(RIFE_HIP_EINVAL, "null frame pointer");
-    if ((rc = deep_supported(E, pixfmt))) return rc;
+    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     const size_t nbytes = (size_t)w * h * pix_bpp(pixfmt);
     // rife.cpp:2470-2480: timestep 0 / 1 return an input frame unchanged (the reference rebinds the Mat; a copy is pixel-identical)
-    if (pixfmt && (timestep == 0.f || timestep == 1.f)) { canon10_host(out, timestep == 0.f ? in0 : in1, (size_t)w * h, pixfmt); return 0; }
+    if (pix_deep(pixfmt) && (timestep == 0.f || timestep == 1.f)) { canon10_host(out, timestep == 0.f ? in0 : in1, (size_t)w * h, pixfmt); return 0; }
     if (timestep == 0.f) { std::memmove(out, in0, nbytes); return 0; }
     if (timestep == 1.f) { std::memmove(out, in1, nbytes); return 0; }
     if ((rc = check_device(E->gpuid))) return rc;
@@ -493,7 +493,7 @@ static int rife_hip_frame_upload_impl(const rife_hip_t* E, const uint8_t* rgb, i
     if (!E || !rgb || !frame) return fail(RIFE_HIP_EINVAL, "null argument");
     if (w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "bad frame size");
     int rc;
-    if ((rc = deep_supported(E, pixfmt))) return rc;
+    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
     std::unique_ptr<rife_hip_frame> f(new rife_hip_frame);
     f->w = w; f->h = h; f->gpuid = E->gpuid; f->pixfmt = pixfmt;
@@ -542,7 +542,7 @@ static int rife_hip_process_frames_impl(const rife_hip_t* E, const rife_hip_fram
     int rc;
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (f0->gpuid != E->gpuid || f1->gpuid != E->gpuid) return fail(RIFE_HIP_EINVAL, "frame was uploaded to another device");
-    if ((rc = deep_supported(E, pixfmt))) return rc;
+    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
     const size_t nbytes = (size_t)w * h * pix_bpp(pixfmt);
     if (timestep == 0.f || timestep == 1.f) {                 // rife.cpp:2470-2480 (a copy stream of the pool, never the legacy stream)
@@ -556,7 +556,7 @@ static int rife_hip_process_frames_impl(const rife_hip_t* E, const rife_hip_fram
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (st) { std::lock_guard<std::mutex> g(E->mu); E->upload_streams.push_back(st); }
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("frame download: ") + hipGetErrorString(e));
-        if (pixfmt) canon10_host(out, out, (size_t)w * h, pixfmt);
+        if (pix_deep(pixfmt)) canon10_host(out, out, (size_t)w * h, pixfmt);
         return 0;
     }
     std::unique_ptr<Ctx> c;
@@ -587,7 +587,7 @@ static int rife_hip_process_device_impl(const rife_hip_t* E, const void* d_in0, 
     int rc;
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (!d_in0 || !d_in1 || !d_out) return fail(RIFE_HIP_EINVAL, "null frame pointer");
-    if ((rc = deep_supported(E, pixfmt))) return rc;
+    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
     Ctx* c;
     {
@@ -651,7 +651,7 @@ static int rife_hip_process_device_batch_impl(const rife_hip_t* E, int n, const 
     if (n < 0 || (n > 0 && (!d_in0 || !d_in1 || !timestep || !d_out))) return fail(RIFE_HIP_EINVAL, "bad batch arguments");
     if ((rc = process_common(E, w, h, 0.5f))) return rc;
     for (int i = 0; i < n; i++) if (!d_in0[i] || !d_in1[i] || !d_out[i]) return fail(RIFE_HIP_EINVAL, "null frame pointer");
-    if ((rc = deep_supported(E, pixfmt))) return rc;
+    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if (n == 0) return 0;
     if ((rc = check_device(E->gpuid))) return rc;
     const bool groups = E->v4 && !E->v40 && !E->v1 && !E->tta && !E->tta_temporal && E->t64;
@@ -846,7 +846,7 @@ static int rife_hip_v4_extract_flow_impl(const rife_hip_t* E, const uint8_t* in0
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (!E->v4) return fail(RIFE_HIP_EINVAL, "stage taps exist for the rife-v4 family only");
     if (pix_bpp(pixfmt) == 0) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
-    if ((rc = deep_supported(E, pixfmt))) return rc;
+    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if (fi < 0 || fi > 3 || n_inject < 0 || n_inject > fi) return fail(RIFE_HIP_EINVAL, "bad stage index");
     if ((rc = check_device(E->gpuid))) return rc;
     Ctx c;
@@ -932,8 +932,8 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (!E->v4 || E->v40) return fail(RIFE_HIP_EINVAL, "the gather taps exist for the rife-v4.6 graph only");
     if (pix_bpp(pixfmt) == 0) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
-    if ((rc = deep_supported(E, pixfmt))) return rc;
-    if (pixfmt && what == 3) return fail(RIFE_HIP_EINVAL, "tap 3 (an A/B form the product does not run) is not served at depth 10");
+    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
+    if (pixfmt && what == 3) return fail(RIFE_HIP_EINVAL, "tap 3 (an A/B form the product does not run) is served for RGB8 frames only");
     if (what < 0 || what > 5) return fail(RIFE_HIP_EINVAL, "bad tap");
     if (what == 5 && b != 3) return fail(RIFE_HIP_EINVAL, "the row-streaming stem kernel serves block 3");
     if (what == 2 ? n_inject != 4 : (b < 1 || b > 3 || n_inject != b)) return fail(RIFE_HIP_EINVAL, "bad block / injection count");
@@ -990,7 +990,7 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
                     a.out = dout; a.timestep = timestep; a.tsp = nullptr; a.wp = c.wp; a.hp = c.hp; a.Hq = Hq; a.Wq = Wq; a.pitch = G.pitch; a.plane = G.plane();
                     a.nunits = ((Wq + SRS_SW - 1) / SRS_SW) * Hq;
                     const int nwg = std::min(2 * device_cus(), a.nunits);
-                    if (pixfmt) hipLaunchKernelGGL((stem_rs_kernel<0, 10>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, st, a);
+                    if (pix_deep(pixfmt)) hipLaunchKernelGGL((stem_rs_kernel<0, 10>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, st, a);
                     else hipLaunchKernelGGL((stem_rs_kernel<0>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, st, a);
                     HIPCHK(hipGetLastError());
                     HIPCHK(hipMemcpyAsync(host.data(), dout, nb, hipMemcpyDeviceToHost, st));
@@ -1013,11 +1013,13 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
     if (what == 2) {
         float4* outf = nullptr;
         if ((rc = dalloc(c, outf, (size_t)c.wp * c.hp))) return rc;
-        if (pixfmt) hipLaunchKernelGGL(k_final_float_d10, grid2d(c.wp, c.hp), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], outf, c.wp, c.hp);
+        const int nch = pixfmt == RIFE_HIP_PIX_RGBA8 ? 4 : 3;      // RGBA8: the alpha plane before quantisation as a fourth channel
+        if (pix_deep(pixfmt)) hipLaunchKernelGGL(k_final_float_d10, grid2d(c.wp, c.hp), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], outf, c.wp, c.hp);
+        else if (nch == 4) hipLaunchKernelGGL(k_final_float_a, grid2d(c.wp, c.hp), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], outf, c.wp, c.hp);
         else hipLaunchKernelGGL(k_final_float, grid2d(c.wp, c.hp), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], outf, c.wp, c.hp);
-        hipLaunchKernelGGL(k_nhwc_to_chw, grid2d(c.wp, c.hp), dim3(256), 0, st, reinterpret_cast<const float*>(outf), tmp, 3, c.hp, c.wp, 4);
+        hipLaunchKernelGGL(k_nhwc_to_chw, grid2d(c.wp, c.hp), dim3(256), 0, st, reinterpret_cast<const float*>(outf), tmp, nch, c.hp, c.wp, 4);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, tmp, (size_t)c.wp * c.hp * 3 * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(out, tmp, (size_t)c.wp * c.hp * nch * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         return 0;
     }
@@ -1057,11 +1059,11 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0, 0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, 0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, 1, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-        if (pending && pixfmt) {
+        if (pending && pix_deep(pixfmt)) {
             fa.pend.flow = pending; fa.pend.Fw = c.F2; fa.pend.Mw = c.M2;
             if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 1, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
             else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 1, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
-        } else if (pixfmt) {
+        } else if (pix_deep(pixfmt)) {
             if (s == 4) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
             else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
             else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 0, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);

@@ -64,7 +64,7 @@ struct Ctx {
     std::mutex use;                                                   // rife_hip_process_device: one caller at a time per stream workspace
     int w = 0, h = 0, wp = 0, hp = 0;
     int pixfmt = 0;                                                   // RIFE_HIP_PIX_* of the frames img0 / img1 hold and of the output being written (set per call; rife-v4.6 plain pass only)
-    int stage_bpp = 0;                                                // bytes per pixel d_in0 / d_in1 / d_out were sized for (3; 6 once a deep-colour call has used the workspace)
+    int stage_bpp = 0;                                                // bytes per pixel d_in0 / d_in1 / d_out were sized for (3; 4 / 6 once an RGBA or deep-colour call has used the workspace)
     uint8_t *d_in0 = nullptr, *d_in1 = nullptr, *d_out = nullptr;   // staging for the host-buffer entry point
     uint32_t *img0 = nullptr, *img1 = nullptr;                       // padded RGBX u8
     float *X = nullptr, *S1 = nullptr, *T0 = nullptr, *T1 = nullptr; // block input, stem-1 output, trunk ping/pong

@@ -123,6 +123,8 @@ static int launch_conv(const ConvLayer& L, TensorView x, int H, int W, TensorVie
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_FINAL, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(head_h2_kernel<EPI_DECONV_PS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, headh2_lds_bytes()));
                 hdone[dev] = true;
             }
@@ -131,7 +133,11 @@ static int launch_conv(const ConvLayer& L, TensorView x, int H, int W, TensorVie
         if (L.epi == EPI_DECONV_PS && (L.cout != 24 || y.ld != 8 || y.coff != 0))
             return fail(RIFE_HIP_EINVAL, "the PixelShuffle head kernel writes the 6-channel flow tensor [4H][4W][8] only");
         if (s16_pitch > 0 && L.epi != EPI_DECONV_PS) return fail(RIFE_HIP_EINVAL, "no S16 variant of this head");
-        if (fin && fin->pixfmt && L.epi == EPI_DECONV_PS) {      // deep colour: 10:10:10 frames in, the caller's 10-bit format out
+        if (fin && fin->pixfmt == RIFE_HIP_PIX_RGBA8 && L.epi == EPI_DECONV_PS) {      // depth-8 frames with alpha in byte 3, RGBA8 out
+            if (s16_pitch > 0) hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, true, 4>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
+            else hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, false, 4>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
+        }
+        else if (fin && fin->pixfmt && L.epi == EPI_DECONV_PS) {      // deep colour: 10:10:10 frames in, the caller's 10-bit format out
             const bool u16 = fin->pixfmt == RIFE_HIP_PIX_RGB10_U16;
             if (s16_pitch > 0 && u16) hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, true, 1>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);
             else if (s16_pitch > 0) hipLaunchKernelGGL((head_h2_kernel<EPI_FINAL, true, 2>), dim3(nb, gy), dim3(512), headh2_lds_bytes(), st, a, *fin);

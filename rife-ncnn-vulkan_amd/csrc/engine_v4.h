@@ -78,7 +78,11 @@ static int ensure_ctx_dims(Ctx& c, int w, int h, int wp, int hp, const Ctx* scra
 }
 
 // bytes per pixel of a frame at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*); 0 = unknown format
-static inline int pix_bpp(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB8 ? 3 : pixfmt == RIFE_HIP_PIX_RGB10_U16 ? 6 : pixfmt == RIFE_HIP_PIX_A2B10G10R10 ? 4 : 0; }
+static inline int pix_bpp(int pixfmt) {
+    return pixfmt == RIFE_HIP_PIX_RGB8 ? 3 : pixfmt == RIFE_HIP_PIX_RGB10_U16 ? 6 : (pixfmt == RIFE_HIP_PIX_A2B10G10R10 || pixfmt == RIFE_HIP_PIX_RGBA8) ? 4 : 0;
+}
+// the resident frames of this format are 10:10:10 dwords (the D = 10 instantiations of everything that reads a frame); RGB8 and RGBA8 frames are depth 8
+static inline bool pix_deep(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB10_U16 || pixfmt == RIFE_HIP_PIX_A2B10G10R10; }
 // the workspace serves frames of `pixfmt` from here on: staging buffers of that size, c.pixfmt for every launch site that reads or writes a frame
 static int ensure_ctx(Ctx& c, int w, int h, int pixfmt = RIFE_HIP_PIX_RGB8) {
     const int rc = ensure_ctx_dims(c, w, h, (w + 31) / 32 * 32, (h + 31) / 32 * 32, nullptr, true, false, pix_bpp(pixfmt));   // pad to 32n, rife.cpp:2499-2500
@@ -111,6 +115,12 @@ static inline void launch_preproc(hipStream_t st, const uint8_t* rgb, int w, int
         else hipLaunchKernelGGL(k_preproc10_packed, grid2d(wp, hp), dim3(256), 0, st, p, w, h, out, wp, hp);
         return;
     }
+    if (pixfmt == RIFE_HIP_PIX_RGBA8) {      // alpha into the spare byte, edge-replicated into the padding
+        if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 15) == 0)
+            hipLaunchKernelGGL(k_preproc_rgba4, dim3((wp / 4 + 255) / 256, hp), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(rgb), w, h, out, wp, hp);
+        else hipLaunchKernelGGL(k_preproc_rgba, grid2d(wp, hp), dim3(256), 0, st, rgb, w, h, out, wp, hp);
+        return;
+    }
     if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 3) == 0) hipLaunchKernelGGL(k_preproc4, dim3((wp / 4 + 255) / 256, hp), dim3(256), 0, st, rgb, w, h, out, wp, hp);
     else hipLaunchKernelGGL(k_preproc, grid2d(wp, hp), dim3(256), 0, st, rgb, w, h, out, wp, hp);
 }
@@ -124,7 +134,7 @@ static int run_assemble(const rife_hip& E, Ctx& c, int b, float timestep, const 
     Timed t(E.prof, "assemble", 0, st);
     const int s = E.blk[b].scale;
     dim3 g = grid2d(c.wp / s, c.hp / s);
-    if (c.pixfmt) {
+    if (pix_deep(c.pixfmt)) {
         if (b == 0) hipLaunchKernelGGL(k_assemble0_d10, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.X, c.wp, c.hp);
         else if (s == 4) hipLaunchKernelGGL((k_assemble<4, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
         else if (s == 2) hipLaunchKernelGGL((k_assemble<2, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
@@ -158,7 +168,7 @@ static int launch_stem_rs(const rife_hip& E, Ctx& c, const rife_hip::Block& B, u
     a.out = out; a.timestep = timestep; a.tsp = tsp; a.wp = c.wp; a.hp = c.hp; a.Hq = Hq; a.Wq = Wq; a.pitch = G.pitch; a.plane = G.plane();
     a.nunits = ((Wq + SRS_SW - 1) / SRS_SW) * Hq;
     const int nwg = std::min(2 * device_cus(), a.nunits);
-    if (c.pixfmt) hipLaunchKernelGGL((stem_rs_kernel<0, 10>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
+    if (pix_deep(c.pixfmt)) hipLaunchKernelGGL((stem_rs_kernel<0, 10>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
     else hipLaunchKernelGGL((stem_rs_kernel<0>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("stem_rs launch: ") + hipGetErrorString(e));
@@ -174,6 +184,7 @@ static int launch_tail_rs(const rife_hip::Block& B, const unsigned char* in, int
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
             done[dev] = true;
         }
     }
@@ -185,6 +196,7 @@ static int launch_tail_rs(const rife_hip::Block& B, const unsigned char* in, int
     const int nwg = std::min(2 * device_cus(), a.nunits);
     if (fin.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL((tail_rs_kernel<0, 1>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
     else if (fin.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL((tail_rs_kernel<0, 2>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
+    else if (fin.pixfmt == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL((tail_rs_kernel<0, 4>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
     else hipLaunchKernelGGL((tail_rs_kernel<0>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("tail_rs launch: ") + hipGetErrorString(e));
@@ -294,17 +306,17 @@ static int run_block_convs(const rife_hip& E, Ctx& c, int b, float timestep, con
         if (upd_flow) {
             if (s > 2 || !c.F2) return fail(RIFE_HIP_EINVAL, "no fused flow update for this block");
             fa.pend.flow = upd_flow; fa.pend.Fw = c.F2; fa.pend.Mw = c.M2;
-            if (c.pixfmt && s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 1, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else if (c.pixfmt) hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 1, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
+            if (pix_deep(c.pixfmt) && s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 1, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (pix_deep(c.pixfmt)) hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 1, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
             else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, true>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
             else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, true>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
             std::swap(c.F, c.F2); std::swap(c.M, c.M2);
         } else if (first_flow) {      // block 1 right after block 0: F, M are not materialised yet, the stem samples the first update itself (first_flow_merged)
             if (s != 4) return fail(RIFE_HIP_EINVAL, "the first flow update is sampled by the scale-4 stem only");
             fa.pend.flow = first_flow;
-            if (c.pixfmt) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 2, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            if (pix_deep(c.pixfmt)) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 2, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
             else hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-        } else if (c.pixfmt) {
+        } else if (pix_deep(c.pixfmt)) {
             if (s == 4) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
             else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
             else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 0, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
@@ -425,7 +437,7 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         launch_preproc(st, d_in1, c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt);
         HIPCHK(hipGetLastError());
     }
-    if (c.pixfmt && E.v40) return fail(RIFE_HIP_ENOSYS, "10-bit frames are served for model family rife-v4.6 only, not rife-v4");
+    if (c.pixfmt && E.v40) return fail(RIFE_HIP_ENOSYS, "10-bit and RGBA frames are served for model family rife-v4.6 only, not rife-v4");
     const bool fuse_tail = !E.v40 && trunk_h2() && g_head_h2 && g_fuse_tail && E.blk[3].head.d_wh != nullptr;
     FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out, c.w, c.h, c.wp, c.hp, c.pixfmt};
     const float* pending = nullptr;                                      // flow whose update of F, M the next block's stem applies
@@ -456,6 +468,7 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         Timed t(E.prof, "final", 0, st);
         if (c.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         else if (c.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        else if (c.pixfmt == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         HIPCHK(hipGetLastError());
     }
@@ -527,6 +540,7 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
             Ctx& c = *cs[g];
             if (c.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
             else if (c.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
+            else if (c.pixfmt == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
             else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
             HIPCHK(hipGetLastError());
         }

@@ -34,7 +34,7 @@ __device__ __forceinline__ constexpr int head_pair_index(int t, int par) {   // 
 struct FinalArgs {
     const uint32_t *img0, *img1;
     const float4* F; const float* M;
-    uint8_t* out;           // u8 HWC RGB, w x h (pixfmt 0); RGB10_U16 / A2B10G10R10 otherwise
+    uint8_t* out;           // u8 HWC RGB, w x h (pixfmt 0); RGB10_U16 / A2B10G10R10 / RGBA8 otherwise
     int w, h, wp, hp;
     int pixfmt = 0;         // include/rife_hip.h RIFE_HIP_PIX_*: read by the host code that picks the kernel instantiation, never by a kernel
 };
@@ -45,7 +45,7 @@ constexpr int headh2_lds_bytes() { return 2 * 10 * 34 * 80 + 16 * 2 * 32 * 16; }
 // EPI: EPI_DECONV_PS (v4 heads: + PixelShuffle scatter, 24 channels), EPI_DECONV (+ per-channel slope, NHWC store at
 // (2y+py, 2x+px)), EPI_DECONV_SIG (sigmoid).  Output channels are tiled by 32 over the grid (a.nz N-tiles per pixel tile).
 // S16IN: the input is an S16 tensor (conv_t64.h; a.s16_pitch pixels per row, zero border): staging is a plain 16-byte copy.
-// PX (EPI_FINAL only): 0 = u8 frames; 1 / 2 = 10:10:10 frames in, RGB10_U16 / A2B10G10R10 out (k_final_px<PX>'s arithmetic)
+// PX (EPI_FINAL only): 0 = u8 frames; 1 / 2 = 10:10:10 frames in, RGB10_U16 / A2B10G10R10 out; 4 = RGBA8 frames (k_final_px<PX>'s arithmetic)
 template <int EPI, bool S16IN = false, int PX = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void head_h2_kernel(ConvArgs a, FinalArgs fa) {
     constexpr int IH = 10, IW = 34, CC = 16, NT = 32;
@@ -228,10 +228,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                         const float mm = (RIFE_ABL(HEAD_ABL & 2) ? 0.5f : fa.M[i]) + dm;
                         const float m = RIFE_ABL(HEAD_ABL & 8) ? mm * 0.01f : 1.f / (1.f + expf(-mm));
                         const float rm = 1.0f - m;
-                        const float3 w1 = RIFE_ABL(HEAD_ABL & 4) ? make_float3(f.z, f.w, f.z) : warp_rgbx<PX ? 10 : 8>(fa.img1, fx, fy, f.z, f.w, fa.wp, fa.hp);
-                        const float3 w0 = RIFE_ABL(HEAD_ABL & 4) ? make_float3(f.x, f.y, f.x) : warp_rgbx<PX ? 10 : 8>(fa.img0, fx, fy, f.x, f.y, fa.wp, fa.hp);
+                        if (PX == 4) {      // RGBA8: alpha from the same taps as the colour, one dword per pixel
+                            const WarpLoads t1 = warp_issue(fa.img1, fx, fy, f.z, f.w, fa.wp, fa.hp);
+                            const WarpLoads t0 = warp_issue(fa.img0, fx, fy, f.x, f.y, fa.wp, fa.hp);
+                            const float3 w1 = warp_finish<8>(t1);
+                            const float3 w0 = warp_finish<8>(t0);
+                            const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
+                            const float al = warp_finish_a(t0) * m + warp_finish_a(t1) * rm;
+                            const uint32_t q = quant8(r) | (quant8(g) << 8) | (quant8(b) << 16) | (quant8(al) << 24);
+                            uint8_t* o = fa.out + ((size_t)fy * fa.w + fx) * 4;      // byte stores: a device frame may sit at any address
+                            o[0] = (uint8_t)q; o[1] = (uint8_t)(q >> 8); o[2] = (uint8_t)(q >> 16); o[3] = (uint8_t)(q >> 24);
+                            continue;
+                        }
+                        const float3 w1 = RIFE_ABL(HEAD_ABL & 4) ? make_float3(f.z, f.w, f.z) : warp_rgbx<px_depth(PX)>(fa.img1, fx, fy, f.z, f.w, fa.wp, fa.hp);
+                        const float3 w0 = RIFE_ABL(HEAD_ABL & 4) ? make_float3(f.x, f.y, f.x) : warp_rgbx<px_depth(PX)>(fa.img0, fx, fy, f.x, f.y, fa.wp, fa.hp);
                         const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
-                        if (PX) { store_px10<PX>(fa.out, (size_t)fy * fa.w + fx, quant10(r, g, b)); continue; }
+                        if (px_deep(PX)) { store_px10<PX>(fa.out, (size_t)fy * fa.w + fx, quant10(r, g, b)); continue; }
                         pk = (uint32_t)min(max((int)(r * 255.f + 0.5f), 0), 255) | ((uint32_t)min(max((int)(g * 255.f + 0.5f), 0), 255) << 8) |
                              ((uint32_t)min(max((int)(b * 255.f + 0.5f), 0), 255) << 16);
                     }

@@ -8,6 +8,8 @@
 // 819-904), re-hosted on std::thread.  Codecs: PNG (8-bit, non-interlaced) through zlib, binary PPM, and WebP through the
 // system libwebp (its stable simple API, declared below because the image ships the library without headers; lossless encoding
 // like src/webp_image.h:66-68), and baseline JPEG through jpeg_codec.h (quality 100 on output like src/main.cpp:215).
+// -a (absent in the reference, whose readers drop alpha): PNG, WebP and 32-bit BMP are read WITH their alpha, the frames cross the boundary as RGBA
+// Mats (include/rife_hip.h RIFE_HIP_PIX_RGBA8) and leave as RGBA PNG or WebP.  Without -a nothing changes.
 // Host glue only: every pixel of arithmetic happens in librife_hip.so.
 #include <dirent.h>
 #include <getopt.h>
@@ -38,6 +40,8 @@
 extern "C" {      // libwebp simple API (webp/decode.h, webp/encode.h)
 uint8_t* WebPDecodeRGB(const uint8_t* data, size_t data_size, int* width, int* height);
 size_t WebPEncodeLosslessRGB(const uint8_t* rgb, int width, int height, int stride, uint8_t** output);
+uint8_t* WebPDecodeRGBA(const uint8_t* data, size_t data_size, int* width, int* height);
+size_t WebPEncodeLosslessRGBA(const uint8_t* rgba, int width, int height, int stride, uint8_t** output);
 void WebPFree(void* ptr);
 }
 #endif
@@ -66,12 +70,16 @@ static int paeth(int a, int b, int c) {
 
 // PNG (every colour type, bit depth and interlace mode stb_image reads) -> tightly packed 8-bit RGB
 // `wide` != null (-b 10): a 16-bit file also leaves its full samples there (w x h x 3, host order); it stays empty for every other depth
-static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb, std::vector<uint16_t>* wide = nullptr) {
+// `alpha` != null (-a): the file's alpha as w x h bytes - the alpha channel of colour types 4 / 6 (16-bit: its high byte, like the colour), the tRNS chunk of a
+// palette file (entries beyond it are opaque) or the tRNS colour key of a grey / RGB file (the pixel that equals the key in every bit is clear, all others
+// opaque); it stays EMPTY for a file that has neither
+static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb, std::vector<uint16_t>* wide = nullptr,
+                       std::vector<unsigned char>* alpha = nullptr) {
     static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     if (d.size() < 33 || memcmp(d.data(), sig, 8)) return false;
     size_t pos = 8;
     int depth = 0, ctype = 0, interlace = 0;
-    std::vector<unsigned char> idat, pal;
+    std::vector<unsigned char> idat, pal, trns;
     while (pos + 12 <= d.size()) {
         const uint32_t len = be32(&d[pos]);
         const unsigned char* typ = &d[pos + 4];
@@ -82,6 +90,7 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
             w = (int)be32(body); h = (int)be32(body + 4); depth = body[8]; ctype = body[9]; interlace = body[12];
         }
         else if (!memcmp(typ, "PLTE", 4)) pal.assign(body, body + len);
+        else if (!memcmp(typ, "tRNS", 4)) trns.assign(body, body + len);
         else if (!memcmp(typ, "IDAT", 4)) idat.insert(idat.end(), body, body + len);
         else if (!memcmp(typ, "IEND", 4)) break;
         pos += 12 + (size_t)len;
@@ -109,6 +118,11 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
     uLongf rawlen = (uLongf)raw.size();
     if (uncompress(raw.data(), &rawlen, idat.data(), (uLong)idat.size()) != Z_OK || rawlen != raw.size()) return false;
     rgb.assign((size_t)w * h * 3, 0);
+    if (alpha) alpha->clear();
+    // a colour key is two bytes per channel whatever the depth (PNG 11.3.2.1); a short chunk is not a key
+    const bool keyed = alpha && ((ctype == 0 && trns.size() >= 2) || (ctype == 2 && trns.size() >= 6));
+    const bool has_alpha = alpha && (ctype == 4 || ctype == 6 || keyed || (ctype == 3 && !trns.empty()));
+    if (has_alpha) alpha->assign((size_t)w * h, 255);
     if (wide) wide->clear();
     if (wide && depth == 16) wide->assign((size_t)w * h * 3, 0);
     const int gscale = depth == 1 ? 255 : depth == 2 ? 85 : depth == 4 ? 17 : 1;
@@ -140,7 +154,7 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
             }
         }
         off += (stride + 1) * ph;
-        if (!interlace && depth == 8 && ctype == 2) { std::memcpy(rgb.data(), img.data(), img.size()); continue; }      // 8-bit RGB rows are the output rows
+        if (!interlace && depth == 8 && ctype == 2 && !keyed) { std::memcpy(rgb.data(), img.data(), img.size()); continue; }      // 8-bit RGB rows are the output rows
         for (int y = 0; y < ph; y++)
             for (int x = 0; x < pw; x++) {
                 const unsigned char* row = &img[stride * y];
@@ -159,6 +173,20 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
                         o16[c] = (uint16_t)((s16[0] << 8) | s16[1]);
                     }
                 }
+                if (has_alpha) {
+                    unsigned char& al = (*alpha)[(size_t)oy * w + ox];
+                    if (ctype == 4 || ctype == 6) al = (unsigned char)sample(ch - 1);
+                    else if (ctype == 3) { const size_t k = (size_t)sample(0); if (k < trns.size()) al = trns[k]; }
+                    else {                                      // colour key: every bit of every channel (the raw sample, before any scaling)
+                        bool same = true;
+                        for (int c = 0; c < ch && same; c++) {
+                            const int key = (trns[2 * c] << 8) | trns[2 * c + 1];
+                            const int v = depth == 16 ? ((row[((size_t)x * ch + c) * 2] << 8) | row[((size_t)x * ch + c) * 2 + 1]) : sample(c);
+                            same = v == key;
+                        }
+                        if (same) al = 0;
+                    }
+                }
                 if (ctype == 2 || ctype == 6) { o[0] = (unsigned char)sample(0); o[1] = (unsigned char)sample(1); o[2] = (unsigned char)sample(2); }
                 else if (ctype == 0 || ctype == 4) { o[0] = o[1] = o[2] = (unsigned char)(sample(0) * (depth < 8 ? gscale : 1)); }
                 else {
@@ -172,7 +200,9 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
 }
 
 // BMP as stb_image reads it in the reference: uncompressed 24- / 32-bit (BI_RGB, or BI_BITFIELDS with the standard masks) and 8-bit palette
-static bool decode_bmp(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb) {
+// `alpha` != null (-a): a 32-bit file's alpha as w x h bytes - the fourth byte of BI_RGB pixels, or the alpha mask of a BI_BITFIELDS header that has one;
+// like stb_image, a file whose alpha is zero in EVERY pixel is read as opaque (writers that leave the fourth byte unused).  Empty for 24- and 8-bit files.
+static bool decode_bmp(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb, std::vector<unsigned char>* alpha = nullptr) {
     if (d.size() < 54 || d[0] != 'B' || d[1] != 'M') return false;
     auto le32 = [&](size_t o) { return (uint32_t)d[o] | ((uint32_t)d[o + 1] << 8) | ((uint32_t)d[o + 2] << 16) | ((uint32_t)d[o + 3] << 24); };
     const uint32_t dataoff = le32(10), hsz = le32(14);
@@ -188,14 +218,18 @@ static bool decode_bmp(const std::vector<unsigned char>& d, int& w, int& h, std:
     const unsigned char* pal = &d[14 + hsz];
     uint32_t ncol = le32(46);
     if (bits == 8) { if (!ncol) ncol = 256; if (14 + (size_t)hsz + 4 * (size_t)ncol > d.size()) return false; }
-    int rs = 16, gs = 8, bs = 0;                              // 32-bit BI_RGB is B, G, R, X
+    if (alpha) alpha->clear();
+    int rs = 16, gs = 8, bs = 0, as = bits == 32 && comp == 0 ? 24 : -1;      // 32-bit BI_RGB is B, G, R, X (A with -a)
     if (bits == 32 && comp == 3) {
         if (hsz < 52 && 14 + (size_t)hsz + 12 > d.size()) return false;
         const uint32_t rm = le32(54), gm = le32(58), bm = le32(62);
         auto shift_of = [](uint32_t m) { int sft = 0; while (m && !(m & 1)) { m >>= 1; sft++; } return m == 0xff ? sft : -1; };
         rs = shift_of(rm); gs = shift_of(gm); bs = shift_of(bm);
         if (rs < 0 || gs < 0 || bs < 0) return false;
+        if (hsz >= 56 && le32(66)) { as = shift_of(le32(66)); if (as < 0) return false; }      // V3+ header: alpha mask (14 + hsz <= d.size() was checked)
     }
+    if (alpha && as >= 0) alpha->assign((size_t)w * h, 0);
+    bool any_alpha = false;
     rgb.resize((size_t)w * h * 3);
     for (int y = 0; y < h; y++) {
         const unsigned char* row = &d[dataoff + stride * (size_t)(flip ? h - 1 - y : y)];
@@ -205,6 +239,7 @@ static bool decode_bmp(const std::vector<unsigned char>& d, int& w, int& h, std:
             else if (bits == 32) {
                 const uint32_t v = (uint32_t)row[4 * x] | ((uint32_t)row[4 * x + 1] << 8) | ((uint32_t)row[4 * x + 2] << 16) | ((uint32_t)row[4 * x + 3] << 24);
                 o[0] = (unsigned char)(v >> rs); o[1] = (unsigned char)(v >> gs); o[2] = (unsigned char)(v >> bs);
+                if (alpha && as >= 0) { const unsigned char al = (unsigned char)(v >> as); (*alpha)[(size_t)y * w + x] = al; any_alpha |= al != 0; }
             } else {
                 if (row[x] >= ncol) return false;
                 const unsigned char* e = pal + 4 * (size_t)row[x];
@@ -212,6 +247,7 @@ static bool decode_bmp(const std::vector<unsigned char>& d, int& w, int& h, std:
             }
         }
     }
+    if (alpha && as >= 0 && !any_alpha) alpha->assign((size_t)w * h, 255);
     return true;
 }
 
@@ -256,9 +292,9 @@ static bool png_deflate_band(const unsigned char* rgb, size_t stride, int y0, in
     return ok;
 }
 
-// depth 8: rgb = w x h x 3 bytes; depth 16 (-b 10): w x h x 3 big-endian 16-bit samples
-static bool encode_png(const std::string& path, int w, int h, const unsigned char* rgb, int depth = 8) {
-    const size_t stride = (size_t)w * 3 * (depth / 8);
+// depth 8: rgb = w x h x 3 bytes; depth 16 (-b 10): w x h x 3 big-endian 16-bit samples; ch = 4 (-a): w x h x 4 bytes R G B A, colour type 6
+static bool encode_png(const std::string& path, int w, int h, const unsigned char* rgb, int depth = 8, int ch = 3) {
+    const size_t stride = (size_t)w * ch * (depth / 8);
     // bands of about 1 MB of pixels, at most 64 (a band must stay below the 4 GB zlib counts in any case)
     int nband = (int)std::min<size_t>(64, std::max<size_t>(1, stride * h >> 20));
     nband = std::min(nband, h);
@@ -290,7 +326,7 @@ static bool encode_png(const std::string& path, int w, int h, const unsigned cha
     const size_t clen = zs.size();
     std::vector<unsigned char> out = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     unsigned char ihdr[13] = {(unsigned char)(w >> 24), (unsigned char)(w >> 16), (unsigned char)(w >> 8), (unsigned char)w,
-                              (unsigned char)(h >> 24), (unsigned char)(h >> 16), (unsigned char)(h >> 8), (unsigned char)h, (unsigned char)depth, 2, 0, 0, 0};
+                              (unsigned char)(h >> 24), (unsigned char)(h >> 16), (unsigned char)(h >> 8), (unsigned char)h, (unsigned char)depth, (unsigned char)(ch == 4 ? 6 : 2), 0, 0, 0};
     put_chunk(out, "IHDR", ihdr, 13);
     put_chunk(out, "IDAT", comp_data, clen);
     put_chunk(out, "IEND", nullptr, 0);
@@ -391,6 +427,37 @@ static bool encode_webp(const std::string& path, int w, int h, const unsigned ch
 #endif
 }
 
+static bool decode_webp_rgba(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgba) {
+#ifdef RIFE_HIP_WITH_WEBP
+    if (d.size() < 12 || memcmp(d.data(), "RIFF", 4) || memcmp(d.data() + 8, "WEBP", 4)) return false;
+    uint8_t* px = WebPDecodeRGBA(d.data(), d.size(), &w, &h);      // a file without alpha comes back opaque
+    if (!px) return false;
+    rgba.assign(px, px + (size_t)w * h * 4);
+    WebPFree(px);
+    return true;
+#else
+    (void)d; (void)w; (void)h; (void)rgba;
+    return false;
+#endif
+}
+
+// lossless, but libwebp's simple API does not keep the colour under fully transparent pixels (its `exact` option is off)
+static bool encode_webp_rgba(const std::string& path, int w, int h, const unsigned char* rgba) {
+#ifdef RIFE_HIP_WITH_WEBP
+    uint8_t* out = nullptr;
+    const size_t n = WebPEncodeLosslessRGBA(rgba, w, h, w * 4, &out);
+    if (!n || !out) return false;
+    FILE* f = fopen(path.c_str(), "wb");
+    const bool ok = f && fwrite(out, 1, n, f) == n;
+    if (f) fclose(f);
+    WebPFree(out);
+    return ok;
+#else
+    (void)path; (void)w; (void)h; (void)rgba;
+    return false;
+#endif
+}
+
 static bool encode_image(const std::string& path, int w, int h, const unsigned char* rgb);
 
 static std::string ext_of(const std::string& p) {
@@ -417,6 +484,34 @@ static bool encode_image(const std::string& path, int w, int h, const unsigned c
     if (e == "webp") return encode_webp(path, w, h, rgb);
     if (e == "jpg" || e == "jpeg") return jpeg::encode(path, w, h, rgb, g_png_helpers);      // same spare cores as the PNG writer
     return encode_png(path, w, h, rgb);
+}
+
+// ---- -a: frames as RGBA (u8 x 4 per pixel; include/rife_hip.h RIFE_HIP_PIX_RGBA8): a file without alpha is read as opaque ----
+static bool decode_image_rgba(const std::string& path, int& w, int& h, std::vector<unsigned char>& rgba) {
+    std::vector<unsigned char> d, rgb, al;
+    if (!read_file(path, d)) return false;
+    if (decode_webp_rgba(d, w, h, rgba)) return true;
+    if (!(decode_png(d, w, h, rgb, nullptr, &al) || decode_ppm(d, w, h, rgb) || decode_bmp(d, w, h, rgb, &al))) {
+        std::string why;
+        al.clear();
+        if (!jpeg::decode(d, w, h, rgb, &why)) {
+            if (d.size() > 2 && d[0] == 0xFF && d[1] == 0xD8) fprintf(stderr, "%s: %s\n", path.c_str(), why.c_str());
+            return false;
+        }
+    }
+    const size_t n = (size_t)w * h;
+    if (rgb.size() != n * 3 || (!al.empty() && al.size() != n)) return false;
+    rgba.resize(n * 4);
+    for (size_t i = 0; i < n; i++) { rgba[4 * i] = rgb[3 * i]; rgba[4 * i + 1] = rgb[3 * i + 1]; rgba[4 * i + 2] = rgb[3 * i + 2]; rgba[4 * i + 3] = al.empty() ? 255 : al[i]; }
+    return true;
+}
+
+// .png: colour type 6, 8 bits; .webp: lossless with alpha; jpg and ppm have no alpha (refused at start-up)
+static bool encode_image_rgba(const std::string& path, int w, int h, const unsigned char* rgba) {
+    const std::string e = ext_of(path);
+    if (e == "webp") return encode_webp_rgba(path, w, h, rgba);
+    if (e == "ppm" || e == "jpg" || e == "jpeg") return false;
+    return encode_png(path, w, h, rgba, 8, 4);
 }
 
 // ---- -b 10: frames as 10-bit codes (u16 x 3 per pixel, 0..1023; include/rife_hip.h RIFE_HIP_PIX_RGB10_U16) ----
@@ -466,10 +561,12 @@ struct SharedFrame {
     int w = 0, h = 0;
     std::vector<unsigned char> px;
     std::vector<uint16_t> px10;                                       // -b 10: the frame as 10-bit codes instead of px
+    bool rgba = false;                                                // -a: px holds four bytes per pixel, R G B A
     const rife_hip_frame* on(const RIFE* r) {
         std::lock_guard<std::mutex> g(mu);
         for (auto& e : resident) if (e.first == r) return e.second;
-        rife_hip_frame* f = px10.empty() ? r->upload(ncnn::Mat(w, h, (void*)px.data(), (size_t)3, 3))
+        rife_hip_frame* f = rgba         ? r->upload(ncnn::Mat(w, h, (void*)px.data(), (size_t)4, 4))      // elemsize 4, elempack 4 = RGBA8 (rife.cpp)
+                            : px10.empty() ? r->upload(ncnn::Mat(w, h, (void*)px.data(), (size_t)3, 3))
                                          : r->upload(ncnn::Mat(w, h, (void*)px10.data(), (size_t)6, 3));      // elemsize 6, elempack 3 = RGB10_U16 (rife.cpp)
         if (f) resident.emplace_back(r, f);
         return f;
@@ -559,6 +656,7 @@ static void print_usage() {
     fprintf(stderr, "  -u                   enable UHD mode\n");
     fprintf(stderr, "  -f pattern-format    output image filename pattern format (%%08d.jpg/png/webp/ppm, default=ext/%%08d.png)\n");
     fprintf(stderr, "  -b bit-depth         bits per sample, 8 or 10 (default=8); 10: rife-v4.6 only, 16-bit png / maxval-1023 ppm output\n");
+    fprintf(stderr, "  -a                   keep the alpha channel (png/webp/32-bit bmp in, png/webp out); rife-v4.6 only, not with -x/-z/-u/-b 10\n");
 }
 
 static bool is_dir(const std::string& p) { struct stat s; return stat(p.c_str(), &s) == 0 && S_ISDIR(s.st_mode); }
@@ -600,6 +698,17 @@ int main(int argc, char** argv) {
         if (!ok) { fprintf(stderr, "encode image %s failed\n", argv[3]); return 1; }
         return 0;
     }
+    // the same with alpha:  rife-hip --transcode -a in.(png|webp|bmp|...) out.(png|webp)
+    if (argc == 5 && std::string(argv[1]) == "--transcode" && std::string(argv[2]) == "-a") {
+        int w = 0, h = 0;
+        std::vector<unsigned char> rgba;
+        g_png_helpers = std::max(0, std::min(15, (int)std::thread::hardware_concurrency() - 1));
+        if (!decode_image_rgba(argv[3], w, h, rgba)) { fprintf(stderr, "decode image %s failed\n", argv[3]); return 1; }
+        const std::string e = ext_of(argv[4]);
+        if (e != "png" && e != "webp") { fprintf(stderr, "RGBA frames are written as png or webp only\n"); return 1; }
+        if (!encode_image_rgba(argv[4], w, h, rgba.data())) { fprintf(stderr, "encode image %s failed\n", argv[4]); return 1; }
+        return 0;
+    }
     // the same for the 10-bit codecs:  rife-hip --transcode10 in.(png|ppm|...) out.(png|ppm)
     if (argc == 4 && std::string(argv[1]) == "--transcode10") {
         int w = 0, h = 0;
@@ -616,10 +725,10 @@ int main(int argc, char** argv) {
     float timestep = 0.5f;
     std::vector<int> gpuid, jobs_proc;
     int jobs_load = 1, jobs_save = 2, bits = 8;
-    bool verbose = false, tta = false, tta_temporal = false, uhd = false;
+    bool verbose = false, tta = false, tta_temporal = false, uhd = false, keep_alpha = false;
 
     int opt;
-    while ((opt = getopt(argc, argv, "0:1:i:o:n:s:m:g:j:f:b:vxzuh")) != -1) {
+    while ((opt = getopt(argc, argv, "0:1:i:o:n:s:m:g:j:f:b:avxzuh")) != -1) {
         switch (opt) {
             case '0': input0 = optarg; break;
             case '1': input1 = optarg; break;
@@ -640,6 +749,7 @@ int main(int argc, char** argv) {
             }
             case 'f': pattern_format = optarg; break;
             case 'b': bits = atoi(optarg); break;
+            case 'a': keep_alpha = true; break;
             case 'v': verbose = true; break;
             case 'x': tta = true; break;
             case 'z': tta_temporal = true; break;
@@ -658,6 +768,11 @@ int main(int argc, char** argv) {
     for (int j : jobs_proc) if (j < 1) { fprintf(stderr, "invalid jobs_proc thread count argument\n"); return -1; }
     if (bits != 8 && bits != 10) { fprintf(stderr, "invalid bit depth argument, must be 8 or 10\n"); return -1; }
     const bool deep = bits == 10;
+    if (keep_alpha && deep) { fprintf(stderr, "alpha (-a) is served at depth 8 only, not with -b 10 (A2B10G10R10 has two alpha bits)\n"); return -1; }
+    if (keep_alpha && (tta || tta_temporal || uhd)) {
+        fprintf(stderr, "alpha (-a) is served in plain mode only, not with %s\n", tta ? "-x (TTA mode)" : tta_temporal ? "-z (temporal TTA mode)" : "-u (UHD mode)");
+        return -1;
+    }
 
     std::string pattern = pattern_format, format;
     {
@@ -676,6 +791,7 @@ int main(int argc, char** argv) {
     }
     if (format != "png" && format != "ppm" && format != "webp" && format != "jpg") { fprintf(stderr, "invalid format argument\n"); return -1; }
     if (deep && format != "png" && format != "ppm") { fprintf(stderr, "10-bit frames (-b 10) are written as png (16-bit) or ppm (maxval 1023) only, not %s\n", format.c_str()); return -1; }
+    if (keep_alpha && format != "png" && format != "webp") { fprintf(stderr, "RGBA frames (-a) are written as png or webp only, %s has no alpha\n", format.c_str()); return -1; }
 #ifndef RIFE_HIP_WITH_WEBP
     if (format == "webp") { fprintf(stderr, "this rife-hip was built without libwebp\n"); return -1; }
 #endif
@@ -684,6 +800,7 @@ int main(int argc, char** argv) {
     if (model.find("rife-v2") != std::string::npos || model.find("rife-v3") != std::string::npos) rife_v2 = true;
     else if (model.find("rife-v4") != std::string::npos) rife_v4 = true;
     else if (model.find("rife") == std::string::npos) { fprintf(stderr, "unknown model dir type\n"); return -1; }
+    if (keep_alpha && !rife_v4) { fprintf(stderr, "alpha (-a) is served for model family rife-v4.6 only, not for %s\n", model.c_str()); return -1; }
     if (!rife_v4 && (numframe != 0 || timestep != 0.5f)) { fprintf(stderr, "only rife-v4 model support custom numframe and timestep\n"); return -1; }
 
     // ---- task list (src/main.cpp:692-766) ----
@@ -742,6 +859,12 @@ int main(int argc, char** argv) {
             if (!f) { fprintf(stderr, "-b 10 is not available: %s\n", rife_hip_last_error()); return -1; }
             RIFE::release(f);
         }
+        if (keep_alpha) {      // likewise: rife-v4 (4.0) shares the directory prefix and is told apart by the engine
+            unsigned char one[4] = {0, 0, 0, 0};
+            rife_hip_frame* f = r->upload(ncnn::Mat(1, 1, (void*)one, (size_t)4, 4));
+            if (!f) { fprintf(stderr, "-a is not available: %s\n", rife_hip_last_error()); return -1; }
+            RIFE::release(f);
+        }
         rife.push_back(r);
     }
 
@@ -757,7 +880,10 @@ int main(int argc, char** argv) {
             { std::lock_guard<std::mutex> g(next_mu); if (next_task >= tasks.size()) return; k = next_task++; }
             Task t = std::move(tasks[k]);
             FrameCache::Frame f0, f1;
-            auto decode = [&](const std::string& p, SharedFrame& fr) { return deep ? decode_image10(p, fr.w, fr.h, fr.px10) : decode_image(p, fr.w, fr.h, fr.px); };
+            auto decode = [&](const std::string& p, SharedFrame& fr) {
+                fr.rgba = keep_alpha;
+                return deep ? decode_image10(p, fr.w, fr.h, fr.px10) : keep_alpha ? decode_image_rgba(p, fr.w, fr.h, fr.px) : decode_image(p, fr.w, fr.h, fr.px);
+            };
             if (!cache.get(t.in0path, f0, decode) || !cache.get(t.in1path, f1, decode)) { fprintf(stderr, "decode image %s or %s failed\n", t.in0path.c_str(), t.in1path.c_str()); continue; }
             if (f1->w != f0->w || f1->h != f0->h) { fprintf(stderr, "%s and %s differ in size\n", t.in0path.c_str(), t.in1path.c_str()); continue; }
             t.w = f0->w; t.h = f0->h; t.fr0 = f0; t.fr1 = f1;
@@ -784,8 +910,9 @@ int main(int argc, char** argv) {
             } else {
                 const rife_hip_frame* d0 = t.fr0->on(r);
                 const rife_hip_frame* d1 = t.fr1->on(r);
-                t.out.resize((size_t)t.w * t.h * 3);
-                ncnn::Mat out(t.w, t.h, (void*)t.out.data(), (size_t)3, 3);
+                const int nch = keep_alpha ? 4 : 3;
+                t.out.resize((size_t)t.w * t.h * nch);
+                ncnn::Mat out(t.w, t.h, (void*)t.out.data(), (size_t)nch, nch);
                 if (!d0 || !d1 || r->process(d0, d1, t.timestep, out) != 0) { fprintf(stderr, "process %s failed: %s\n", t.outpath.c_str(), rife_hip_last_error()); continue; }
             }
             t.fr0.reset(); t.fr1.reset();                                      // the save stage needs only the output
@@ -796,7 +923,8 @@ int main(int argc, char** argv) {
         for (;;) {
             Task t = tosave.get();
             if (t.id == -233) return;
-            const bool ok = deep ? encode_image10(t.outpath, t.w, t.h, t.out10.data()) : encode_image(t.outpath, t.w, t.h, t.out.data());
+            const bool ok = deep ? encode_image10(t.outpath, t.w, t.h, t.out10.data()) : keep_alpha ? encode_image_rgba(t.outpath, t.w, t.h, t.out.data())
+                                                                                              : encode_image(t.outpath, t.w, t.h, t.out.data());
             if (!ok) fprintf(stderr, "encode image %s failed\n", t.outpath.c_str());
             else if (verbose) fprintf(stderr, "%s %s %f -> %s done\n", t.in0path.c_str(), t.in1path.c_str(), t.timestep, t.outpath.c_str());
         }

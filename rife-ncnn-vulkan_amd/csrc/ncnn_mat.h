@@ -2,6 +2,8 @@
 // (reference src/main.cpp:187 `ncnn::Mat(w, h, (void*)pixeldata, (size_t)3, 3)` wraps caller-owned pixels,
 //  src/main.cpp:332 `ncnn::Mat(w, h, (size_t)3, 3)` allocates the output; src/rife.cpp:407-411, 2482-2486 read
 //  `.data/.w/.h`; rife.cpp:2470-2480 assigns one Mat to another, sharing the buffer).
+// elemsize / elempack also say what a pixel is at this boundary (csrc/rife.cpp mat_pixfmt): 3, 3 = u8 RGB as above; 6, 3 = three u16 codes 0..1023 (10-bit);
+// 4, 4 = u8 RGBA, alpha carried through (include/rife_hip.h RIFE_HIP_PIX_RGBA8).
 // Real ncnn is an un-vendored submodule of the reference, so a build against this engine uses this header; a build
 // inside the reference tree keeps using ncnn's own Mat — the field names and semantics match.
 #pragma once

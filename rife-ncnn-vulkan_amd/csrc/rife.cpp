@@ -8,10 +8,12 @@
 
 #include "../../include/rife_hip.h"
 
-// the pixel format of a Mat at this boundary: elemsize 6, elempack 3 = three u16 codes 0..1023 per pixel (RIFE_HIP_PIX_RGB10_U16); every other Mat is the
+// the pixel format of a Mat at this boundary: elemsize 6, elempack 3 = three u16 codes 0..1023 per pixel (RIFE_HIP_PIX_RGB10_U16); elemsize 4, elempack 4 =
+// u8 RGBA (RIFE_HIP_PIX_RGBA8); every other Mat is the
 // 8-bit RGB Mat the reference builds (src/main.cpp:187, 332)
 static int mat_pixfmt(const ncnn::Mat& m)
 {
+    if (m.elemsize == 4 && m.elempack == 4) return RIFE_HIP_PIX_RGBA8;      // four u8 per pixel, R G B A: alpha is carried through
     return (m.elemsize == 6 && m.elempack == 3) ? RIFE_HIP_PIX_RGB10_U16 : RIFE_HIP_PIX_RGB8;
 }
 
@@ -42,7 +44,7 @@ int RIFE::process(const ncnn::Mat& in0image, const ncnn::Mat& in1image, float ti
     const int pixfmt = mat_pixfmt(in0image);
     if (pixfmt != mat_pixfmt(in1image) || (outimage.data && mat_pixfmt(outimage) != pixfmt))
     {
-        fprintf(stderr, "RIFE::process: the three images differ in pixel format (8-bit and 10-bit Mats mixed)\n");
+        fprintf(stderr, "RIFE::process: the three images differ in pixel format (8-bit RGB, RGBA and 10-bit Mats mixed)\n");
         return -RIFE_HIP_EINVAL;
     }
 

@@ -70,7 +70,8 @@ __device__ __forceinline__ void trs_put_px10(uint8_t* base, unsigned i, uint32_t
     else { trs_put_short(base, i * 6u, pk & 0x3ffu); trs_put_short(base, i * 6u + 2u, (pk >> 10) & 0x3ffu); trs_put_short(base, i * 6u + 4u, (pk >> 20) & 0x3ffu); }
 }
 
-// PX (include/rife_hip.h RIFE_HIP_PIX_*): 0 = u8 frames; 1 / 2 = 10:10:10 frames in, RGB10_U16 / A2B10G10R10 out (k_final_px<PX>'s arithmetic)
+// PX (include/rife_hip.h RIFE_HIP_PIX_*): 0 = u8 frames; 1 / 2 = 10:10:10 frames in, RGB10_U16 / A2B10G10R10 out (k_final_px<PX>'s arithmetic);
+// 4 = RGBA8: depth-8 frames with alpha in byte 3, finished from the taps already loaded (warp_finish_a) and stored as one aligned dword per lane
 template <int TAG, int PX = 0>
 __global__ __launch_bounds__(TRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))) void tail_rs_kernel(TailRsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
@@ -245,10 +246,15 @@ __global__ __launch_bounds__(TRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
             const bool valid = ox < a.w_ && (!RIFE_ABL(TAG & TRS_NOSTORE) || mm == 123.456f);
             const float m = 1.f / (1.f + expf(-mm));
             const float rm = 1.0f - m;
-            const float3 w1 = warp_finish<PX ? 10 : 8>(tb);
-            const float3 w0 = warp_finish<PX ? 10 : 8>(ta);
+            const float3 w1 = warp_finish<px_depth(PX)>(tb);
+            const float3 w0 = warp_finish<px_depth(PX)>(ta);
             const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
-            if (PX) { if (valid) trs_put_px10<PX>(a.out, (unsigned)(oy * a.w_ + ox), quant10(r, g, b)); return; }
+            if (px_deep(PX)) { if (valid) trs_put_px10<PX>(a.out, (unsigned)(oy * a.w_ + ox), quant10(r, g, b)); return; }
+            if (PX == 4) {
+                const float al = warp_finish_a(ta) * m + warp_finish_a(tb) * rm;
+                if (valid) trs_store_dword(a.out, (unsigned)(oy * a.w_ + ox) * 4u, quant8(r) | (quant8(g) << 8) | (quant8(b) << 16) | (quant8(al) << 24));
+                return;
+            }
             const uint32_t pk = (uint32_t)min(max((int)(r * 255.f + 0.5f), 0), 255) | ((uint32_t)min(max((int)(g * 255.f + 0.5f), 0), 255) << 8) |
                                 ((uint32_t)min(max((int)(b * 255.f + 0.5f), 0), 255) << 16);
             const unsigned orow = (unsigned)(oy * a.w_ + oxb) * 3u;     // byte offset of the segment (frames stay below 4 GB)
@@ -288,10 +294,15 @@ __global__ __launch_bounds__(TRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
             const bool valid = ox < a.w_;
             const float m = 1.f / (1.f + expf(-mm_prev));
             const float rm = 1.0f - m;
-            const float3 w1 = warp_finish<PX ? 10 : 8>(wb);
-            const float3 w0 = warp_finish<PX ? 10 : 8>(wa);
+            const float3 w1 = warp_finish<px_depth(PX)>(wb);
+            const float3 w0 = warp_finish<px_depth(PX)>(wa);
             const float r = w0.x * m + w1.x * rm, g = w0.y * m + w1.y * rm, b = w0.z * m + w1.z * rm;
-            if (PX) { if (valid) trs_put_px10<PX>(a.out, (unsigned)(oy * a.w_ + ox), quant10(r, g, b)); return; }
+            if (px_deep(PX)) { if (valid) trs_put_px10<PX>(a.out, (unsigned)(oy * a.w_ + ox), quant10(r, g, b)); return; }
+            if (PX == 4) {
+                const float al = warp_finish_a(wa) * m + warp_finish_a(wb) * rm;
+                if (valid) trs_store_dword(a.out, (unsigned)(oy * a.w_ + ox) * 4u, quant8(r) | (quant8(g) << 8) | (quant8(b) << 16) | (quant8(al) << 24));
+                return;
+            }
             const uint32_t pk = (uint32_t)min(max((int)(r * 255.f + 0.5f), 0), 255) | ((uint32_t)min(max((int)(g * 255.f + 0.5f), 0), 255) << 8) |
                                 ((uint32_t)min(max((int)(b * 255.f + 0.5f), 0), 255) << 16);
             const unsigned orow = (unsigned)(oy * a.w_ + oxb) * 3u;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # ASan + UBSan and TSan job for the HOST side (csrc/main.cpp, rife.cpp, jpeg_codec.h, the PNG band writer); no GPU needed: the engine behind the C-ABI is
-# tests/sanitize/stub_engine.cpp.  Writes a log to stdout; exit code != 0 if any sanitizer reported.
+# tests/sanitize/stub_engine.cpp (+ stub_engine_deep.cpp / stub_engine_alpha.cpp for the 10-bit and RGBA entry points).  Writes a log to stdout; exit code != 0 if any sanitizer reported.
 #   tools/sanitize_run.sh > profiles/r5/sanitize.txt
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -19,6 +19,9 @@ RIFE_HIP_BIN=$ASAN python -m pytest tests/test_cli.py -q -m "not gpu" -k "cpp_cl
 [ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
 echo "== 1b. the 10-bit codecs (--transcode10: 16-bit png, ppm with maxval 1023 / 65535, truncated and crafted files) of tests/test_cli_deep.py through the same binary"
 RIFE_HIP_BIN=$ASAN python -m pytest tests/test_cli_deep.py -q -m "not gpu" -k "cpp_cli" 2>&1 | tail -4
+[ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
+echo "== 1c. the RGBA codecs (--transcode -a: png colour types 4 / 6, tRNS, 16-bit, webp, 32-bit bmp, truncated and crafted files) of tests/test_cli_alpha.py through the same binary"
+RIFE_HIP_BIN=$ASAN python -m pytest tests/test_cli_alpha.py -q -m "not gpu" -k "cpp_cli" 2>&1 | tail -4
 [ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
 T=$(mktemp -d)
 python - $T <<'PY'
@@ -94,6 +97,31 @@ for fmt in png ppm; do
     rm -rf $T/out; mkdir -p $T/out
     run "tsan -b 10 $fmt -g 0,0 -j 2:1,2:3" $TSAN -i $T/in_deep -o $T/out -m rife-v4.6 -n 13 -b 10 -f %08d.$fmt -g 0,0 -j 2:1,2:3
 done
+echo "== 3c. -a (RGBA png in, RGBA png / webp out; four-byte frames through upload_px / process_frames of the stub) under both"
+python - $T <<'PY'
+import sys, os
+sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+from PIL import Image
+import alpha_ref
+t = sys.argv[1]
+os.makedirs(os.path.join(t, "in_alpha"))
+for i in range(5):
+    Image.fromarray(alpha_ref.rgba_pair(333, 241, 80 + i, "smooth")[i & 1], "RGBA").save(os.path.join(t, "in_alpha", "%03d.png" % i))
+PY
+for fmt in png webp; do
+    rm -rf $T/out; mkdir -p $T/out
+    run "asan -a $fmt -g 0,1 -j 3:2,3:4" $ASAN -i $T/in_alpha -o $T/out -m rife-v4.6 -n 13 -a -f %08d.$fmt -g 0,1 -j 3:2,3:4
+    rm -rf $T/out; mkdir -p $T/out
+    run "tsan -a $fmt -g 0,0 -j 2:1,2:3" $TSAN -i $T/in_alpha -o $T/out -m rife-v4.6 -n 13 -a -f %08d.$fmt -g 0,0 -j 2:1,2:3
+done
+python - $T <<'PY'
+import sys, os, numpy as np
+from PIL import Image
+t = sys.argv[1]
+names = sorted(os.listdir(os.path.join(t, "out")))
+im = Image.open(os.path.join(t, "out", names[0]))
+print("   -a output is RGBA:", im.mode == "RGBA", im.size)
+PY
 echo "== 4. single-pair mode, error paths (missing file, size mismatch, bad extension) under ASan + UBSan"
 rm -rf $T/out; mkdir -p $T/out
 run "asan pair" $ASAN -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/o.png -m rife-v4.6 -s 0.3
