@@ -130,7 +130,41 @@ void rife_hip_frame_release(rife_hip_frame_t* frame);
  *   transparent pixels).
  * Out of scope: alpha at depth 10 (A2B10G10R10 has two alpha bits), other families and modes, rife_hip_process_batch (the host batch). */
 
-size_t rife_hip_frame_bytes(int w, int h, int pixfmt);      /* 0 for an unknown format or w, h <= 0 */
+/* ---- video: 4:2:0 Y'CbCr frames in and out (absent in the reference, whose frames are RGB stills) ---------------------------------------------------------
+ * What decoders, `ffmpeg -f yuv4mpegpipe`, VapourSynth / AviSynth clips and hardware surfaces deliver: 1.5 bytes per pixel (3 at 10 bits) instead of 3 (6).
+ * cw = (w + 1) / 2, ch = (h + 1) / 2; planes tightly packed, one after the other; odd sizes are served.
+ * 5 .. 15 are reserved (unknown formats today, like 3): the 4:2:0 formats are 16 + 2 * (10 bits) + (planar). */
+#define RIFE_HIP_PIX_NV12         16  /* u8: Y plane w*h, then one plane of interleaved Cb, Cr pairs, cw*ch*2 */
+#define RIFE_HIP_PIX_I420         17  /* u8: planes Y w*h, Cb cw*ch, Cr cw*ch (what Y4M C420* holds) */
+#define RIFE_HIP_PIX_P010         18  /* u16 little-endian, the code in the HIGH 10 bits, NV12 plane layout; low bits ignored on input, written as zero */
+#define RIFE_HIP_PIX_I420P10      19  /* u16 little-endian, the code in the LOW 10 bits, I420 plane layout (what Y4M C420p10 holds); a larger value is read as 1023 */
+/* The colour description is OR-ed into pixfmt (4:2:0 formats only; on an RGB format any of these bits is -RIFE_HIP_EINVAL):
+ * bits 8-11 the matrix (an unknown one: -RIFE_HIP_EINVAL), bit 12 the range (limited is the default). */
+#define RIFE_HIP_CSP_BT709        (0 << 8)   /* the default */
+#define RIFE_HIP_CSP_BT601        (1 << 8)
+#define RIFE_HIP_CSP_BT2020NCL    (2 << 8)
+#define RIFE_HIP_CSP_FULL         (1 << 12)  /* full range ("JPEG" levels); 8-bit formats only: with a 10-bit format -RIFE_HIP_EINVAL (its round trip below is not exact) */
+/* A 4:2:0 call is, byte for byte, the A2B10G10R10 call on the converted frames, converted back:
+ *     out = rgb10_to_yuv(process_px(yuv_to_rgb10(in0), yuv_to_rgb10(in1), timestep, A2B10G10R10))
+ * with INTEGER conversions (tests/yuv_ref.py states them in numpy, csrc/yuv.h in HIP; the two agree bit for bit):
+ *   coefficients  the matrix's real coefficients times 1023 / range (in) or range / 1023 (out), rounded to Q16; range = 219 s luma, 224 s chroma (limited),
+ *                 255 both (full); s = 1 at 8 bits, 4 at 10.  Products are summed in integers, + 0x8000, arithmetic shift right by 16.
+ *   in            subtract the offsets (16 s and 128 s; full range 0 and 128 s), apply the matrix, clamp to 0..1023.  The chroma of a pixel is the sample of
+ *                 its 2x2 block (replication).  The padding to 32n is zero RGB, as everywhere.
+ *   out           Y per pixel; Cb, Cr from the SUM of the RGB codes of the block's pixels inside the frame (n = 4, 2 or 1), shifted by 16 + log2 n with the
+ *                 rounding constant scaled alike; add the offsets, clamp to 0..255 / 0..1023.
+ * YUV -> 10-bit RGB -> YUV is the identity on every sample whose RGB did not clamp, at both depths (half a code of RGB error weighs less than half a code of
+ * any output), which is why 8- AND 10-bit video ride the engine's depth-10 path unchanged, and a difference of one RGB code moves no Y, Cb, Cr by more than
+ * one code, which carries the engine's 1-code contract across.
+ * Chroma siting: replication up and the box average down are each other's inverse on block-constant chroma and have no net shift whatever the stream's
+ * siting is; chroma siting tags (Y4M C420jpeg / C420mpeg2 / C420paldv) are ignored.
+ * timestep 0 / 1 return the first / second frame's samples (P010: low bits cleared; I420P10: clamped to 1023).  Input and output of a call share one format and
+ * one colour description; rife_hip_process_frames refuses two frames that differ in either.
+ * Scope: that of the 10-bit formats - model family rife-v4.6, plain mode, every frame size; any other family or mode returns -RIFE_HIP_ENOSYS with a message
+ * that names it, before anything is written; the opt-in graph replay does not apply.  Out of scope: rife_hip_process_batch (the host batch), 4:2:2 / 4:4:4,
+ * interlaced chroma. */
+
+size_t rife_hip_frame_bytes(int w, int h, int pixfmt);      /* 0 for an unknown format or w, h <= 0; 4:2:0: (w*h + 2*cw*ch) samples; colour bits are ignored */
 int rife_hip_process_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt);
 int rife_hip_process_device_px(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt,
                                void* hip_stream);

@@ -51,6 +51,11 @@ int rife_hip_op_deconv4x4(int gpuid, const float* x_chw, int c, int h, int w, co
 /* rife.Warp (src/warp.cpp:96-168): image c x h x w, flow 2 x h x w. */
 int rife_hip_op_warp(int gpuid, const float* image_chw, const float* flow_chw, int c, int h, int w, float* out_chw);
 
+/* The two 4:2:0 kernels alone (csrc/yuv.h; pixfmt = a RIFE_HIP_PIX_NV12 .. I420P10 format with its colour description): k_preproc_yuv on one host frame ->
+ * the resident form, hp x wp dwords R | G << 10 | B << 20, zero outside w x h; k_postproc_yuv on h x w A2B10G10R10 dwords -> one frame of `pixfmt`. */
+int rife_hip_op_yuv_to_rgb10(int gpuid, const void* yuv, int w, int h, int pixfmt, uint32_t* out_padded);
+int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int h, int pixfmt, void* yuv_out);
+
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */
 int rife_hip_pool_state(const rife_hip_t* r, int* pooled, int* leased, int* high_water);

@@ -36,9 +36,13 @@ C_ABI_SYMBOLS = [
 # pixel formats at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*)
 PIX_RGB8, PIX_RGB10_U16, PIX_A2B10G10R10 = 0, 1, 2
 PIX_RGBA8 = 4      # 3 is reserved
+# 4:2:0 Y'CbCr (flat arrays: uint8 for NV12 / I420, uint16 for P010 / I420P10); the colour description is OR-ed into the format
+PIX_NV12, PIX_I420, PIX_P010, PIX_I420P10 = 16, 17, 18, 19      # 5 .. 15 are reserved
+CSP_BT709, CSP_BT601, CSP_BT2020NCL = 0 << 8, 1 << 8, 2 << 8
+CSP_FULL = 1 << 12
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
-                    "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px"]
+                    "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv"]
 
 
 def build(force=False):
@@ -103,6 +107,8 @@ def _load(path, with_test_surface):
         L.rife_hip_pool_state.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
         L.rife_hip_v4_extract_flow_px.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp, ci]
         L.rife_hip_v4_tap_px.argtypes = [vp, vp, vp, ci, ci, cf, ci, ci, vp, ci, vp, ci]
+        L.rife_hip_op_yuv_to_rgb10.argtypes = [ci, vp, ci, ci, ci, vp]
+        L.rife_hip_op_rgb10_to_yuv.argtypes = [ci, vp, ci, ci, ci, vp]
     return L
 
 
@@ -210,6 +216,30 @@ def frame_bytes(w, h, pixfmt=PIX_RGB8):
     return int(lib().rife_hip_frame_bytes(int(w), int(h), int(pixfmt)))
 
 
+def _yuv_base(pixfmt):
+    b = int(pixfmt) & 0xff
+    if int(pixfmt) < 0 or b not in (PIX_NV12, PIX_I420, PIX_P010, PIX_I420P10):
+        raise ValueError("%r is not a 4:2:0 YUV pixfmt" % (pixfmt,))
+    return b
+
+
+def yuv_dtype(pixfmt):
+    return np.uint16 if _yuv_base(pixfmt) in (PIX_P010, PIX_I420P10) else np.uint8
+
+
+def yuv_frame_bytes(w, h, pixfmt):
+    """Size of one w x h 4:2:0 frame: (w * h + 2 * cw * ch) samples of 1 or 2 bytes, cw = (w + 1) // 2, ch = (h + 1) // 2."""
+    return (w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)) * np.dtype(yuv_dtype(pixfmt)).itemsize
+
+
+def _yuv_buf(buf, w, h, pixfmt, what):
+    dt = yuv_dtype(pixfmt)
+    n = yuv_frame_bytes(w, h, pixfmt) // np.dtype(dt).itemsize
+    if w <= 0 or h <= 0 or not isinstance(buf, np.ndarray) or buf.dtype != dt or buf.size != n or not buf.flags.c_contiguous:
+        raise ValueError("%s must be a contiguous %s array of %d samples (a %dx%d frame)" % (what, np.dtype(dt).name, n, w, h))
+    return buf
+
+
 _PIX_LAYOUT = {PIX_RGB8: (np.uint8, 3), PIX_RGB10_U16: (np.uint16, 3), PIX_A2B10G10R10: (np.uint32, 2), PIX_RGBA8: (np.uint8, 3)}      # dtype, ndim
 _PIX_NAME = {PIX_RGB10_U16: "RGB10_U16", PIX_A2B10G10R10: "A2B10G10R10", PIX_RGBA8: "RGBA8"}
 
@@ -306,6 +336,23 @@ class RIFE:
         _check(self._L.rife_hip_process(self._h, _p(a), _p(b), w, h, float(timestep), _p(out)), "process", self._L)
         return out
 
+    def process_yuv(self, buf0, buf1, w, h, timestep, pixfmt, out=None):
+        """4:2:0 frames in and out (rife-v4.6, plain mode): flat uint8 (NV12, I420) or uint16 (P010, I420P10) arrays of yuv_frame_bytes(w, h, pixfmt) bytes;
+        pixfmt = PIX_NV12 .. PIX_I420P10, OR-ed with CSP_BT709 / CSP_BT601 / CSP_BT2020NCL and CSP_FULL.  The result has the inputs' format."""
+        a = _yuv_buf(buf0, w, h, pixfmt, "buf0"); b = _yuv_buf(buf1, w, h, pixfmt, "buf1")
+        o = _yuv_buf(out if out is not None else np.empty_like(a), w, h, pixfmt, "out")
+        if not o.flags.writeable:
+            raise ValueError("out must be writable")
+        _check(self._L.rife_hip_process_px(self._h, _p(a), _p(b), int(w), int(h), float(timestep), _p(o), int(pixfmt)), "process_px", self._L)
+        return o
+
+    def upload_yuv(self, buf, w, h, pixfmt):
+        """Stream mode for 4:2:0 frames: the frame stays in device memory in its own format and is converted at each use; process_frames() returns a flat array."""
+        a = _yuv_buf(buf, w, h, pixfmt, "buf")
+        f = ctypes.c_void_p()
+        _check(self._L.rife_hip_frame_upload_px(self._h, _p(a), int(w), int(h), int(pixfmt), ctypes.byref(f)), "frame_upload_px", self._L)
+        return Frame(f, int(w), int(h), self._L, int(pixfmt))
+
     def upload(self, image, pixfmt=None):
         """Stream mode: copy one (h, w, 3) uint8 frame to the device and keep it there (deep colour: a uint16 (h, w, 3) or uint32 (h, w)
         array, see process())."""
@@ -329,8 +376,12 @@ class RIFE:
         if frame0.pixfmt != frame1.pixfmt:
             raise ValueError("the two frames differ in pixel format")
         if frame0.pixfmt != PIX_RGB8:      # the result has the format the frames were uploaded in
-            dt, nd = _PIX_LAYOUT[frame0.pixfmt]
-            shape = _pix_shape(frame0.pixfmt, frame0.h, frame0.w)
+            if (frame0.pixfmt & 0xff) >= PIX_NV12:
+                dt = yuv_dtype(frame0.pixfmt)
+                shape = (yuv_frame_bytes(frame0.w, frame0.h, frame0.pixfmt) // np.dtype(dt).itemsize,)
+            else:
+                dt, nd = _PIX_LAYOUT[frame0.pixfmt]
+                shape = _pix_shape(frame0.pixfmt, frame0.h, frame0.w)
             out = outimage if outimage is not None else np.empty(shape, dt)
             if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dt or not out.flags.c_contiguous or not out.flags.writeable:
                 raise ValueError("outimage must be a writable contiguous array of the frames' format and size")
@@ -345,7 +396,7 @@ class RIFE:
     def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
         """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
         if pixfmt not in _PIX_LAYOUT:
-            raise ValueError("unknown pixfmt %r" % (pixfmt,))
+            _yuv_base(pixfmt)
         if pixfmt != PIX_RGB8:
             _check(self._L.rife_hip_process_device_px(self._h, d_in0, d_in1, w, h, float(timestep), d_out, pixfmt, stream), "process_device_px", self._L)
             return
@@ -363,7 +414,7 @@ class RIFE:
     def process_device_batch(self, d_in0, d_in1, w, h, timesteps, d_out, stream=None, pixfmt=PIX_RGB8):
         """n resident pairs in one call (rife_hip_process_device_batch): lists of device pointers; enqueued relative to `stream`."""
         if pixfmt not in _PIX_LAYOUT:
-            raise ValueError("unknown pixfmt %r" % (pixfmt,))
+            _yuv_base(pixfmt)
         n = len(d_in0)
         if len(d_in1) != n or len(d_out) != n or len(timesteps) != n:
             raise ValueError("one in1 / out / timestep per pair")
@@ -503,4 +554,23 @@ def op_warp(image, flow, gpuid=0):
     c, h, w = image.shape
     out = np.empty_like(image)
     _check(testlib().rife_hip_op_warp(gpuid, _p(image), _p(flow), c, h, w, _p(out)), "op_warp", testlib())
+    return out
+
+
+def op_yuv_to_rgb10(buf, w, h, pixfmt, gpuid=0):
+    """k_preproc_yuv alone: one flat 4:2:0 frame -> the resident form, (hp, wp) uint32 R | G << 10 | B << 20 with zero padding (hp, wp = h, w rounded up to 32n)."""
+    a = _yuv_buf(buf, w, h, pixfmt, "buf")
+    out = np.empty(((h + 31) // 32 * 32, (w + 31) // 32 * 32), np.uint32)
+    _check(testlib().rife_hip_op_yuv_to_rgb10(gpuid, _p(a), int(w), int(h), int(pixfmt), _p(out)), "op_yuv_to_rgb10", testlib())
+    return out
+
+
+def op_rgb10_to_yuv(packed, pixfmt, gpuid=0):
+    """k_postproc_yuv alone: an (h, w) uint32 A2B10G10R10 frame -> one flat 4:2:0 frame of `pixfmt`."""
+    a = np.ascontiguousarray(packed, np.uint32)
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError("packed must be an (h, w) uint32 array")
+    h, w = a.shape
+    out = np.empty(yuv_frame_bytes(w, h, pixfmt) // np.dtype(yuv_dtype(pixfmt)).itemsize, yuv_dtype(pixfmt))
+    _check(testlib().rife_hip_op_rgb10_to_yuv(gpuid, _p(a), w, h, int(pixfmt), _p(out)), "op_rgb10_to_yuv", testlib())
     return out

@@ -37,6 +37,7 @@
 #include "conv_mfma.h"
 #include "conv_img.h"
 #include "elementwise.h"
+#include "yuv.h"
 #include "elementwise_v2.h"
 #include "stem_fused.h"
 #include "stem_fused_v2.h"

@@ -156,11 +156,22 @@ static int pixfmt_supported(const rife_hip* E, int pixfmt) {
     const char* what = E->v1 ? "model family rife (v1: rife, rife-HD, rife-UHD, rife-anime)" : (!E->v4 && E->v3) ? "model family rife-v3.x" : !E->v4 ? "model family rife-v2.x"
                        : E->v40 ? "model family rife-v4 (4.0)" : E->tta ? "TTA mode (-x)" : E->tta_temporal ? "temporal TTA mode (-z)" : E->uhd ? "UHD mode (-u)" : nullptr;
     if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
+    return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : pix_yuv(pixfmt) ? "4:2:0 YUV" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
 }
 // argument checks of the _px entry points that need no engine; then "no HIP device at all" before anything looks at the engine
+// a pixfmt argument = format | colour description (include/rife_hip.h RIFE_HIP_CSP_*): both must be something the library knows
+static int pixfmt_check(int pixfmt) {
+    const int csp = pixfmt & ~0xff;
+    if (pixfmt < 0 || frame_bytes(1, 1, pix_base(pixfmt)) == 0 || (csp & ~0x1f00)) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
+    if (!pix_yuv(pixfmt)) return csp ? fail(RIFE_HIP_EINVAL, "a colour description (RIFE_HIP_CSP_*) goes with a 4:2:0 YUV format, not with an RGB format") : 0;
+    if (((csp >> 8) & 15) > 2) return fail(RIFE_HIP_EINVAL, "unknown colour matrix");
+    if ((csp & RIFE_HIP_CSP_FULL) && yuv_depth(pix_base(pixfmt)) == 10)
+        return fail(RIFE_HIP_EINVAL, "full-range YUV is served at 8 bits only (the 10-bit full-range round trip through 10-bit RGB is not exact)");
+    return 0;
+}
 static int px_precheck(int pixfmt, bool ptrs_ok, int w, int h) {
-    if (pix_bpp(pixfmt) == 0) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
+    int rc;
+    if ((rc = pixfmt_check(pixfmt))) return rc;
     if (!ptrs_ok) return fail(RIFE_HIP_EINVAL, "null pointer argument");
     if (w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "bad frame size");
     int n = 0;
@@ -168,7 +179,17 @@ static int px_precheck(int pixfmt, bool ptrs_ok, int w, int h) {
     return 0;
 }
 // timestep 0 / 1 at depth 10: the input frame in canonical form (samples clamped to 1023, alpha bits 3) - what a pass over identical frames would write
-static void canon10_host(void* out, const void* in, size_t npix, int pixfmt) {
+// (4:2:0: the samples' codes - P010 low bits cleared, I420P10 samples clamped to 1023, 8-bit frames unchanged)
+static void canon10_host(void* out, const void* in, int w, int h, int pixfmt) {
+    const size_t npix = (size_t)w * h;
+    if (pix_yuv(pixfmt)) {
+        const size_t nbytes = frame_bytes(w, h, pixfmt);
+        if (yuv_depth(pix_base(pixfmt)) == 8) { std::memmove(out, in, nbytes); return; }
+        const bool p010 = pix_base(pixfmt) == RIFE_HIP_PIX_P010;
+        const uint16_t* s = static_cast<const uint16_t*>(in); uint16_t* d = static_cast<uint16_t*>(out);
+        for (size_t i = 0; i < nbytes / 2; i++) d[i] = p010 ? (uint16_t)(s[i] & 0xffc0u) : std::min<uint16_t>(s[i], 1023);
+        return;
+    }
     if (pixfmt == RIFE_HIP_PIX_RGB10_U16) {
         const uint16_t* s = static_cast<const uint16_t*>(in); uint16_t* d = static_cast<uint16_t*>(out);
         for (size_t i = 0; i < npix * 3; i++) d[i] = std::min<uint16_t>(s[i], 1023);
@@ -183,7 +204,12 @@ static int copy_frame_device(hipStream_t st, const void* src, void* dst, int w, 
         hipLaunchKernelGGL(k_canon10_u16, dim3((unsigned)((npix * 3 + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), npix * 3);
     else if (pixfmt == RIFE_HIP_PIX_A2B10G10R10)
         hipLaunchKernelGGL(k_canon10_packed, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), npix);
-    else { HIPCHK(hipMemcpyAsync(dst, src, npix * pix_bpp(pixfmt), hipMemcpyDeviceToDevice, st)); return 0; }      // RGB8, RGBA8: the bytes unchanged
+    else if (pix_yuv(pixfmt) && yuv_depth(pix_base(pixfmt)) == 10) {
+        const size_t n = frame_bytes(w, h, pixfmt) / 2;
+        if (pix_base(pixfmt) == RIFE_HIP_PIX_P010) hipLaunchKernelGGL(k_canon_yuv10<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), n);
+        else hipLaunchKernelGGL(k_canon_yuv10<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), n);
+    }
+    else { HIPCHK(hipMemcpyAsync(dst, src, frame_bytes(w, h, pixfmt), hipMemcpyDeviceToDevice, st)); return 0; }      // RGB8, RGBA8, NV12, I420: the bytes unchanged
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -275,7 +301,7 @@ static void release_ctx(const rife_hip* E, std::unique_ptr<Ctx>& c) {
 
 // H2D of both frames, the whole pass and the D2H of the result, all enqueued on the workspace's stream (no host wait)
 static int enqueue_host_pair(const rife_hip* E, Ctx& c, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out) {
-    const size_t nbytes = (size_t)w * h * pix_bpp(c.pixfmt);      // c.pixfmt: set by lease_ctx (deep colour: rife-v4.6 plain pass only, pixfmt_supported)
+    const size_t nbytes = frame_bytes(w, h, c.pixfmt);      // c.pixfmt: set by lease_ctx (deep colour: rife-v4.6 plain pass only, pixfmt_supported)
     hipError_t e;
     {
         // Upload token (round 6, RIFE_HIP_H2D_TOKEN=0 in the test build: off): one caller uploads at a time and holds the token until its two frames have landed.
@@ -309,9 +335,9 @@ static int rife_hip_process_impl(const rife_hip_t* E, const uint8_t* in0, const 
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (!in0 || !in1 || !out) return fail(RIFE_HIP_EINVAL, "null frame pointer");
     if ((rc = pixfmt_supported(E, pixfmt))) return rc;
-    const size_t nbytes = (size_t)w * h * pix_bpp(pixfmt);
+    const size_t nbytes = frame_bytes(w, h, pixfmt);
     // rife.cpp:2470-2480: timestep 0 / 1 return an input frame unchanged (the reference rebinds the Mat; a copy is pixel-identical)
-    if (pix_deep(pixfmt) && (timestep == 0.f || timestep == 1.f)) { canon10_host(out, timestep == 0.f ? in0 : in1, (size_t)w * h, pixfmt); return 0; }
+    if (pix_deep(pixfmt) && (timestep == 0.f || timestep == 1.f)) { canon10_host(out, timestep == 0.f ? in0 : in1, w, h, pixfmt); return 0; }
     if (timestep == 0.f) { std::memmove(out, in0, nbytes); return 0; }
     if (timestep == 1.f) { std::memmove(out, in1, nbytes); return 0; }
     if ((rc = check_device(E->gpuid))) return rc;
@@ -328,7 +354,7 @@ int rife_hip_process(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1
     catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_process: unknown exception"); }
 }
 size_t rife_hip_frame_bytes(int w, int h, int pixfmt) {
-    return (w > 0 && h > 0) ? (size_t)w * h * pix_bpp(pixfmt) : 0;
+    return (w > 0 && h > 0 && pixfmt >= 0) ? frame_bytes(w, h, pix_base(pixfmt)) : 0;      // the colour bits do not change the size
 }
 int rife_hip_process_px(const rife_hip_t* E, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt) {
     int rc;
@@ -497,7 +523,7 @@ static int rife_hip_frame_upload_impl(const rife_hip_t* E, const uint8_t* rgb, i
     if ((rc = check_device(E->gpuid))) return rc;
     std::unique_ptr<rife_hip_frame> f(new rife_hip_frame);
     f->w = w; f->h = h; f->gpuid = E->gpuid; f->pixfmt = pixfmt;
-    const size_t nbytes = (size_t)w * h * pix_bpp(pixfmt);
+    const size_t nbytes = frame_bytes(w, h, pixfmt);
     f->nbytes = nbytes; f->pool = E->frame_pool;
     if (!(f->d = f->pool->take(nbytes))) return fail(RIFE_HIP_EHIP, "hipMalloc of a resident frame failed");
     // a copy on its own stream, drained here: the frame is complete before any stream of any caller can see the handle
@@ -537,14 +563,14 @@ void rife_hip_frame_release(rife_hip_frame_t* f) {
 static int rife_hip_process_frames_impl(const rife_hip_t* E, const rife_hip_frame_t* f0, const rife_hip_frame_t* f1, float timestep, uint8_t* out) {
     if (!f0 || !f1 || !out) return fail(RIFE_HIP_EINVAL, "null frame pointer");
     if (f0->w != f1->w || f0->h != f1->h) return fail(RIFE_HIP_EINVAL, "the two frames differ in size");
-    if (f0->pixfmt != f1->pixfmt) return fail(RIFE_HIP_EINVAL, "the two frames differ in pixel format");
+    if (f0->pixfmt != f1->pixfmt) return fail(RIFE_HIP_EINVAL, "the two frames differ in pixel format or colour description");
     const int w = f0->w, h = f0->h, pixfmt = f0->pixfmt;
     int rc;
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (f0->gpuid != E->gpuid || f1->gpuid != E->gpuid) return fail(RIFE_HIP_EINVAL, "frame was uploaded to another device");
     if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
-    const size_t nbytes = (size_t)w * h * pix_bpp(pixfmt);
+    const size_t nbytes = frame_bytes(w, h, pixfmt);
     if (timestep == 0.f || timestep == 1.f) {                 // rife.cpp:2470-2480 (a copy stream of the pool, never the legacy stream)
         hipStream_t st = nullptr;
         {
@@ -556,7 +582,7 @@ static int rife_hip_process_frames_impl(const rife_hip_t* E, const rife_hip_fram
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (st) { std::lock_guard<std::mutex> g(E->mu); E->upload_streams.push_back(st); }
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("frame download: ") + hipGetErrorString(e));
-        if (pix_deep(pixfmt)) canon10_host(out, out, (size_t)w * h, pixfmt);
+        if (pix_deep(pixfmt)) canon10_host(out, out, w, h, pixfmt);
         return 0;
     }
     std::unique_ptr<Ctx> c;
@@ -853,7 +879,7 @@ static int rife_hip_v4_extract_flow_impl(const rife_hip_t* E, const uint8_t* in0
     if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
     c.own_stream = true;
     if ((rc = ensure_ctx(c, w, h, pixfmt))) return rc;
-    const size_t nbytes = (size_t)w * h * pix_bpp(pixfmt);
+    const size_t nbytes = frame_bytes(w, h, pixfmt);
     HIPCHK(hipMemcpyAsync(c.d_in0, in0, nbytes, hipMemcpyHostToDevice, c.stream));
     HIPCHK(hipMemcpyAsync(c.d_in1, in1, nbytes, hipMemcpyHostToDevice, c.stream));
     launch_preproc(c.stream, c.d_in0, c.w, c.h, c.img0, c.wp, c.hp, pixfmt);
@@ -899,7 +925,7 @@ static int tap_prologue(const rife_hip_t* E, Ctx& c, const uint8_t* in0, const u
     if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
     c.own_stream = true;
     if ((rc = ensure_ctx(c, w, h, pixfmt))) return rc;
-    const size_t nbytes = (size_t)w * h * pix_bpp(pixfmt);
+    const size_t nbytes = frame_bytes(w, h, pixfmt);
     HIPCHK(hipMemcpyAsync(c.d_in0, in0, nbytes, hipMemcpyHostToDevice, c.stream));
     HIPCHK(hipMemcpyAsync(c.d_in1, in1, nbytes, hipMemcpyHostToDevice, c.stream));
     launch_preproc(c.stream, c.d_in0, c.w, c.h, c.img0, c.wp, c.hp, pixfmt);
@@ -1236,6 +1262,47 @@ int rife_hip_op_warp(int gpuid, const float* image, const float* flow, int c, in
     }
     (void)hipFree(d_i); (void)hipFree(d_f); (void)hipFree(d_o);
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_warp: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// the two 4:2:0 kernels alone (yuv.h), in the form the host would pick for a frame at an aligned address: planes -> zero-padded 10:10:10 dwords (hp x wp),
+// A2B10G10R10 (h x w) -> planes
+int rife_hip_op_yuv_to_rgb10(int gpuid, const void* yuv, int w, int h, int pixfmt, uint32_t* out_padded) {
+    int rc;
+    if ((rc = pixfmt_check(pixfmt))) return rc;
+    if (!pix_yuv(pixfmt) || !yuv || !out_padded || w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "op_yuv_to_rgb10: a 4:2:0 format, two arrays and a frame size");
+    if ((rc = check_device(gpuid))) return rc;
+    const int wp = (w + 31) / 32 * 32, hp = (h + 31) / 32 * 32;
+    const size_t nin = frame_bytes(w, h, pixfmt), nout = (size_t)wp * hp * 4;
+    void *d_i = nullptr, *d_o = nullptr;
+    hipError_t e = hipMalloc(&d_i, nin);
+    if (e == hipSuccess) e = hipMalloc(&d_o, nout);
+    if (e == hipSuccess) e = hipMemcpy(d_i, yuv, nin, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_o, 0xa5, nout);                     // the kernel writes the padding too
+    if (e == hipSuccess) {
+        launch_preproc_yuv(0, d_i, w, h, static_cast<uint32_t*>(d_o), wp, hp, pixfmt);
+        e = hipMemcpy(out_padded, d_o, nout, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_i); (void)hipFree(d_o);
+    if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_yuv_to_rgb10: ") + hipGetErrorString(e));
+    return 0;
+}
+int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int h, int pixfmt, void* yuv_out) {
+    int rc;
+    if ((rc = pixfmt_check(pixfmt))) return rc;
+    if (!pix_yuv(pixfmt) || !a2b10g10r10 || !yuv_out || w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "op_rgb10_to_yuv: a 4:2:0 format, two arrays and a frame size");
+    if ((rc = check_device(gpuid))) return rc;
+    const size_t nin = (size_t)w * h * 4, nout = frame_bytes(w, h, pixfmt);
+    void *d_i = nullptr, *d_o = nullptr;
+    hipError_t e = hipMalloc(&d_i, nin);
+    if (e == hipSuccess) e = hipMalloc(&d_o, nout);
+    if (e == hipSuccess) e = hipMemcpy(d_i, a2b10g10r10, nin, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_postproc_yuv(0, static_cast<const uint32_t*>(d_i), w, h, d_o, pixfmt);
+        e = hipMemcpy(yuv_out, d_o, nout, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_i); (void)hipFree(d_o);
+    if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_rgb10_to_yuv: ") + hipGetErrorString(e));
     return 0;
 }
 

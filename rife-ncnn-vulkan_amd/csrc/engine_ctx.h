@@ -64,7 +64,7 @@ struct Ctx {
     std::mutex use;                                                   // rife_hip_process_device: one caller at a time per stream workspace
     int w = 0, h = 0, wp = 0, hp = 0;
     int pixfmt = 0;                                                   // RIFE_HIP_PIX_* of the frames img0 / img1 hold and of the output being written (set per call; rife-v4.6 plain pass only)
-    int stage_bpp = 0;                                                // bytes per pixel d_in0 / d_in1 / d_out were sized for (3; 4 / 6 once an RGBA or deep-colour call has used the workspace)
+    size_t stage_bytes = 0;                                           // bytes d_in0 / d_in1 / d_out were sized for (frame_bytes of the largest format the workspace has served at this size)
     uint8_t *d_in0 = nullptr, *d_in1 = nullptr, *d_out = nullptr;   // staging for the host-buffer entry point
     uint32_t *img0 = nullptr, *img1 = nullptr;                       // padded RGBX u8
     float *X = nullptr, *S1 = nullptr, *T0 = nullptr, *T1 = nullptr; // block input, stem-1 output, trunk ping/pong
@@ -74,6 +74,7 @@ struct Ctx {
     float4* F = nullptr; float* M = nullptr;                         // full-resolution flow (4ch) and mask logit
     float4* F2 = nullptr; float* M2 = nullptr;                       // the other pair of buffers for a flow update fused into the next stem (stem_fused.h UPD); F, M are swapped with them
     float4* outf = nullptr;                                          // TTA only: out0 as float, padded
+    uint32_t* yuv_rgb = nullptr;                                     // 4:2:0 calls only (allocated by the first): the pass's A2B10G10R10 frame, tight w x h in wp x hp dwords; k_postproc_yuv reads it
     // hipGraph replay of the plain v4 schedule for launch-bound frame sizes: fixed staging buffers (d_in0 / d_in1 / d_out), the
     // timestep in device memory, one warm-up pass (lazy allocations, kernel attributes), then capture once and replay
     float* d_ts = nullptr;

@@ -14,15 +14,15 @@ static std::atomic<bool> g_fuse_flow_buffers{false};                 // some eng
 // (Re)allocate a workspace for frames of w x h (padded wp x hp).  `scratch` != null: borrow the big per-layer
 // scratch tensors (block input, stem output, trunk ping/pong) from another context of the same pixel count —
 // the TTA passes run one after another on one stream, only flows / F / M / images must persist per pass.
-static int ensure_ctx_dims_impl(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch, bool own_images, bool want_outf, int bpp) {
-    if (!c.v2 && c.wp == wp && c.hp == hp && c.w == w && c.h == h && (!want_outf || c.outf) && (scratch || c.stage_bpp >= bpp)) return 0;
-    c.stage_bpp = bpp;
+static int ensure_ctx_dims_impl(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch, bool own_images, bool want_outf, size_t stage_bytes) {
+    if (!c.v2 && c.wp == wp && c.hp == hp && c.w == w && c.h == h && (!want_outf || c.outf) && (scratch || c.stage_bytes >= stage_bytes)) return 0;
+    c.stage_bytes = stage_bytes;
     c.v2 = false;
     if (c.gexec) { (void)hipGraphExecDestroy(c.gexec); c.gexec = nullptr; }
     c.g_warm = false; c.d_ts = nullptr;
     for (void* p : c.allocs) (void)hipFree(p);
     c.allocs.clear();
-    c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr;
+    c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr;
     for (auto& pb : c.P) pb[0] = pb[1] = nullptr;                       // S16 trunk tensors: allocated by the first block that runs on them (ensure_s16)
     c.w = w; c.h = h; c.wp = wp; c.hp = hp;
     const size_t P = (size_t)wp * hp;
@@ -33,9 +33,9 @@ static int ensure_ctx_dims_impl(Ctx& c, int w, int h, int wp, int hp, const Ctx*
     }
     if (scratch) { c.X = scratch->X; c.S1 = scratch->S1; c.T0 = scratch->T0; c.T1 = scratch->T1; c.T2 = scratch->T2; }
     else {
-        if ((rc = dalloc(c, c.d_in0, (size_t)w * h * bpp))) return rc;
-        if ((rc = dalloc(c, c.d_in1, (size_t)w * h * bpp))) return rc;
-        if ((rc = dalloc(c, c.d_out, (size_t)w * h * bpp))) return rc;
+        if ((rc = dalloc(c, c.d_in0, stage_bytes))) return rc;
+        if ((rc = dalloc(c, c.d_in1, stage_bytes))) return rc;
+        if ((rc = dalloc(c, c.d_out, stage_bytes))) return rc;
         if ((rc = dalloc(c, c.X, P * 16))) return rc;                  // block 3: full res x 16 ch
         if ((rc = dalloc(c, c.S1, P / 4 * 32))) return rc;             // block 3 stem-0 output: (hp/2 x wp/2) x 32
         if ((rc = dalloc(c, c.T0, P / 16 * 64))) return rc;            // block 3 trunk: (hp/4 x wp/4) x 64 (the largest trunk)
@@ -69,23 +69,35 @@ static void reset_ctx(Ctx& c) {
     if (c.gexec) { (void)hipGraphExecDestroy(c.gexec); c.gexec = nullptr; }
     for (void* p : c.allocs) (void)hipFree(p);
     c.allocs.clear();
-    c.w = c.h = c.wp = c.hp = 0; c.stage_bpp = 0; c.v2 = false; c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.d_ts = nullptr; c.g_warm = false; for (auto& pb : c.P) pb[0] = pb[1] = nullptr;
+    c.w = c.h = c.wp = c.hp = 0; c.stage_bytes = 0; c.v2 = false; c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr; c.d_ts = nullptr; c.g_warm = false; for (auto& pb : c.P) pb[0] = pb[1] = nullptr;
 }
-static int ensure_ctx_dims(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch = nullptr, bool own_images = true, bool want_outf = false, int bpp = 3) {
-    const int rc = ensure_ctx_dims_impl(c, w, h, wp, hp, scratch, own_images, want_outf, bpp);
+static int ensure_ctx_dims(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch = nullptr, bool own_images = true, bool want_outf = false, size_t stage_bytes = 0) {
+    const int rc = ensure_ctx_dims_impl(c, w, h, wp, hp, scratch, own_images, want_outf, stage_bytes ? stage_bytes : (size_t)w * h * 3);
     if (rc) reset_ctx(c);
     return rc;
 }
 
-// bytes per pixel of a frame at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*); 0 = unknown format
+// bytes per pixel of an RGB frame at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*); 0 = not an RGB format (unknown, or 4:2:0: see frame_bytes)
 static inline int pix_bpp(int pixfmt) {
     return pixfmt == RIFE_HIP_PIX_RGB8 ? 3 : pixfmt == RIFE_HIP_PIX_RGB10_U16 ? 6 : (pixfmt == RIFE_HIP_PIX_A2B10G10R10 || pixfmt == RIFE_HIP_PIX_RGBA8) ? 4 : 0;
 }
-// the resident frames of this format are 10:10:10 dwords (the D = 10 instantiations of everything that reads a frame); RGB8 and RGBA8 frames are depth 8
-static inline bool pix_deep(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB10_U16 || pixfmt == RIFE_HIP_PIX_A2B10G10R10; }
+// a pixfmt = format (bits 0-7) | colour description (bits 8-12, 4:2:0 formats only)
+static inline int pix_base(int pixfmt) { return pixfmt & 0xff; }
+static inline bool pix_yuv(int pixfmt) { return pix_base(pixfmt) >= RIFE_HIP_PIX_NV12 && pix_base(pixfmt) <= RIFE_HIP_PIX_I420P10; }
+// size of a tightly packed w x h frame; 0 = unknown format.  4:2:0: a luma plane and two chroma planes of (w + 1) / 2 x (h + 1) / 2 samples
+static inline size_t frame_bytes(int w, int h, int pixfmt) {
+    if (!pix_yuv(pixfmt)) return (size_t)w * h * pix_bpp(pixfmt);
+    return ((size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2)) * (yuv_depth(pix_base(pixfmt)) == 10 ? 2 : 1);
+}
+// the resident frames of this format are 10:10:10 dwords (the D = 10 instantiations of everything that reads a frame); RGB8 and RGBA8 frames are depth 8.
+// 4:2:0 frames of either depth are converted to 10-bit RGB on the way in (exactly invertible, include/rife_hip.h) and ride the depth-10 schedule.
+static inline bool pix_deep(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB10_U16 || pixfmt == RIFE_HIP_PIX_A2B10G10R10 || pix_yuv(pixfmt); }
+// the format the quantising kernels of a pass write: the caller's, or for 4:2:0 the internal A2B10G10R10 frame k_postproc_yuv reads (Ctx::yuv_rgb)
+static inline int pix_inner(int pixfmt) { return pix_yuv(pixfmt) ? RIFE_HIP_PIX_A2B10G10R10 : pixfmt; }
 // the workspace serves frames of `pixfmt` from here on: staging buffers of that size, c.pixfmt for every launch site that reads or writes a frame
 static int ensure_ctx(Ctx& c, int w, int h, int pixfmt = RIFE_HIP_PIX_RGB8) {
-    const int rc = ensure_ctx_dims(c, w, h, (w + 31) / 32 * 32, (h + 31) / 32 * 32, nullptr, true, false, pix_bpp(pixfmt));   // pad to 32n, rife.cpp:2499-2500
+    int rc = ensure_ctx_dims(c, w, h, (w + 31) / 32 * 32, (h + 31) / 32 * 32, nullptr, true, false, frame_bytes(w, h, pixfmt));   // pad to 32n, rife.cpp:2499-2500
+    if (!rc && pix_yuv(pixfmt) && !c.yuv_rgb && (rc = dalloc(c, c.yuv_rgb, (size_t)c.wp * c.hp))) reset_ctx(c);      // only once a 4:2:0 format is served
     if (!rc) c.pixfmt = pixfmt;
     return rc;
 }
@@ -103,6 +115,7 @@ static inline dim3 tta_block(int elem_bytes) { return elem_bytes >= 16 ? dim3(8,
 static inline dim3 tta_grid(int w, int h, int elem_bytes) { const dim3 b = tta_block(elem_bytes); return dim3((w + b.x - 1) / b.x, (h + b.y - 1) / b.y); }
 // rife_preproc.comp: u8 HWC RGB -> zero-padded RGBX; four pixels per lane when the frame allows 4-byte loads
 static inline void launch_preproc(hipStream_t st, const uint8_t* rgb, int w, int h, uint32_t* out, int wp, int hp, int pixfmt = RIFE_HIP_PIX_RGB8) {
+    if (pix_yuv(pixfmt)) { launch_preproc_yuv(st, rgb, w, h, out, wp, hp, pixfmt); return; }      // 4:2:0 planes -> 10:10:10 dwords (yuv.h)
     if (pixfmt == RIFE_HIP_PIX_RGB10_U16) {
         const uint16_t* p = reinterpret_cast<const uint16_t*>(rgb);
         if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 7) == 0) hipLaunchKernelGGL(k_preproc10_u16x4, dim3((wp / 4 + 255) / 256, hp), dim3(256), 0, st, p, w, h, out, wp, hp);
@@ -439,7 +452,11 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
     }
     if (c.pixfmt && E.v40) return fail(RIFE_HIP_ENOSYS, "10-bit and RGBA frames are served for model family rife-v4.6 only, not rife-v4");
     const bool fuse_tail = !E.v40 && trunk_h2() && g_head_h2 && g_fuse_tail && E.blk[3].head.d_wh != nullptr;
-    FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out, c.w, c.h, c.wp, c.hp, c.pixfmt};
+    // 4:2:0: the quantising kernels write the internal A2B10G10R10 frame with the instantiations the packed 10-bit format uses; k_postproc_yuv follows below
+    uint8_t* const caller_out = d_out;
+    const int opf = pix_inner(c.pixfmt);
+    if (pix_yuv(c.pixfmt)) d_out = reinterpret_cast<uint8_t*>(c.yuv_rgb);
+    FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out, c.w, c.h, c.wp, c.hp, opf};
     const float* pending = nullptr;                                      // flow whose update of F, M the next block's stem applies
     // The update after block 0 never reaches HBM on its own (round 5): block 1's scale-4 stem samples it from flow0 (assemble_pixel UPD = 2) and ONE pass after
     // block 1 writes F, M with both updates applied (k_flow_update2) - bit for bit the tensors of the two-kernel sequence, one launch and 20 B / pixel of writes +
@@ -466,10 +483,15 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         HIPCHK(hipGetLastError());
     } else if (!fuse_tail) {
         Timed t(E.prof, "final", 0, st);
-        if (c.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
-        else if (c.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
-        else if (c.pixfmt == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        if (opf == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        else if (opf == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        else if (opf == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        HIPCHK(hipGetLastError());
+    }
+    if (pix_yuv(c.pixfmt)) {
+        Timed t(E.prof, "postproc_yuv", 0, st);
+        launch_postproc_yuv(st, c.yuv_rgb, c.w, c.h, caller_out, c.pixfmt);
         HIPCHK(hipGetLastError());
     }
     return 0;
@@ -502,7 +524,7 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
         const bool batched = G >= 2 && block_on_row_kernel(E, *cs[0], b) && block_on_s16(E, *cs[0], b);
         for (int g = 0; g < G; g++) {
             Ctx& c = *cs[g];
-            FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out[g], c.w, c.h, c.wp, c.hp, c.pixfmt};
+            FinalArgs fin{c.img0, c.img1, c.F, c.M, pix_yuv(c.pixfmt) ? reinterpret_cast<uint8_t*>(c.yuv_rgb) : d_out[g], c.w, c.h, c.wp, c.hp, pix_inner(c.pixfmt)};
             if (!batched) {
                 if ((rc = run_block_convs(E, c, b, ts[g], (b == 3 && fuse_tail) ? &fin : nullptr, nullptr, PH_ALL, pend[g]))) return rc;
                 pend[g] = nullptr;
@@ -535,15 +557,23 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
             if ((rc = after_block(c, g, b))) return rc;
         }
     }
-    for (int g = 0; g < G; g++)
+    for (int g = 0; g < G; g++) {
+        Ctx& c = *cs[g];
         if (!fuse_tail) {
-            Ctx& c = *cs[g];
-            if (c.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
-            else if (c.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
-            else if (c.pixfmt == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
-            else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], d_out[g], c.w, c.h, c.wp, c.hp);
+            const int opf = pix_inner(c.pixfmt);
+            uint8_t* const o = pix_yuv(c.pixfmt) ? reinterpret_cast<uint8_t*>(c.yuv_rgb) : d_out[g];
+            if (opf == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], o, c.w, c.h, c.wp, c.hp);
+            else if (opf == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], o, c.w, c.h, c.wp, c.hp);
+            else if (opf == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], o, c.w, c.h, c.wp, c.hp);
+            else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], o, c.w, c.h, c.wp, c.hp);
             HIPCHK(hipGetLastError());
         }
+        if (pix_yuv(c.pixfmt)) {      // on the pair's own stream: the caller's join comes after it
+            Timed t(E.prof, "postproc_yuv", 0, c.stream);
+            launch_postproc_yuv(c.stream, c.yuv_rgb, c.w, c.h, d_out[g], c.pixfmt);
+            HIPCHK(hipGetLastError());
+        }
+    }
     return 0;
 }
 

@@ -10,10 +10,15 @@
 // like src/webp_image.h:66-68), and baseline JPEG through jpeg_codec.h (quality 100 on output like src/main.cpp:215).
 // -a (absent in the reference, whose readers drop alpha): PNG, WebP and 32-bit BMP are read WITH their alpha, the frames cross the boundary as RGBA
 // Mats (include/rife_hip.h RIFE_HIP_PIX_RGBA8) and leave as RGBA PNG or WebP.  Without -a nothing changes.
+// Video mode (absent in the reference, whose frames are stills):  rife-hip -i in.y4m -o out.y4m|- -m .../rife-v4.6 [-n N] [-c MATRIX[:RANGE]]
+// A YUV4MPEG2 file goes through the same pipeline as 4:2:0 frames (include/rife_hip.h RIFE_HIP_PIX_I420 / I420P10): no image codec and no colour conversion
+// on the host, every input frame uploaded once (stream mode), output frames written in order.
 // Host glue only: every pixel of arithmetic happens in librife_hip.so.
 #include <dirent.h>
+#include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
+#include <unistd.h>
 #include <zlib.h>
 
 #include <algorithm>
@@ -25,6 +30,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <queue>
@@ -562,10 +568,12 @@ struct SharedFrame {
     std::vector<unsigned char> px;
     std::vector<uint16_t> px10;                                       // -b 10: the frame as 10-bit codes instead of px
     bool rgba = false;                                                // -a: px holds four bytes per pixel, R G B A
+    int yuv = 0;                                                      // video mode: px holds one 4:2:0 frame of this pixfmt (RIFE_HIP_PIX_I420 / I420P10 | RIFE_HIP_CSP_*)
     const rife_hip_frame* on(const RIFE* r) {
         std::lock_guard<std::mutex> g(mu);
         for (auto& e : resident) if (e.first == r) return e.second;
-        rife_hip_frame* f = rgba         ? r->upload(ncnn::Mat(w, h, (void*)px.data(), (size_t)4, 4))      // elemsize 4, elempack 4 = RGBA8 (rife.cpp)
+        rife_hip_frame* f = yuv          ? r->upload_yuv(px.data(), w, h, yuv)
+                            : rgba       ? r->upload(ncnn::Mat(w, h, (void*)px.data(), (size_t)4, 4))      // elemsize 4, elempack 4 = RGBA8 (rife.cpp)
                             : px10.empty() ? r->upload(ncnn::Mat(w, h, (void*)px.data(), (size_t)3, 3))
                                          : r->upload(ncnn::Mat(w, h, (void*)px10.data(), (size_t)6, 3));      // elemsize 6, elempack 3 = RGB10_U16 (rife.cpp)
         if (f) resident.emplace_back(r, f);
@@ -637,9 +645,144 @@ private:
     std::queue<Task> q;
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// YUV4MPEG2 (video mode)
+// ---------------------------------------------------------------------------------------------------------------
+// The frame / timestep schedule of directory mode (src/main.cpp:705-731): output i of numframe over `count` input frames takes frames sx, sx + 1 at fx.
+static void schedule_step(int i, int count, int numframe, int& sx, float& fx) {
+    const double scale = (double)count / numframe;                          // double product rounded to float, like src/main.cpp:713-718
+    fx = (float)(i * scale);
+    sx = (int)std::floor(fx);
+    fx -= sx;
+    if (sx < 0) { sx = 0; fx = 0.f; }
+    if (sx >= count - 1) { sx = count - 2; fx = 1.f; }
+}
+
+struct Y4m {
+    int fd = -1;
+    int w = 0, h = 0;
+    long long fnum = 0, fden = 0;
+    bool p10 = false;                                                 // C420p10: u16 little-endian samples, the code in the low ten bits
+    int range = -1;                                                   // XCOLORRANGE: 1 FULL, 0 LIMITED, -1 absent
+    std::vector<std::string> other;                                   // every header field but W, H, F, verbatim and in order (I, A, C, X...)
+    size_t hdr_len = 0, frame_bytes = 0;
+    long long count = 0;
+    ~Y4m() { if (fd >= 0) close(fd); }
+    // frame k: the bytes after its "FRAME\n" marker
+    bool read_frame(long long k, std::vector<unsigned char>& px) const {
+        px.resize(frame_bytes);
+        const off_t at = (off_t)hdr_len + (off_t)k * (off_t)(frame_bytes + 6) + 6;
+        size_t got = 0;
+        while (got < frame_bytes) {
+            const ssize_t n = pread(fd, px.data() + got, frame_bytes - got, at + (off_t)got);
+            if (n <= 0) return false;
+            got += (size_t)n;
+        }
+        return true;
+    }
+};
+
+// Header: "YUV4MPEG2 W H F [I] [A] [C] [X...]" and a newline within the first 256 bytes; progressive 4:2:0 at 8 or 10 bits only.  The frame count comes from the
+// file size; every frame starts with a plain "FRAME\n".
+static bool y4m_open(const std::string& path, Y4m& y, std::string& err) {
+    y.fd = open(path.c_str(), O_RDONLY);
+    struct stat st;
+    if (y.fd < 0 || fstat(y.fd, &st) != 0 || !S_ISREG(st.st_mode)) { err = "cannot open " + path; return false; }
+    char buf[256];
+    const ssize_t n = pread(y.fd, buf, sizeof buf, 0);
+    const char* nl = n > 0 ? (const char*)memchr(buf, '\n', (size_t)n) : nullptr;
+    if (!nl) { err = "no YUV4MPEG2 header line in the first 256 bytes"; return false; }
+    const std::string line(buf, (size_t)(nl - buf));
+    y.hdr_len = (size_t)(nl - buf) + 1;
+    if (line.compare(0, 9, "YUV4MPEG2") != 0 || (line.size() > 9 && line[9] != ' ')) { err = "not a YUV4MPEG2 file"; return false; }
+    bool have_c = false;
+    size_t pos = 9;
+    while (pos < line.size()) {
+        while (pos < line.size() && line[pos] == ' ') pos++;
+        const size_t e = std::min(line.find(' ', pos), line.size());
+        if (e == pos) break;
+        const std::string tok = line.substr(pos, e - pos);
+        pos = e;
+        const std::string val = tok.substr(1);
+        auto number = [&](long long& v) {
+            if (val.empty() || val.size() > 9 || val.find_first_not_of("0123456789") != std::string::npos) return false;
+            v = atoll(val.c_str());
+            return true;
+        };
+        if (tok[0] == 'W' || tok[0] == 'H') {
+            long long v = 0;
+            if (!number(v) || v < 1 || v > 65535) { err = "bad frame size field '" + tok + "'"; return false; }
+            (tok[0] == 'W' ? y.w : y.h) = (int)v;
+        } else if (tok[0] == 'F') {
+            const size_t c = val.find(':');
+            const std::string a = val.substr(0, c), b = c == std::string::npos ? "" : val.substr(c + 1);
+            if (a.empty() || b.empty() || a.size() > 9 || b.size() > 9 || a.find_first_not_of("0123456789") != std::string::npos ||
+                b.find_first_not_of("0123456789") != std::string::npos || atoll(a.c_str()) < 1 || atoll(b.c_str()) < 1) { err = "bad frame rate field '" + tok + "'"; return false; }
+            y.fnum = atoll(a.c_str()); y.fden = atoll(b.c_str());
+        } else {
+            if (tok[0] == 'I' && tok != "Ip") { err = "interlacing '" + tok + "' is not served (progressive frames, Ip, only)"; return false; }
+            if (tok[0] == 'C') {
+                have_c = true;
+                if (tok == "C420p10") y.p10 = true;
+                else if (tok != "C420" && tok != "C420jpeg" && tok != "C420mpeg2" && tok != "C420paldv") {
+                    err = "colourspace '" + tok + "' is not served (C420, C420jpeg, C420mpeg2, C420paldv, C420p10 only)"; return false;
+                }
+            }
+            if (tok == "XCOLORRANGE=FULL") y.range = 1;
+            if (tok == "XCOLORRANGE=LIMITED") y.range = 0;
+            y.other.push_back(tok);
+        }
+    }
+    (void)have_c;                                                     // no C field: 4:2:0 at 8 bits, the format's default
+    if (y.w < 1 || y.h < 1) { err = "the header has no W / H field"; return false; }
+    if (y.fnum < 1) { err = "the header has no F (frame rate) field"; return false; }
+    if ((long long)y.w * y.h > (1ll << 27)) { err = "frame too large"; return false; }
+    y.frame_bytes = ((size_t)y.w * y.h + 2 * (size_t)((y.w + 1) / 2) * ((y.h + 1) / 2)) * (y.p10 ? 2 : 1);
+    const long long body = (long long)st.st_size - (long long)y.hdr_len, rec = (long long)y.frame_bytes + 6;
+    y.count = body / rec;
+    for (long long k = 0; k < y.count + (body % rec >= 6 ? 1 : 0); k++) {
+        char m[6];
+        if (pread(y.fd, m, 6, (off_t)y.hdr_len + (off_t)(k * rec)) != 6 || memcmp(m, "FRAME\n", 6) != 0) {
+            err = "no plain FRAME marker where frame " + std::to_string(k) + " should start"; return false;
+        }
+    }
+    if (body % rec) { err = "truncated: " + std::to_string(body % rec) + " stray byte(s) after the last whole frame (" + std::to_string(y.count) + " whole frames)"; return false; }
+    if (y.count < 2) { err = "a video needs at least two frames"; return false; }
+    return true;
+}
+
+// The one save stage that must emit in order: frames arrive from the save threads in any order and leave by output index.  The loaders keep at most `window`
+// outputs in flight past the next one to be written (wait_turn), which bounds this buffer.
+struct Y4mWriter {
+    FILE* f = nullptr;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::map<int, std::vector<unsigned char>> pending;
+    int next = 0;
+    bool failed = false;
+    void submit(int id, std::vector<unsigned char>&& px) {
+        std::lock_guard<std::mutex> g(mu);
+        if (failed) return;
+        pending.emplace(id, std::move(px));
+        for (auto it = pending.find(next); it != pending.end(); it = pending.find(next)) {
+            if (fwrite("FRAME\n", 1, 6, f) != 6 || fwrite(it->second.data(), 1, it->second.size(), f) != it->second.size()) { failed = true; pending.clear(); break; }
+            pending.erase(it);
+            next++;
+        }
+        cv.notify_all();
+    }
+    void fail() { std::lock_guard<std::mutex> g(mu); failed = true; pending.clear(); cv.notify_all(); }
+    bool wait_turn(int id, int window) {      // false: the run has failed, issue nothing more
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return failed || id < next + window; });
+        return !failed;
+    }
+};
+
 static void print_usage() {
     fprintf(stderr, "Usage: rife-hip -0 infile -1 infile1 -o outfile [options]...\n");
-    fprintf(stderr, "       rife-hip -i indir -o outdir [options]...\n\n");
+    fprintf(stderr, "       rife-hip -i indir -o outdir [options]...\n");
+    fprintf(stderr, "       rife-hip -i in.y4m -o out.y4m|- [-n num-frame] [-c matrix[:range]] -m rife-v4.6-model-path ...\n\n");
     fprintf(stderr, "  -h                   show this help\n");
     fprintf(stderr, "  -v                   verbose output\n");
     fprintf(stderr, "  -0 input0-path       input image0 path (jpg/png/webp/bmp/pnm)\n");
@@ -656,6 +799,9 @@ static void print_usage() {
     fprintf(stderr, "  -u                   enable UHD mode\n");
     fprintf(stderr, "  -f pattern-format    output image filename pattern format (%%08d.jpg/png/webp/ppm, default=ext/%%08d.png)\n");
     fprintf(stderr, "  -b bit-depth         bits per sample, 8 or 10 (default=8); 10: rife-v4.6 only, 16-bit png / maxval-1023 ppm output\n");
+    fprintf(stderr, "  -c matrix[:range]    video mode (-i in.y4m): colour description, 709 / 601 / 2020 and limited / full (default=709:limited, or the file's XCOLORRANGE);\n");
+    fprintf(stderr, "                       4:2:0 YUV4MPEG2 at 8 or 10 bits, rife-v4.6 only, not with -x/-z/-u/-a/-b 10; -o - writes to stdout; -i - (stdin) is not served;\n");
+    fprintf(stderr, "                       the header line must end within 256 bytes and every frame must start with a plain FRAME line (no frame parameters)\n");
     fprintf(stderr, "  -a                   keep the alpha channel (png/webp/32-bit bmp in, png/webp out); rife-v4.6 only, not with -x/-z/-u/-b 10\n");
 }
 
@@ -720,7 +866,7 @@ int main(int argc, char** argv) {
         if (!encode_image10(argv[3], w, h, codes.data())) { fprintf(stderr, "encode image %s failed\n", argv[3]); return 1; }
         return 0;
     }
-    std::string input0, input1, inputpath, outputpath, model = "rife-v2.3", pattern_format = "%08d.png";
+    std::string input0, input1, inputpath, outputpath, model = "rife-v2.3", pattern_format = "%08d.png", colour;
     int numframe = 0;
     float timestep = 0.5f;
     std::vector<int> gpuid, jobs_proc;
@@ -728,7 +874,7 @@ int main(int argc, char** argv) {
     bool verbose = false, tta = false, tta_temporal = false, uhd = false, keep_alpha = false;
 
     int opt;
-    while ((opt = getopt(argc, argv, "0:1:i:o:n:s:m:g:j:f:b:avxzuh")) != -1) {
+    while ((opt = getopt(argc, argv, "0:1:i:o:n:s:m:g:j:f:b:c:avxzuh")) != -1) {
         switch (opt) {
             case '0': input0 = optarg; break;
             case '1': input1 = optarg; break;
@@ -749,6 +895,7 @@ int main(int argc, char** argv) {
             }
             case 'f': pattern_format = optarg; break;
             case 'b': bits = atoi(optarg); break;
+            case 'c': colour = optarg; break;
             case 'a': keep_alpha = true; break;
             case 'v': verbose = true; break;
             case 'x': tta = true; break;
@@ -774,14 +921,41 @@ int main(int argc, char** argv) {
         return -1;
     }
 
+    // ---- video mode: -i names a regular .y4m file.  Everything that is wrong with the file or the flags ends here with a message and exit status 1 ----
+    const bool video = !inputpath.empty() && !is_dir(inputpath) && ext_of(inputpath) == "y4m";
+    Y4m y4m;
+    Y4mWriter y4m_out;
+    int yuv_pixfmt = 0;
+    if (inputpath == "-") { fprintf(stderr, "reading a video from stdin (-i -) is not served: the frame count must be known\n"); return 1; }
+    if (!colour.empty() && !video) { fprintf(stderr, "-c goes with video mode (-i in.y4m) only\n"); return 1; }
+    if (video) {
+        const char* mode = tta ? "TTA mode (-x)" : tta_temporal ? "temporal TTA mode (-z)" : uhd ? "UHD mode (-u)" : nullptr;
+        if (mode) { fprintf(stderr, "4:2:0 YUV frames are served for model family rife-v4.6 in plain mode only, not for %s\n", mode); return 1; }
+        if (keep_alpha || deep) { fprintf(stderr, "%s goes with image files, not with a .y4m video (its depth comes from the file, and it has no alpha)\n", keep_alpha ? "-a" : "-b 10"); return 1; }
+        if (outputpath != "-" && (is_dir(outputpath) || ext_of(outputpath) != "y4m")) { fprintf(stderr, "a .y4m input goes to a .y4m file or to - (stdout)\n"); return 1; }
+        std::string err;
+        if (!y4m_open(inputpath, y4m, err)) { fprintf(stderr, "%s: %s\n", inputpath.c_str(), err.c_str()); return 1; }
+        int matrix = RIFE_HIP_CSP_BT709, full = y4m.range == 1;
+        if (!colour.empty()) {
+            const size_t c = colour.find(':');
+            const std::string m = colour.substr(0, c), r = c == std::string::npos ? "" : colour.substr(c + 1);
+            if (m == "709") matrix = RIFE_HIP_CSP_BT709; else if (m == "601") matrix = RIFE_HIP_CSP_BT601; else if (m == "2020") matrix = RIFE_HIP_CSP_BT2020NCL;
+            else { fprintf(stderr, "invalid colour matrix '%s', must be 709, 601 or 2020\n", m.c_str()); return 1; }
+            if (r == "full") full = 1; else if (r == "limited") full = 0;
+            else if (!r.empty()) { fprintf(stderr, "invalid colour range '%s', must be limited or full\n", r.c_str()); return 1; }
+        }
+        yuv_pixfmt = (y4m.p10 ? RIFE_HIP_PIX_I420P10 : RIFE_HIP_PIX_I420) | matrix | (full ? RIFE_HIP_CSP_FULL : 0);
+        if (numframe == 0) numframe = (int)std::min<long long>(y4m.count * 2, 1 << 30);
+    }
+
     std::string pattern = pattern_format, format;
-    {
+    if (!video) {
         const size_t dot = pattern_format.rfind('.');
         if (dot != std::string::npos) { pattern = pattern_format.substr(0, dot); format = pattern_format.substr(dot + 1); }
         else { pattern = "%08d"; format = pattern_format; }
         if (pattern.empty()) pattern = "%08d";
     }
-    if (!is_dir(outputpath)) {
+    if (!video && !is_dir(outputpath)) {
         const std::string e = ext_of(outputpath);
         if (e == "png") format = "png";
         else if (e == "ppm") format = "ppm";
@@ -789,7 +963,7 @@ int main(int argc, char** argv) {
         else if (e == "jpg" || e == "jpeg") format = "jpg";
         else { fprintf(stderr, "invalid outputpath extension type\n"); return -1; }
     }
-    if (format != "png" && format != "ppm" && format != "webp" && format != "jpg") { fprintf(stderr, "invalid format argument\n"); return -1; }
+    if (!video && format != "png" && format != "ppm" && format != "webp" && format != "jpg") { fprintf(stderr, "invalid format argument\n"); return -1; }
     if (deep && format != "png" && format != "ppm") { fprintf(stderr, "10-bit frames (-b 10) are written as png (16-bit) or ppm (maxval 1023) only, not %s\n", format.c_str()); return -1; }
     if (keep_alpha && format != "png" && format != "webp") { fprintf(stderr, "RGBA frames (-a) are written as png or webp only, %s has no alpha\n", format.c_str()); return -1; }
 #ifndef RIFE_HIP_WITH_WEBP
@@ -801,22 +975,29 @@ int main(int argc, char** argv) {
     else if (model.find("rife-v4") != std::string::npos) rife_v4 = true;
     else if (model.find("rife") == std::string::npos) { fprintf(stderr, "unknown model dir type\n"); return -1; }
     if (keep_alpha && !rife_v4) { fprintf(stderr, "alpha (-a) is served for model family rife-v4.6 only, not for %s\n", model.c_str()); return -1; }
+    if (video && !rife_v4) { fprintf(stderr, "4:2:0 YUV frames are served for model family rife-v4.6 in plain mode only, not for %s\n", model.c_str()); return 1; }
     if (!rife_v4 && (numframe != 0 || timestep != 0.5f)) { fprintf(stderr, "only rife-v4 model support custom numframe and timestep\n"); return -1; }
 
     // ---- task list (src/main.cpp:692-766) ----
     std::vector<Task> tasks;
-    if (!inputpath.empty() && is_dir(inputpath) && is_dir(outputpath)) {
+    if (video) {
+        for (int i = 0; i < numframe; i++) {
+            int sx; float fx;
+            schedule_step(i, (int)y4m.count, numframe, sx, fx);
+            Task t;
+            t.id = i; t.timestep = fx; t.w = y4m.w; t.h = y4m.h;
+            t.in0path = "frame " + std::to_string(sx); t.in1path = "frame " + std::to_string(sx + 1);      // the cache's keys
+            t.outpath = "output frame " + std::to_string(i);
+            tasks.push_back(std::move(t));
+        }
+    } else if (!inputpath.empty() && is_dir(inputpath) && is_dir(outputpath)) {
         std::vector<std::string> names;
         if (!list_directory(inputpath, names) || names.size() < 2) return -1;
         const int count = (int)names.size();
         if (numframe == 0) numframe = count * 2;
-        const double scale = (double)count / numframe;                          // double product rounded to float, like src/main.cpp:713-718
         for (int i = 0; i < numframe; i++) {
-            float fx = (float)(i * scale);
-            int sx = (int)std::floor(fx);
-            fx -= sx;
-            if (sx < 0) { sx = 0; fx = 0.f; }
-            if (sx >= count - 1) { sx = count - 2; fx = 1.f; }
+            int sx; float fx;
+            schedule_step(i, count, numframe, sx, fx);
             char name[512];
             snprintf(name, sizeof name, pattern.c_str(), i + 1);               // ffmpeg numbering starts at 1
             Task t;
@@ -848,11 +1029,17 @@ int main(int argc, char** argv) {
         g_png_helpers = std::max(0, std::min(15, spare / jobs_save - 1));
     }
     const int ndev = rife_hip_device_count();
-    for (int g : gpuid) if (g < 0 || g >= ndev) { fprintf(stderr, "invalid gpu device\n"); return -1; }
+    for (int g : gpuid) if (g < 0 || g >= ndev) { fprintf(stderr, "invalid gpu device\n"); return video ? 1 : -1; }
     std::vector<RIFE*> rife;
     for (int g : gpuid) {
         RIFE* r = new RIFE(g, tta, tta_temporal, uhd, 1, rife_v2, rife_v4);
-        if (r->load(model) != 0) { fprintf(stderr, "loading %s failed: %s\n", model.c_str(), rife_hip_last_error()); return -1; }
+        if (r->load(model) != 0) { fprintf(stderr, "loading %s failed: %s\n", model.c_str(), rife_hip_last_error()); return video ? 1 : -1; }
+        if (video) {      // rife-v4 (4.0) shares the directory prefix, and the engine knows which colour descriptions it serves: ask it now, with one pixel
+            const uint16_t one[3] = {0, 0, 0};
+            rife_hip_frame* f = r->upload_yuv(one, 1, 1, yuv_pixfmt);
+            if (!f) { fprintf(stderr, "video mode is not available: %s\n", rife_hip_last_error()); return 1; }
+            RIFE::release(f);
+        }
         if (deep) {      // the engine refuses 10-bit frames for every family but rife-v4.6 and for -x / -z / -u: ask it now, with one pixel, not at the first pair
             uint16_t one[3] = {0, 0, 0};
             rife_hip_frame* f = r->upload(ncnn::Mat(1, 1, (void*)one, (size_t)6, 3));
@@ -868,6 +1055,16 @@ int main(int argc, char** argv) {
         rife.push_back(r);
     }
 
+    if (video) {      // the output header: the input's, with the frame rate times numframe / count as a reduced fraction
+        y4m_out.f = outputpath == "-" ? stdout : fopen(outputpath.c_str(), "wb");
+        if (!y4m_out.f) { fprintf(stderr, "cannot write %s\n", outputpath.c_str()); return 1; }
+        long long num = y4m.fnum * numframe, den = y4m.fden * y4m.count, a = num, b = den;
+        while (b) { const long long t = a % b; a = b; b = t; }
+        std::string hdr = "YUV4MPEG2 W" + std::to_string(y4m.w) + " H" + std::to_string(y4m.h) + " F" + std::to_string(num / a) + ":" + std::to_string(den / a);
+        for (const std::string& tok : y4m.other) hdr += " " + tok;
+        hdr += "\n";
+        if (fwrite(hdr.data(), 1, hdr.size(), y4m_out.f) != hdr.size()) { fprintf(stderr, "cannot write %s\n", outputpath.c_str()); return 1; }
+    }
     const auto tp1 = std::chrono::steady_clock::now();
     // ---- load -> proc -> save (src/main.cpp:309-436, 830-904) ----
     TaskQueue toproc, tosave;
@@ -880,11 +1077,20 @@ int main(int argc, char** argv) {
             { std::lock_guard<std::mutex> g(next_mu); if (next_task >= tasks.size()) return; k = next_task++; }
             Task t = std::move(tasks[k]);
             FrameCache::Frame f0, f1;
+            if (video && !y4m_out.wait_turn(t.id, 32)) return;                  // at most 32 outputs past the next one to be written: bounds the writer's reorder buffer
             auto decode = [&](const std::string& p, SharedFrame& fr) {
+                if (video) {
+                    fr.w = y4m.w; fr.h = y4m.h; fr.yuv = yuv_pixfmt;
+                    return y4m.read_frame(atoll(p.c_str() + 6), fr.px);         // "frame <k>"
+                }
                 fr.rgba = keep_alpha;
                 return deep ? decode_image10(p, fr.w, fr.h, fr.px10) : keep_alpha ? decode_image_rgba(p, fr.w, fr.h, fr.px) : decode_image(p, fr.w, fr.h, fr.px);
             };
-            if (!cache.get(t.in0path, f0, decode) || !cache.get(t.in1path, f1, decode)) { fprintf(stderr, "decode image %s or %s failed\n", t.in0path.c_str(), t.in1path.c_str()); continue; }
+            if (!cache.get(t.in0path, f0, decode) || !cache.get(t.in1path, f1, decode)) {
+                fprintf(stderr, "decode image %s or %s failed\n", t.in0path.c_str(), t.in1path.c_str());
+                if (video) { y4m_out.fail(); return; }                          // a video with a hole is no output
+                continue;
+            }
             if (f1->w != f0->w || f1->h != f0->h) { fprintf(stderr, "%s and %s differ in size\n", t.in0path.c_str(), t.in1path.c_str()); continue; }
             t.w = f0->w; t.h = f0->h; t.fr0 = f0; t.fr1 = f1;
             toproc.put(std::move(t));
@@ -899,7 +1105,14 @@ int main(int argc, char** argv) {
             Task t = toproc.get();
             if (t.id == -233) return;                                          // end marker, like the reference
             replica_tasks[me]++;
-            if (deep && (t.timestep == 0.f || t.timestep == 1.f)) t.out10 = (t.timestep == 0.f ? t.fr0 : t.fr1)->px10;
+            if (video) {                                                       // timestep 0 / 1 too: the engine returns the frame's samples as codes, the rule lives there
+                const rife_hip_frame* d0 = t.fr0->on(r);
+                const rife_hip_frame* d1 = t.fr1->on(r);
+                t.out.resize(y4m.frame_bytes);
+                ncnn::Mat out(t.w, t.h, (void*)t.out.data(), (size_t)1, 1);    // process() writes one frame of the resident frames' format behind .data
+                if (!d0 || !d1 || r->process(d0, d1, t.timestep, out) != 0) { fprintf(stderr, "process %s failed: %s\n", t.outpath.c_str(), rife_hip_last_error()); y4m_out.fail(); continue; }
+            }
+            else if (deep && (t.timestep == 0.f || t.timestep == 1.f)) t.out10 = (t.timestep == 0.f ? t.fr0 : t.fr1)->px10;
             else if (t.timestep == 0.f || t.timestep == 1.f) t.out = (t.timestep == 0.f ? t.fr0 : t.fr1)->px;      // rife.cpp:2470-2480: an input frame, unchanged
             else if (deep) {
                 const rife_hip_frame* d0 = t.fr0->on(r);
@@ -923,6 +1136,11 @@ int main(int argc, char** argv) {
         for (;;) {
             Task t = tosave.get();
             if (t.id == -233) return;
+            if (video) {
+                y4m_out.submit(t.id, std::move(t.out));
+                if (verbose) fprintf(stderr, "%s %s %f -> %s done\n", t.in0path.c_str(), t.in1path.c_str(), t.timestep, t.outpath.c_str());
+                continue;
+            }
             const bool ok = deep ? encode_image10(t.outpath, t.w, t.h, t.out10.data()) : keep_alpha ? encode_image_rgba(t.outpath, t.w, t.h, t.out.data())
                                                                                               : encode_image(t.outpath, t.w, t.h, t.out.data());
             if (!ok) fprintf(stderr, "encode image %s failed\n", t.outpath.c_str());
@@ -946,5 +1164,10 @@ int main(int argc, char** argv) {
     }
     cache.clear();                                                             // resident frames go before their engines
     for (RIFE* r : rife) delete r;
+    if (video) {
+        const bool flushed = fflush(y4m_out.f) == 0;
+        if (y4m_out.f != stdout) fclose(y4m_out.f);
+        if (y4m_out.failed || !flushed || y4m_out.next != numframe) { fprintf(stderr, "%s is incomplete: %d of %d frames written\n", outputpath.c_str(), y4m_out.next, numframe); return 1; }
+    }
     return 0;
 }

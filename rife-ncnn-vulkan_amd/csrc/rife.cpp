@@ -95,6 +95,23 @@ int RIFE::process(const rife_hip_frame* frame0, const rife_hip_frame* frame1, fl
     return ret;
 }
 
+int RIFE::process_yuv(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    int ret = rife_hip_process_px(engine, in0, in1, w, h, timestep, out, pixfmt);
+    if (ret) fprintf(stderr, "RIFE::process_yuv: %s\n", rife_hip_last_error());
+    return ret;
+}
+
+rife_hip_frame* RIFE::upload_yuv(const void* frame, int w, int h, int pixfmt) const
+{
+    if (!engine || !frame) return 0;
+    rife_hip_frame* f = 0;
+    if (rife_hip_frame_upload_px(engine, frame, w, h, pixfmt, &f))
+        fprintf(stderr, "RIFE::upload_yuv: %s\n", rife_hip_last_error());
+    return f;
+}
+
 void RIFE::release(rife_hip_frame* frame)
 {
     rife_hip_frame_release(frame);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # ASan + UBSan and TSan job for the HOST side (csrc/main.cpp, rife.cpp, jpeg_codec.h, the PNG band writer); no GPU needed: the engine behind the C-ABI is
-# tests/sanitize/stub_engine.cpp (+ stub_engine_deep.cpp / stub_engine_alpha.cpp for the 10-bit and RGBA entry points).  Writes a log to stdout; exit code != 0 if any sanitizer reported.
+# tests/sanitize/stub_engine.cpp (+ stub_engine_deep.cpp / stub_engine_yuv.cpp for the 10-bit, RGBA and 4:2:0 entry points).  Writes a log to stdout; exit code != 0 if any sanitizer reported.
 #   tools/sanitize_run.sh > profiles/r5/sanitize.txt
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -22,6 +22,9 @@ RIFE_HIP_BIN=$ASAN python -m pytest tests/test_cli_deep.py -q -m "not gpu" -k "c
 [ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
 echo "== 1c. the RGBA codecs (--transcode -a: png colour types 4 / 6, tRNS, 16-bit, webp, 32-bit bmp, truncated and crafted files) of tests/test_cli_alpha.py through the same binary"
 RIFE_HIP_BIN=$ASAN python -m pytest tests/test_cli_alpha.py -q -m "not gpu" -k "cpp_cli" 2>&1 | tail -4
+[ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
+echo "== 1d. the YUV4MPEG2 reader and writer (headers, rate fraction, schedule, in-order output from 4 save threads, truncated / malformed files, flags out of scope) of tests/test_cli_yuv.py through the same binary"
+RIFE_HIP_BIN=$ASAN python -m pytest tests/test_cli_yuv.py -q -m "not gpu" -k "cpp_cli" 2>&1 | tail -4
 [ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
 T=$(mktemp -d)
 python - $T <<'PY'
@@ -122,6 +125,39 @@ names = sorted(os.listdir(os.path.join(t, "out")))
 im = Image.open(os.path.join(t, "out", names[0]))
 print("   -a output is RGBA:", im.mode == "RGBA", im.size)
 PY
+echo "== 3d. video mode (.y4m in, .y4m out; 4:2:0 frames through upload_px / process_frames of the stub, the in-order writer behind several save threads) under both"
+python - $T <<'PY'
+import sys, os
+sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+import yuv_ref as yr
+from test_cli_yuv import write_y4m, random_frames
+t = sys.argv[1]
+write_y4m(os.path.join(t, "odd.y4m"), "YUV4MPEG2 W333 H241 F30000:1001 Ip A1:1 C420jpeg XCOLORRANGE=LIMITED", random_frames(9, 333, 241, yr.PIX_I420, 1))
+write_y4m(os.path.join(t, "p10.y4m"), "YUV4MPEG2 W333 H241 F25:1 Ip C420p10", random_frames(5, 333, 241, yr.PIX_I420P10, 2))
+PY
+for v in odd p10; do
+    run "asan $v.y4m -g 0 -j 1:1:1" $ASAN -i $T/$v.y4m -o $T/ref.y4m -m rife-v4.6 -n 23 -g 0 -j 1:1:1
+    run "asan $v.y4m -g 0,1 -j 3:2,3:4" $ASAN -i $T/$v.y4m -o $T/out.y4m -m rife-v4.6 -n 23 -g 0,1 -j 3:2,3:4
+    cmp -s $T/ref.y4m $T/out.y4m && echo "      == the 1-thread file" || { echo "      Y4M DIFFERS from the 1-thread file"; FAIL=1; }
+    run "tsan $v.y4m -g 0,1 -j 3:2,3:4" $TSAN -i $T/$v.y4m -o $T/out.y4m -m rife-v4.6 -n 23 -g 0,1 -j 3:2,3:4
+    cmp -s $T/ref.y4m $T/out.y4m && echo "      == the 1-thread file" || { echo "      Y4M DIFFERS from the 1-thread file"; FAIL=1; }
+    $TSAN -i $T/$v.y4m -o - -m rife-v4.6 -n 23 -g 0,0 -j 2:1,2:3 > $T/out.y4m 2> $T/log.txt; rc=$?
+    echo "   tsan $v.y4m -o - -g 0,0 -j 2:1,2:3: rc $rc"; [ $rc -ne 0 ] && { FAIL=1; tail -30 $T/log.txt; }
+    cmp -s $T/ref.y4m $T/out.y4m && echo "      == the 1-thread file" || { echo "      Y4M DIFFERS from the 1-thread file"; FAIL=1; }
+done
+for bad in "YUV4MPEG2 W8 H6 F25:1 C422" "YUV4MPEG2 W8 H6 F25:1 It C420" "YUV4MPEG2 W0 H6 F25:1 C420" "YUV4MPEG2 W99999999 H99999999 F25:1 C420" "YUV4MPEG2 W8 H6 F25:1 C420 FRAME"; do
+    { printf '%s\n' "$bad"; head -c 100 /dev/zero; } > $T/bad.y4m
+    for B in $ASAN $TSAN; do
+        $B -i $T/bad.y4m -o $T/bad_out.y4m -m rife-v4.6 > $T/log.txt 2>&1; rc=$?
+        [ $rc -eq 1 ] || { echo "   $(basename $B) malformed header '$bad': rc $rc (a refusal is 1)"; FAIL=1; tail -20 $T/log.txt; }
+    done
+done
+head -c 300 $T/odd.y4m > $T/bad.y4m
+for B in $ASAN $TSAN; do
+    $B -i $T/bad.y4m -o $T/bad_out.y4m -m rife-v4.6 > $T/log.txt 2>&1; rc=$?
+    [ $rc -eq 1 ] && grep -q truncated $T/log.txt || { echo "   $(basename $B) truncated file: rc $rc"; FAIL=1; tail -20 $T/log.txt; }
+done
+echo "   malformed headers and a truncated file: refused with exit status 1 by both binaries"
 echo "== 4. single-pair mode, error paths (missing file, size mismatch, bad extension) under ASan + UBSan"
 rm -rf $T/out; mkdir -p $T/out
 run "asan pair" $ASAN -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/o.png -m rife-v4.6 -s 0.3
