@@ -174,6 +174,41 @@ int rife_hip_process_device_batch_px(const rife_hip_t* r, int n, const void* con
  * out_rgb then points at rife_hip_frame_bytes() bytes. */
 int rife_hip_frame_upload_px(const rife_hip_t* r, const void* pixels, int w, int h, int pixfmt, rife_hip_frame_t** frame);
 
+/* ---- strides and planes: frames as video producers hand them over --------------------------------------------------------------------------------------
+ * The _px calls take a tightly packed frame with its planes glued one after the other.  An AVFrame has data[] and linesize[], a VapourSynth / AviSynth frame one
+ * allocation per plane with padded rows, a decoder surface is pitched NV12 / P010 in device memory, a crop or tile is a window with its parent's pitch: an image
+ * descriptor names each plane and the BYTES from one of its rows to the next, and the image calls read and write those planes in place. */
+typedef struct rife_hip_image {
+    int w, h, pixfmt;        /* pixfmt as for the _px calls, colour bits included */
+    void* plane[3];          /* RGB8 / RGB10_U16 / A2B10G10R10 / RGBA8: plane[0];  NV12 / P010: Y, CbCr;  I420 / I420P10: Y, Cb, Cr */
+    ptrdiff_t pitch[3];      /* BYTES from one row of the plane to the next */
+} rife_hip_image_t;
+/* Entries of plane[] and pitch[] that the format does not use are ignored.  YV12 and its 10-bit form need no format of their own: the caller swaps plane[1] and
+ * plane[2] of an I420 / I420P10 image.
+ * Rules (the check function below states them, and every image call repeats them before it touches anything; a violation is -RIFE_HIP_EINVAL with a message):
+ *   w, h > 0 and pixfmt is one the _px calls accept; every plane the format has is non-NULL; each pitch is positive, at least the plane's row bytes, at most
+ *   INT32_MAX and a multiple of the plane's element size (1 for the u8 formats, 2 for the u16 formats, 4 for A2B10G10R10); each plane pointer is aligned to that
+ *   element size.  A negative pitch (bottom-up rows) is refused.  The three images of one call agree in w, h and pixfmt.
+ *   Output planes must not overlap each other or the inputs (documented, not checked).
+ * Contract: an image call is, byte for byte, the _px call on the same samples repacked tight, with the result unpacked into `out`.  It writes only the first
+ * row-bytes bytes of each of the h (chroma: ch) rows of each output plane; the gap between rows and everything around the window keep their bytes.  Timestep
+ * 0 / 1 return the first / second frame's canonical samples (see the formats above) into the strided output.
+ * Device planes are read and written by the pre- and post-processing kernels directly (no staging copy); host planes are copied row by row (2-D copies) into and
+ * out of the staging buffers of the tight path, which then runs unchanged.
+ * Scope: that of the _px formats - model family rife-v4.6, plain mode, every format and size served there; any other family or mode returns -RIFE_HIP_ENOSYS
+ * with a message that names it, before anything is written.  Exception: an RGB8 image that is tight (pitch[0] == 3 * w) IS the call without the suffix and is
+ * served wherever that is.  The opt-in graph replay does not apply.  Out of scope: a batch call on images, NV21, negative pitches, 4:2:2 / 4:4:4. */
+int rife_hip_image_check(const rife_hip_image_t* img);                   /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
+size_t rife_hip_image_row_bytes(int w, int pixfmt, int plane);            /* host only: bytes of one row of that plane; 0 for a plane the format does not have */
+/* planes in host memory */
+int rife_hip_process_image(const rife_hip_t* r, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out);
+/* planes in device memory; stream semantics as for the device _px call (NULL = the engine's own stream, synchronised before returning) */
+int rife_hip_process_device_image(const rife_hip_t* r, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out,
+                                  void* hip_stream);
+/* stream mode: upload host planes once (the resident frame is tight, in the image's format), write a result into strided host planes */
+int rife_hip_frame_upload_image(const rife_hip_t* r, const rife_hip_image_t* img, rife_hip_frame_t** frame);
+int rife_hip_process_frames_image(const rife_hip_t* r, const rife_hip_frame_t* frame0, const rife_hip_frame_t* frame1, float timestep, const rife_hip_image_t* out);
+
 const char* rife_hip_last_error(void);
 
 /* ---- measurement hooks (bench.py / profiles) ---------------------------------------------------------------

@@ -56,6 +56,15 @@ int rife_hip_op_warp(int gpuid, const float* image_chw, const float* flow_chw, i
 int rife_hip_op_yuv_to_rgb10(int gpuid, const void* yuv, int w, int h, int pixfmt, uint32_t* out_padded);
 int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int h, int pixfmt, void* yuv_out);
 
+/* The pitched kernels alone (csrc/planes.h), on an image whose planes are in HOST memory: the call uploads every plane, gaps between rows included, into one
+ * device allocation with the same pitches and the same pointer alignment modulo 16, so the form the host picks is the one it would pick for the caller's planes.
+ * force_scalar: 0 = the host's choice, 1 = the scalar form, 2 (image_to_resident only, a TIGHT image) = the tight kernels of the _px path, the reference.
+ * image_to_resident: the pre-processing kernel -> the resident form, hp x wp dwords (depth 8: R | G << 8 | B << 16 | A << 24, depth 10: R | G << 10 | B << 20).
+ * resident_to_image: tight_frame = what the pass leaves behind - for a 4:2:0 format h x w A2B10G10R10 dwords (k_postproc_yuv's input), for an RGB format the tight
+ * frame of that format (the store kernel's input); the planes come back with every byte the kernel did not write as it went in. */
+int rife_hip_op_image_to_resident(int gpuid, const rife_hip_image_t* host_img, int force_scalar, uint32_t* out_padded);
+int rife_hip_op_resident_to_image(int gpuid, const uint32_t* tight_frame, const rife_hip_image_t* host_img_out, int force_scalar);
+
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */
 int rife_hip_pool_state(const rife_hip_t* r, int* pooled, int* leased, int* high_water);

@@ -32,6 +32,7 @@ C_ABI_SYMBOLS = [
     "rife_hip_host_alloc", "rife_hip_host_free", "rife_hip_host_register", "rife_hip_host_unregister",
     "rife_hip_graph_check", "rife_hip_param_hash",
     "rife_hip_frame_bytes", "rife_hip_process_px", "rife_hip_process_device_px", "rife_hip_process_device_batch_px", "rife_hip_frame_upload_px",
+    "rife_hip_image_check", "rife_hip_image_row_bytes", "rife_hip_process_image", "rife_hip_process_device_image", "rife_hip_frame_upload_image", "rife_hip_process_frames_image",
 ]
 # pixel formats at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*)
 PIX_RGB8, PIX_RGB10_U16, PIX_A2B10G10R10 = 0, 1, 2
@@ -40,9 +41,16 @@ PIX_RGBA8 = 4      # 3 is reserved
 PIX_NV12, PIX_I420, PIX_P010, PIX_I420P10 = 16, 17, 18, 19      # 5 .. 15 are reserved
 CSP_BT709, CSP_BT601, CSP_BT2020NCL = 0 << 8, 1 << 8, 2 << 8
 CSP_FULL = 1 << 12
+ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
-                    "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv"]
+                    "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
+                    "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image"]
+
+
+class rife_hip_image(ctypes.Structure):
+    """rife_hip_image_t of include/rife_hip.h: a frame as a pointer and a pitch in BYTES per plane."""
+    _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("pixfmt", ctypes.c_int), ("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_ssize_t * 3)]
 
 
 def build(force=False):
@@ -96,7 +104,17 @@ def _load(path, with_test_surface):
     L.rife_hip_process_device_px.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, vp]
     L.rife_hip_process_device_batch_px.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
     L.rife_hip_frame_upload_px.argtypes = [vp, vp, ci, ci, ci, vp]
+    ip = ctypes.POINTER(rife_hip_image)
+    L.rife_hip_image_check.argtypes = [ip]
+    L.rife_hip_image_row_bytes.restype = ctypes.c_size_t
+    L.rife_hip_image_row_bytes.argtypes = [ci, ci, ci]
+    L.rife_hip_process_image.argtypes = [vp, ip, ip, cf, ip]
+    L.rife_hip_process_device_image.argtypes = [vp, ip, ip, cf, ip, vp]
+    L.rife_hip_frame_upload_image.argtypes = [vp, ip, vp]
+    L.rife_hip_process_frames_image.argtypes = [vp, vp, vp, cf, ip]
     if with_test_surface:
+        L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
+        L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
         L.rife_hip_v4_extract_flow.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp]
         L.rife_hip_v4_flow_dims.argtypes = [vp, ci, ci, ci, vp, vp, vp]
         L.rife_hip_v4_tap.argtypes = [vp, vp, vp, ci, ci, cf, ci, ci, vp, ci, vp]
@@ -271,6 +289,81 @@ def _pix_of(image, pixfmt=None):
     return pixfmt
 
 
+_ELEM = {PIX_RGB8: 1, PIX_RGB10_U16: 2, PIX_A2B10G10R10: 4, PIX_RGBA8: 1, PIX_NV12: 1, PIX_I420: 1, PIX_P010: 2, PIX_I420P10: 2}
+
+
+def image_row_bytes(w, pixfmt, plane):
+    """rife_hip_image_row_bytes: bytes of one row of that plane of a frame w pixels wide (0 for a plane the format does not have)."""
+    return int(lib().rife_hip_image_row_bytes(int(w), int(pixfmt), int(plane)))
+
+
+def image_check(img):
+    """rife_hip_image_check (host only): raises RifeError with the fault."""
+    _check(lib().rife_hip_image_check(ctypes.byref(img)), "image_check")
+
+
+def device_image(w, h, pixfmt, planes):
+    """A rife_hip_image from a list of (pointer, pitch in bytes) per plane - for process_device_image() (device pointers) or any of the C calls."""
+    im = rife_hip_image(int(w), int(h), int(pixfmt))
+    for i, (ptr, pitch) in enumerate(planes):
+        im.plane[i] = int(ptr) or None
+        im.pitch[i] = int(pitch)
+    return im
+
+
+def _rows_strided(a):
+    """True if the pixels of each row of `a` are contiguous and the rows follow each other at a positive stride: what a crop big[y0:y1, x0:x1], an array with
+    padded rows or a plane view of a video frame is.  (A one-row array has no row stride to speak of; its own width stands in.)"""
+    if not isinstance(a, np.ndarray) or a.ndim not in (2, 3) or a.size == 0:
+        return False
+    inner = a.itemsize
+    for n, st in zip(a.shape[:0:-1], a.strides[:0:-1]):
+        if n > 1 and st != inner:
+            return False
+        inner *= n
+    return a.shape[0] == 1 or a.strides[0] >= inner
+
+
+def _pitch(a):
+    return a.strides[0] if a.shape[0] > 1 else max(a.strides[0], a.itemsize * int(np.prod(a.shape[1:])))
+
+
+def image_of(a, pixfmt=None):
+    """The descriptor process() / upload() pass for a frame array WITHOUT copying it, or None where they fall back to a contiguous copy as they always did:
+    an RGB-format array ((h, w, 3) uint8 / uint16, (h, w) uint32, (h, w, 4) uint8) whose rows are strided but whose pixels are contiguous, with a pitch and a
+    base address the format's element size divides."""
+    px = _pix_of(a, pixfmt)
+    if px is None:
+        px = PIX_RGB8
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+            return None
+    if not _rows_strided(a):
+        return None
+    pitch = _pitch(a)
+    if pitch % _ELEM[px] or a.ctypes.data % _ELEM[px] or pitch > 0x7fffffff:
+        return None
+    im = device_image(a.shape[1], a.shape[0], px, [(a.ctypes.data, pitch)])
+    im._keep = a      # the descriptor holds raw addresses: the array lives as long as it does
+    return im
+
+
+def planes_image(planes, w, h, pixfmt, what="planes", writable=False):
+    """The descriptor of a 4:2:0 frame given as a tuple of 2-D arrays, each with its own base and row stride: (h, w) luma and, cw = (w + 1) // 2, ch = (h + 1) // 2,
+    one (ch, 2 * cw) array of interleaved pairs (NV12, P010) or two (ch, cw) arrays Cb, Cr (I420, I420P10; swap them for YV12).  Raises ValueError."""
+    base = _yuv_base(pixfmt)
+    dt = yuv_dtype(pixfmt)
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    shapes = [(h, w), (ch, 2 * cw)] if base in (PIX_NV12, PIX_P010) else [(h, w), (ch, cw), (ch, cw)]
+    if w <= 0 or h <= 0 or len(planes) != len(shapes):
+        raise ValueError("%s: %d arrays of shapes %s" % (what, len(shapes), shapes))
+    for a, shp in zip(planes, shapes):
+        if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shp or not _rows_strided(a) or (writable and not a.flags.writeable):
+            raise ValueError("%s: each plane is a%s %s array of shape %s whose rows are contiguous" % (what, " writable" if writable else "", np.dtype(dt).name, shp))
+    im = device_image(w, h, pixfmt, [(a.ctypes.data, _pitch(a)) for a in planes])
+    im._keep = tuple(planes)
+    return im
+
+
 class Frame:
     """A frame resident in device memory (rife_hip_frame_t): upload once, use as either side of any number of pairs."""
 
@@ -315,6 +408,11 @@ class RIFE:
         arrays' dtype or by pixfmt=; the result has the inputs' format.
         Alpha (rife-v4.6, plain mode): (h, w, 4) uint8 RGBA arrays (RGBA8); the colour bytes are those of the RGB call, alpha is warped and blended with it."""
         px = _pix_of(in0image, pixfmt)
+        strided = self._strided(in0image, in1image, outimage, px)
+        if strided is not None:
+            done = strided(float(timestep))
+            if done is not None:
+                return done      # else: this engine does not serve strided images (another family, -x / -z / -u) and wrote nothing - the contiguous copies below, as ever
         if px is not None:
             if _pix_of(in1image, px) != px or in1image.shape != in0image.shape:
                 raise ValueError("both frames must have the same pixel format and size")
@@ -335,6 +433,59 @@ class RIFE:
             raise ValueError("outimage must be a writable contiguous (h, w, 3) uint8 array of the frames' size")
         _check(self._L.rife_hip_process(self._h, _p(a), _p(b), w, h, float(timestep), _p(out)), "process", self._L)
         return out
+
+    def _strided(self, in0image, in1image, outimage, px):
+        """process() without a copy: some frame of the call is not contiguous, and every one of them is an array whose rows are strided but whose pixels are
+        contiguous (image_of) of one format and size.  Returns the call to make, or None: today's path (contiguous copies)."""
+        arrs = [in0image, in1image] + ([outimage] if outimage is not None else [])
+        if not all(isinstance(x, np.ndarray) for x in arrs) or all(x.flags.c_contiguous for x in arrs):
+            return None
+        if any(x.shape != in0image.shape or x.dtype != in0image.dtype for x in arrs) or (outimage is not None and not outimage.flags.writeable):
+            return None
+        imgs = [image_of(x, px) for x in arrs]
+        if any(im is None for im in imgs):
+            return None
+        out = outimage if outimage is not None else np.empty(in0image.shape, in0image.dtype)
+        if outimage is None:
+            imgs.append(image_of(out, px))
+
+        def call(timestep):
+            rc = self._L.rife_hip_process_image(self._h, ctypes.byref(imgs[0]), ctypes.byref(imgs[1]), timestep, ctypes.byref(imgs[2]))
+            if rc == -ENOSYS:      # refused before anything was written (include/rife_hip.h): the caller falls back
+                return None
+            _check(rc, "process_image", self._L)
+            return out
+        return call
+
+    def process_planes(self, planes0, planes1, timestep, pixfmt, out=None):
+        """4:2:0 frames as tuples of 2-D plane arrays, each with its own base and row stride (what VapourSynth's plane views or an AVFrame's data / linesize
+        are; shapes: planes_image()).  Nothing is repacked on the host.  out: a tuple of writable plane arrays to fill, or None; returns the output planes."""
+        h, w = planes0[0].shape if len(planes0) and isinstance(planes0[0], np.ndarray) and planes0[0].ndim == 2 else (0, 0)
+        a = planes_image(planes0, w, h, pixfmt, "planes0"); b = planes_image(planes1, w, h, pixfmt, "planes1")
+        if out is None:
+            out = tuple(np.empty(p.shape, p.dtype) for p in planes0)
+        o = planes_image(out, w, h, pixfmt, "out", writable=True)
+        _check(self._L.rife_hip_process_image(self._h, ctypes.byref(a), ctypes.byref(b), float(timestep), ctypes.byref(o)), "process_image", self._L)
+        return tuple(out)
+
+    def upload_planes(self, planes, pixfmt):
+        """Stream mode for a 4:2:0 frame given as plane arrays (process_planes); the resident frame is that of upload_yuv() on the packed frame."""
+        h, w = planes[0].shape if len(planes) and isinstance(planes[0], np.ndarray) and planes[0].ndim == 2 else (0, 0)
+        a = planes_image(planes, w, h, pixfmt, "planes")
+        f = ctypes.c_void_p()
+        _check(self._L.rife_hip_frame_upload_image(self._h, ctypes.byref(a), ctypes.byref(f)), "frame_upload_image", self._L)
+        return Frame(f, int(w), int(h), self._L, int(pixfmt))
+
+    def process_frames_image(self, frame0, frame1, timestep, out):
+        """process_frames() into a strided result: `out` is a rife_hip_image (image_of / planes_image / device_image on HOST memory) of the frames' size and format."""
+        if frame0._f is None or frame1._f is None:
+            raise ValueError("frame was released")
+        _check(self._L.rife_hip_process_frames_image(self._h, frame0._f, frame1._f, float(timestep), ctypes.byref(out)), "process_frames_image", self._L)
+
+    def process_device_image(self, img0, img1, timestep, out, stream=None):
+        """rife_hip_process_device_image: three rife_hip_image descriptors of DEVICE planes (device_image(w, h, pixfmt, [(ptr, pitch), ...])), read and written in
+        place by the pitched kernels; enqueues on `stream` (hipStream_t as int; None = the engine's own stream, synchronised before returning)."""
+        _check(self._L.rife_hip_process_device_image(self._h, ctypes.byref(img0), ctypes.byref(img1), float(timestep), ctypes.byref(out), stream), "process_device_image", self._L)
 
     def process_yuv(self, buf0, buf1, w, h, timestep, pixfmt, out=None):
         """4:2:0 frames in and out (rife-v4.6, plain mode): flat uint8 (NV12, I420) or uint16 (P010, I420P10) arrays of yuv_frame_bytes(w, h, pixfmt) bytes;
@@ -357,6 +508,13 @@ class RIFE:
         """Stream mode: copy one (h, w, 3) uint8 frame to the device and keep it there (deep colour: a uint16 (h, w, 3) or uint32 (h, w)
         array, see process())."""
         px = _pix_of(image, pixfmt)
+        im = image_of(image, px) if isinstance(image, np.ndarray) and not image.flags.c_contiguous else None
+        if im is not None:      # rows strided, pixels contiguous: uploaded from where it lies
+            f = ctypes.c_void_p()
+            rc = self._L.rife_hip_frame_upload_image(self._h, ctypes.byref(im), ctypes.byref(f))
+            if rc != -ENOSYS:      # -ENOSYS: an engine that does not serve strided images - the contiguous copy below, as ever
+                _check(rc, "frame_upload_image", self._L)
+                return Frame(f, im.w, im.h, self._L, im.pixfmt)
         if px is not None:
             a = np.ascontiguousarray(image)
             f = ctypes.c_void_p()
@@ -563,6 +721,20 @@ def op_yuv_to_rgb10(buf, w, h, pixfmt, gpuid=0):
     out = np.empty(((h + 31) // 32 * 32, (w + 31) // 32 * 32), np.uint32)
     _check(testlib().rife_hip_op_yuv_to_rgb10(gpuid, _p(a), int(w), int(h), int(pixfmt), _p(out)), "op_yuv_to_rgb10", testlib())
     return out
+
+
+def op_image_to_resident(img, force_scalar=0, gpuid=0):
+    """The pitched pre-processing kernel alone (force_scalar = 2: the tight kernel of the _px path on a tight image) on a rife_hip_image of HOST planes ->
+    the resident form, (hp, wp) uint32."""
+    out = np.empty(((img.h + 31) // 32 * 32, (img.w + 31) // 32 * 32), np.uint32)
+    _check(testlib().rife_hip_op_image_to_resident(gpuid, ctypes.byref(img), int(force_scalar), _p(out)), "op_image_to_resident", testlib())
+    return out
+
+
+def op_resident_to_image(tight, img, force_scalar=0, gpuid=0):
+    """The pitched output kernel alone: `tight` (4:2:0: (h, w) uint32 A2B10G10R10; RGB formats: the tight frame of the format) -> the HOST planes of `img`."""
+    a = np.ascontiguousarray(tight)
+    _check(testlib().rife_hip_op_resident_to_image(gpuid, _p(a), ctypes.byref(img), int(force_scalar)), "op_resident_to_image", testlib())
 
 
 def op_rgb10_to_yuv(packed, pixfmt, gpuid=0):

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <array>
 #include <map>
 #include <memory>
@@ -38,6 +39,8 @@
 #include "conv_img.h"
 #include "elementwise.h"
 #include "yuv.h"
+#include "planes.h"
+#include "image_check.h"
 #include "elementwise_v2.h"
 #include "stem_fused.h"
 #include "stem_fused_v2.h"
@@ -63,3 +66,4 @@
 #include "engine_v2.h"
 #include "engine_v1.h"
 #include "engine_abi.h"
+#include "engine_image.h"

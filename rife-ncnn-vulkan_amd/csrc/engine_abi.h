@@ -151,23 +151,22 @@ static int process_common(const rife_hip* E, int w, int h, float timestep) {
 
 // ---- deep colour and alpha (include/rife_hip.h RIFE_HIP_PIX_*) ----
 // The 10-bit formats and RGBA8 are served by the plain rife-v4.6 schedule only; everything else is refused BEFORE anything is written or enqueued.
+// nullptr = the plain rife-v4.6 schedule; otherwise the family or mode by name (the words of every "served for ... only" refusal)
+static const char* not_plain_v46(const rife_hip* E) {
+    return E->v1 ? "model family rife (v1: rife, rife-HD, rife-UHD, rife-anime)" : (!E->v4 && E->v3) ? "model family rife-v3.x" : !E->v4 ? "model family rife-v2.x"
+           : E->v40 ? "model family rife-v4 (4.0)" : E->tta ? "TTA mode (-x)" : E->tta_temporal ? "temporal TTA mode (-z)" : E->uhd ? "UHD mode (-u)" : nullptr;
+}
 static int pixfmt_supported(const rife_hip* E, int pixfmt) {
     if (pixfmt == RIFE_HIP_PIX_RGB8) return 0;
-    const char* what = E->v1 ? "model family rife (v1: rife, rife-HD, rife-UHD, rife-anime)" : (!E->v4 && E->v3) ? "model family rife-v3.x" : !E->v4 ? "model family rife-v2.x"
-                       : E->v40 ? "model family rife-v4 (4.0)" : E->tta ? "TTA mode (-x)" : E->tta_temporal ? "temporal TTA mode (-z)" : E->uhd ? "UHD mode (-u)" : nullptr;
+    const char* what = not_plain_v46(E);
     if (!what) return 0;
     return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : pix_yuv(pixfmt) ? "4:2:0 YUV" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
 }
 // argument checks of the _px entry points that need no engine; then "no HIP device at all" before anything looks at the engine
 // a pixfmt argument = format | colour description (include/rife_hip.h RIFE_HIP_CSP_*): both must be something the library knows
-static int pixfmt_check(int pixfmt) {
-    const int csp = pixfmt & ~0xff;
-    if (pixfmt < 0 || frame_bytes(1, 1, pix_base(pixfmt)) == 0 || (csp & ~0x1f00)) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
-    if (!pix_yuv(pixfmt)) return csp ? fail(RIFE_HIP_EINVAL, "a colour description (RIFE_HIP_CSP_*) goes with a 4:2:0 YUV format, not with an RGB format") : 0;
-    if (((csp >> 8) & 15) > 2) return fail(RIFE_HIP_EINVAL, "unknown colour matrix");
-    if ((csp & RIFE_HIP_CSP_FULL) && yuv_depth(pix_base(pixfmt)) == 10)
-        return fail(RIFE_HIP_EINVAL, "full-range YUV is served at 8 bits only (the 10-bit full-range round trip through 10-bit RGB is not exact)");
-    return 0;
+static int pixfmt_check(int pixfmt) {      // the rules and their words: csrc/image_check.h, shared with rife_hip_image_check
+    const char* fault = rife_img::pixfmt_fault(pixfmt);
+    return fault ? fail(RIFE_HIP_EINVAL, fault) : 0;
 }
 static int px_precheck(int pixfmt, bool ptrs_ok, int w, int h) {
     int rc;

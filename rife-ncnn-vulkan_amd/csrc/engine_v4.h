@@ -441,13 +441,20 @@ static int run_flow_update(const rife_hip& E, Ctx& c, int b) {
 }
 
 // RIFE::process_v4, non-TTA branch (rife.cpp:2931-3173) on device-resident frames.
-static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t* d_in1, float timestep, uint8_t* d_out, const float* tsp = nullptr) {
+// pio != null (an image call, engine_image.h): the frames are the caller's strided planes, read and written in place by the pitched kernels of planes.h; d_in0 / d_in1 are
+// unused and d_out is the tight frame an RGB format's quantising kernels write
+static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t* d_in1, float timestep, uint8_t* d_out, const float* tsp = nullptr, const PlaneIO* pio = nullptr) {
     hipStream_t st = c.stream;
     int rc;
     {
         Timed t(E.prof, "preproc", 0, st);
-        launch_preproc(st, d_in0, c.w, c.h, c.img0, c.wp, c.hp, c.pixfmt);
-        launch_preproc(st, d_in1, c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt);
+        if (pio) {      // an image call: the caller's planes with their pitches (planes.h)
+            launch_preproc_planes(st, pio->in0, c.w, c.h, c.img0, c.wp, c.hp, c.pixfmt);
+            launch_preproc_planes(st, pio->in1, c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt);
+        } else {
+            launch_preproc(st, d_in0, c.w, c.h, c.img0, c.wp, c.hp, c.pixfmt);
+            launch_preproc(st, d_in1, c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt);
+        }
         HIPCHK(hipGetLastError());
     }
     if (c.pixfmt && E.v40) return fail(RIFE_HIP_ENOSYS, "10-bit and RGBA frames are served for model family rife-v4.6 only, not rife-v4");
@@ -491,7 +498,8 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
     }
     if (pix_yuv(c.pixfmt)) {
         Timed t(E.prof, "postproc_yuv", 0, st);
-        launch_postproc_yuv(st, c.yuv_rgb, c.w, c.h, caller_out, c.pixfmt);
+        if (pio) launch_postproc_yuv_planes(st, c.yuv_rgb, c.w, c.h, pio->out, c.pixfmt);
+        else launch_postproc_yuv(st, c.yuv_rgb, c.w, c.h, caller_out, c.pixfmt);
         HIPCHK(hipGetLastError());
     }
     return 0;

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "ncnn_mat.h"
+#include "../../include/rife_hip.h"      // rife_hip_image_t for the image calls below
 
 struct rife_hip;
 struct rife_hip_frame;
@@ -38,6 +39,20 @@ public:
     // A frame of upload_yuv() goes through process(frame0, frame1, timestep, outimage) above, whose outimage.data then points at a frame of that size.
     int process_yuv(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt) const;
     rife_hip_frame* upload_yuv(const void* frame, int w, int h, int pixfmt) const;
+
+    // Extension, not in the reference (include/rife_hip.h "strides and planes"): frames as an AVFrame or a VapourSynth frame holds them - a pointer and a
+    // pitch in BYTES per plane, any of the _px formats.  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
+    // program that never calls them links against an engine without those two symbols as before; the message of a failure is rife_hip_last_error()).
+    int process_image(const rife_hip_image_t& in0, const rife_hip_image_t& in1, float timestep, const rife_hip_image_t& out) const
+    {
+        return engine ? rife_hip_process_image(engine, &in0, &in1, timestep, &out) : -RIFE_HIP_ENODEV;
+    }
+    rife_hip_frame* upload_image(const rife_hip_image_t& image) const
+    {
+        rife_hip_frame* f = 0;
+        if (engine) rife_hip_frame_upload_image(engine, &image, &f);
+        return f;
+    }
 
 private:
     RIFE(const RIFE&);

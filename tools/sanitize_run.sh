@@ -163,6 +163,9 @@ rm -rf $T/out; mkdir -p $T/out
 run "asan pair" $ASAN -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/o.png -m rife-v4.6 -s 0.3
 $ASAN -0 $T/in_png/000.png -1 $T/nothing.png -o $T/out/o2.png -m rife-v4.6 > $T/log.txt 2>&1; rc=$?; echo "   asan missing input: rc $rc (sanitizer exit codes are 99 / 98)"; [ $rc -ge 98 ] && [ $rc -le 99 ] && FAIL=1
 $ASAN -0 $T/in_png/000.png -1 $T/in_big/000.png -o $T/out/o3.png -m rife-v4.6 > $T/log.txt 2>&1; rc=$?; echo "   asan size mismatch: rc $rc"; [ $rc -ge 98 ] && [ $rc -le 99 ] && FAIL=1
+echo "== 5. rife_hip_image_check's rules (csrc/image_check.h, host only) over refusing and accepting descriptors, a program of its own under ASan + UBSan"
+$ROOT/rife-ncnn-vulkan_amd/image-check-asan > $T/log.txt 2>&1; rc=$?
+echo "   image-check-asan: rc $rc, $(tail -1 $T/log.txt)"; [ $rc -ne 0 ] && { FAIL=1; tail -30 $T/log.txt; }
 rm -rf $T
 echo "== result: $([ $FAIL -eq 0 ] && echo CLEAN || echo FAILED)"
 exit $FAIL
