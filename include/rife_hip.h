@@ -138,33 +138,43 @@ void rife_hip_frame_release(rife_hip_frame_t* frame);
 #define RIFE_HIP_PIX_I420         17  /* u8: planes Y w*h, Cb cw*ch, Cr cw*ch (what Y4M C420* holds) */
 #define RIFE_HIP_PIX_P010         18  /* u16 little-endian, the code in the HIGH 10 bits, NV12 plane layout; low bits ignored on input, written as zero */
 #define RIFE_HIP_PIX_I420P10      19  /* u16 little-endian, the code in the LOW 10 bits, I420 plane layout (what Y4M C420p10 holds); a larger value is read as 1023 */
-/* The colour description is OR-ed into pixfmt (4:2:0 formats only; on an RGB format any of these bits is -RIFE_HIP_EINVAL):
+/* 4:2:2 and 4:4:4 (mezzanine and camera material; screen capture, animation masters, chains that upsampled chroma): 16 * class + 2 * (10 bits) + (planar), class 1 =
+ * 4:2:0 above, 2 = 4:2:2, 3 = 4:4:4.  Planar only: 32, 34, 48, 50 (the semi-planar slots NV16 / P210 / NV24 / P410) are unknown formats, as are 20 .. 31 and 52 up.
+ * Chroma planes have h rows (not ch); YV16 / YV24: swap plane[1] and plane[2] of an image. */
+#define RIFE_HIP_PIX_I422         33  /* u8: planes Y w*h, Cb cw*h, Cr cw*h (what Y4M C422 holds) */
+#define RIFE_HIP_PIX_I422P10      35  /* u16 little-endian, the code in the LOW 10 bits, I422 plane layout; a larger value is read as 1023 */
+#define RIFE_HIP_PIX_I444         49  /* u8: planes Y, Cb, Cr, each w*h */
+#define RIFE_HIP_PIX_I444P10      51  /* u16 little-endian, the code in the LOW 10 bits, I444 plane layout; a larger value is read as 1023 */
+/* The colour description is OR-ed into pixfmt (YUV formats only; on an RGB format any of these bits is -RIFE_HIP_EINVAL):
  * bits 8-11 the matrix (an unknown one: -RIFE_HIP_EINVAL), bit 12 the range (limited is the default). */
 #define RIFE_HIP_CSP_BT709        (0 << 8)   /* the default */
 #define RIFE_HIP_CSP_BT601        (1 << 8)
 #define RIFE_HIP_CSP_BT2020NCL    (2 << 8)
 #define RIFE_HIP_CSP_FULL         (1 << 12)  /* full range ("JPEG" levels); 8-bit formats only: with a 10-bit format -RIFE_HIP_EINVAL (its round trip below is not exact) */
-/* A 4:2:0 call is, byte for byte, the A2B10G10R10 call on the converted frames, converted back:
+/* A YUV call is, byte for byte, the A2B10G10R10 call on the converted frames, converted back:
  *     out = rgb10_to_yuv(process_px(yuv_to_rgb10(in0), yuv_to_rgb10(in1), timestep, A2B10G10R10))
- * with INTEGER conversions (tests/yuv_ref.py states them in numpy, csrc/yuv.h in HIP; the two agree bit for bit):
+ * with INTEGER conversions (tests/yuv_ref.py and, for 4:2:2 / 4:4:4, tests/chroma_ref.py state them in numpy, csrc/yuv.h in HIP; they agree bit for bit):
  *   coefficients  the matrix's real coefficients times 1023 / range (in) or range / 1023 (out), rounded to Q16; range = 219 s luma, 224 s chroma (limited),
  *                 255 both (full); s = 1 at 8 bits, 4 at 10.  Products are summed in integers, + 0x8000, arithmetic shift right by 16.
  *   in            subtract the offsets (16 s and 128 s; full range 0 and 128 s), apply the matrix, clamp to 0..1023.  The chroma of a pixel is the sample of
  *                 its 2x2 block (replication).  The padding to 32n is zero RGB, as everywhere.
  *   out           Y per pixel; Cb, Cr from the SUM of the RGB codes of the block's pixels inside the frame (n = 4, 2 or 1), shifted by 16 + log2 n with the
  *                 rounding constant scaled alike; add the offsets, clamp to 0..255 / 0..1023.
+ *   4:2:2, 4:4:4  coefficients, offsets, clamps and colour bits are the same; only the block changes.  4:2:2: the chroma of a pixel is the sample of its 2x1 block, and
+ *                 Cb, Cr come from the sum over the block's pixels inside the frame (n = 2, or 1 in the last column of an odd width).  4:4:4: every pixel has its
+ *                 own chroma and n = 1 everywhere.
  * YUV -> 10-bit RGB -> YUV is the identity on every sample whose RGB did not clamp, at both depths (half a code of RGB error weighs less than half a code of
  * any output), which is why 8- AND 10-bit video ride the engine's depth-10 path unchanged, and a difference of one RGB code moves no Y, Cb, Cr by more than
  * one code, which carries the engine's 1-code contract across.
  * Chroma siting: replication up and the box average down are each other's inverse on block-constant chroma and have no net shift whatever the stream's
  * siting is; chroma siting tags (Y4M C420jpeg / C420mpeg2 / C420paldv) are ignored.
- * timestep 0 / 1 return the first / second frame's samples (P010: low bits cleared; I420P10: clamped to 1023).  Input and output of a call share one format and
+ * timestep 0 / 1 return the first / second frame's samples (P010: low bits cleared; I420P10, I422P10, I444P10: clamped to 1023).  Input and output of a call share one format and
  * one colour description; rife_hip_process_frames refuses two frames that differ in either.
  * Scope: that of the 10-bit formats - model family rife-v4.6, plain mode, every frame size; any other family or mode returns -RIFE_HIP_ENOSYS with a message
- * that names it, before anything is written; the opt-in graph replay does not apply.  Out of scope: rife_hip_process_batch (the host batch), 4:2:2 / 4:4:4,
- * interlaced chroma. */
+ * that names it, before anything is written; the opt-in graph replay does not apply.  Out of scope: rife_hip_process_batch (the host batch), semi-planar
+ * 4:2:2 / 4:4:4, 12-bit samples, planar RGB, alpha planes, interlaced chroma. */
 
-size_t rife_hip_frame_bytes(int w, int h, int pixfmt);      /* 0 for an unknown format or w, h <= 0; 4:2:0: (w*h + 2*cw*ch) samples; colour bits are ignored */
+size_t rife_hip_frame_bytes(int w, int h, int pixfmt);      /* 0 for an unknown format or w, h <= 0; YUV: (w*h + 2*cw*ch) samples (4:2:2: ch = h; 4:4:4: cw = w, ch = h); colour bits are ignored */
 int rife_hip_process_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt);
 int rife_hip_process_device_px(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt,
                                void* hip_stream);
@@ -180,7 +190,7 @@ int rife_hip_frame_upload_px(const rife_hip_t* r, const void* pixels, int w, int
  * descriptor names each plane and the BYTES from one of its rows to the next, and the image calls read and write those planes in place. */
 typedef struct rife_hip_image {
     int w, h, pixfmt;        /* pixfmt as for the _px calls, colour bits included */
-    void* plane[3];          /* RGB8 / RGB10_U16 / A2B10G10R10 / RGBA8: plane[0];  NV12 / P010: Y, CbCr;  I420 / I420P10: Y, Cb, Cr */
+    void* plane[3];          /* RGB8 / RGB10_U16 / A2B10G10R10 / RGBA8: plane[0];  NV12 / P010: Y, CbCr;  I420 / I422 / I444 and their P10 forms: Y, Cb, Cr */
     ptrdiff_t pitch[3];      /* BYTES from one row of the plane to the next */
 } rife_hip_image_t;
 /* Entries of plane[] and pitch[] that the format does not use are ignored.  YV12 and its 10-bit form need no format of their own: the caller swaps plane[1] and
@@ -191,13 +201,13 @@ typedef struct rife_hip_image {
  *   element size.  A negative pitch (bottom-up rows) is refused.  The three images of one call agree in w, h and pixfmt.
  *   Output planes must not overlap each other or the inputs (documented, not checked).
  * Contract: an image call is, byte for byte, the _px call on the same samples repacked tight, with the result unpacked into `out`.  It writes only the first
- * row-bytes bytes of each of the h (chroma: ch) rows of each output plane; the gap between rows and everything around the window keep their bytes.  Timestep
+ * row-bytes bytes of each of the h (4:2:0 chroma: ch) rows of each output plane; the gap between rows and everything around the window keep their bytes.  Timestep
  * 0 / 1 return the first / second frame's canonical samples (see the formats above) into the strided output.
  * Device planes are read and written by the pre- and post-processing kernels directly (no staging copy); host planes are copied row by row (2-D copies) into and
  * out of the staging buffers of the tight path, which then runs unchanged.
  * Scope: that of the _px formats - model family rife-v4.6, plain mode, every format and size served there; any other family or mode returns -RIFE_HIP_ENOSYS
  * with a message that names it, before anything is written.  Exception: an RGB8 image that is tight (pitch[0] == 3 * w) IS the call without the suffix and is
- * served wherever that is.  The opt-in graph replay does not apply.  Out of scope: a batch call on images, NV21, negative pitches, 4:2:2 / 4:4:4. */
+ * served wherever that is.  The opt-in graph replay does not apply.  Out of scope: a batch call on images, NV21, negative pitches. */
 int rife_hip_image_check(const rife_hip_image_t* img);                   /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
 size_t rife_hip_image_row_bytes(int w, int pixfmt, int plane);            /* host only: bytes of one row of that plane; 0 for a plane the format does not have */
 /* planes in host memory */

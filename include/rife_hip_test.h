@@ -51,8 +51,9 @@ int rife_hip_op_deconv4x4(int gpuid, const float* x_chw, int c, int h, int w, co
 /* rife.Warp (src/warp.cpp:96-168): image c x h x w, flow 2 x h x w. */
 int rife_hip_op_warp(int gpuid, const float* image_chw, const float* flow_chw, int c, int h, int w, float* out_chw);
 
-/* The two 4:2:0 kernels alone (csrc/yuv.h; pixfmt = a RIFE_HIP_PIX_NV12 .. I420P10 format with its colour description): k_preproc_yuv on one host frame ->
- * the resident form, hp x wp dwords R | G << 10 | B << 20, zero outside w x h; k_postproc_yuv on h x w A2B10G10R10 dwords -> one frame of `pixfmt`. */
+/* The YUV kernels alone (csrc/yuv.h; pixfmt = a RIFE_HIP_PIX_NV12 .. I420P10, I422, I422P10, I444 or I444P10 format with its colour description): k_preproc_yuv
+ * (4:2:2 / 4:4:4: k_preproc_yuvc) on one host frame -> the resident form, hp x wp dwords R | G << 10 | B << 20, zero outside w x h; k_postproc_yuv (k_postproc_yuvc)
+ * on h x w A2B10G10R10 dwords -> one frame of `pixfmt`. */
 int rife_hip_op_yuv_to_rgb10(int gpuid, const void* yuv, int w, int h, int pixfmt, uint32_t* out_padded);
 int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int h, int pixfmt, void* yuv_out);
 
@@ -60,7 +61,7 @@ int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int 
  * device allocation with the same pitches and the same pointer alignment modulo 16, so the form the host picks is the one it would pick for the caller's planes.
  * force_scalar: 0 = the host's choice, 1 = the scalar form, 2 (image_to_resident only, a TIGHT image) = the tight kernels of the _px path, the reference.
  * image_to_resident: the pre-processing kernel -> the resident form, hp x wp dwords (depth 8: R | G << 8 | B << 16 | A << 24, depth 10: R | G << 10 | B << 20).
- * resident_to_image: tight_frame = what the pass leaves behind - for a 4:2:0 format h x w A2B10G10R10 dwords (k_postproc_yuv's input), for an RGB format the tight
+ * resident_to_image: tight_frame = what the pass leaves behind - for a YUV format h x w A2B10G10R10 dwords (k_postproc_yuv's input), for an RGB format the tight
  * frame of that format (the store kernel's input); the planes come back with every byte the kernel did not write as it went in. */
 int rife_hip_op_image_to_resident(int gpuid, const rife_hip_image_t* host_img, int force_scalar, uint32_t* out_padded);
 int rife_hip_op_resident_to_image(int gpuid, const uint32_t* tight_frame, const rife_hip_image_t* host_img_out, int force_scalar);

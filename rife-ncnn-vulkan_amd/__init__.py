@@ -37,8 +37,11 @@ C_ABI_SYMBOLS = [
 # pixel formats at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*)
 PIX_RGB8, PIX_RGB10_U16, PIX_A2B10G10R10 = 0, 1, 2
 PIX_RGBA8 = 4      # 3 is reserved
-# 4:2:0 Y'CbCr (flat arrays: uint8 for NV12 / I420, uint16 for P010 / I420P10); the colour description is OR-ed into the format
+# Y'CbCr (flat arrays: uint8 for NV12 / I420, uint16 for P010 / I420P10); the colour description is OR-ed into the format
 PIX_NV12, PIX_I420, PIX_P010, PIX_I420P10 = 16, 17, 18, 19      # 5 .. 15 are reserved
+# 4:2:2 and 4:4:4, planar (16 * class + 2 * (10 bits) + planar; class 2 = 4:2:2, 3 = 4:4:4): Y (h, w), then Cb and Cr of (h, cw) / (h, w) samples
+PIX_I422, PIX_I422P10, PIX_I444, PIX_I444P10 = 33, 35, 49, 51
+_YUV_FORMATS = (PIX_NV12, PIX_I420, PIX_P010, PIX_I420P10, PIX_I422, PIX_I422P10, PIX_I444, PIX_I444P10)
 CSP_BT709, CSP_BT601, CSP_BT2020NCL = 0 << 8, 1 << 8, 2 << 8
 CSP_FULL = 1 << 12
 ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
@@ -236,18 +239,25 @@ def frame_bytes(w, h, pixfmt=PIX_RGB8):
 
 def _yuv_base(pixfmt):
     b = int(pixfmt) & 0xff
-    if int(pixfmt) < 0 or b not in (PIX_NV12, PIX_I420, PIX_P010, PIX_I420P10):
-        raise ValueError("%r is not a 4:2:0 YUV pixfmt" % (pixfmt,))
+    if int(pixfmt) < 0 or b not in _YUV_FORMATS:
+        raise ValueError("%r is not a YUV pixfmt" % (pixfmt,))
     return b
 
 
 def yuv_dtype(pixfmt):
-    return np.uint16 if _yuv_base(pixfmt) in (PIX_P010, PIX_I420P10) else np.uint8
+    return np.uint16 if _yuv_base(pixfmt) & 2 else np.uint8
+
+
+def yuv_chroma_dims(w, h, pixfmt):
+    """(cw, ch) of a w x h frame: 4:2:0 ((w + 1) // 2, (h + 1) // 2), 4:2:2 ((w + 1) // 2, h), 4:4:4 (w, h)."""
+    cls = _yuv_base(pixfmt) >> 4
+    return (w if cls == 3 else (w + 1) // 2), (h if cls >= 2 else (h + 1) // 2)
 
 
 def yuv_frame_bytes(w, h, pixfmt):
-    """Size of one w x h 4:2:0 frame: (w * h + 2 * cw * ch) samples of 1 or 2 bytes, cw = (w + 1) // 2, ch = (h + 1) // 2."""
-    return (w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)) * np.dtype(yuv_dtype(pixfmt)).itemsize
+    """Size of one w x h YUV frame: (w * h + 2 * cw * ch) samples of 1 or 2 bytes, cw, ch = yuv_chroma_dims(w, h, pixfmt)."""
+    cw, ch = yuv_chroma_dims(w, h, pixfmt)
+    return (w * h + 2 * cw * ch) * np.dtype(yuv_dtype(pixfmt)).itemsize
 
 
 def _yuv_buf(buf, w, h, pixfmt, what):
@@ -289,7 +299,8 @@ def _pix_of(image, pixfmt=None):
     return pixfmt
 
 
-_ELEM = {PIX_RGB8: 1, PIX_RGB10_U16: 2, PIX_A2B10G10R10: 4, PIX_RGBA8: 1, PIX_NV12: 1, PIX_I420: 1, PIX_P010: 2, PIX_I420P10: 2}
+_ELEM = {PIX_RGB8: 1, PIX_RGB10_U16: 2, PIX_A2B10G10R10: 4, PIX_RGBA8: 1, PIX_NV12: 1, PIX_I420: 1, PIX_P010: 2, PIX_I420P10: 2,
+         PIX_I422: 1, PIX_I422P10: 2, PIX_I444: 1, PIX_I444P10: 2}
 
 
 def image_row_bytes(w, pixfmt, plane):
@@ -348,11 +359,12 @@ def image_of(a, pixfmt=None):
 
 
 def planes_image(planes, w, h, pixfmt, what="planes", writable=False):
-    """The descriptor of a 4:2:0 frame given as a tuple of 2-D arrays, each with its own base and row stride: (h, w) luma and, cw = (w + 1) // 2, ch = (h + 1) // 2,
-    one (ch, 2 * cw) array of interleaved pairs (NV12, P010) or two (ch, cw) arrays Cb, Cr (I420, I420P10; swap them for YV12).  Raises ValueError."""
+    """The descriptor of a YUV frame given as a tuple of 2-D arrays, each with its own base and row stride: (h, w) luma and, cw, ch = yuv_chroma_dims(w, h, pixfmt),
+    one (ch, 2 * cw) array of interleaved pairs (NV12, P010) or two (ch, cw) arrays Cb, Cr (I420, I422, I444 and their P10 forms; swap them for YV12 / YV16 /
+    YV24).  Raises ValueError."""
     base = _yuv_base(pixfmt)
     dt = yuv_dtype(pixfmt)
-    cw, ch = (w + 1) // 2, (h + 1) // 2
+    cw, ch = yuv_chroma_dims(w, h, pixfmt)
     shapes = [(h, w), (ch, 2 * cw)] if base in (PIX_NV12, PIX_P010) else [(h, w), (ch, cw), (ch, cw)]
     if w <= 0 or h <= 0 or len(planes) != len(shapes):
         raise ValueError("%s: %d arrays of shapes %s" % (what, len(shapes), shapes))
@@ -458,7 +470,7 @@ class RIFE:
         return call
 
     def process_planes(self, planes0, planes1, timestep, pixfmt, out=None):
-        """4:2:0 frames as tuples of 2-D plane arrays, each with its own base and row stride (what VapourSynth's plane views or an AVFrame's data / linesize
+        """YUV frames as tuples of 2-D plane arrays, each with its own base and row stride (what VapourSynth's plane views or an AVFrame's data / linesize
         are; shapes: planes_image()).  Nothing is repacked on the host.  out: a tuple of writable plane arrays to fill, or None; returns the output planes."""
         h, w = planes0[0].shape if len(planes0) and isinstance(planes0[0], np.ndarray) and planes0[0].ndim == 2 else (0, 0)
         a = planes_image(planes0, w, h, pixfmt, "planes0"); b = planes_image(planes1, w, h, pixfmt, "planes1")
@@ -469,7 +481,7 @@ class RIFE:
         return tuple(out)
 
     def upload_planes(self, planes, pixfmt):
-        """Stream mode for a 4:2:0 frame given as plane arrays (process_planes); the resident frame is that of upload_yuv() on the packed frame."""
+        """Stream mode for a YUV frame given as plane arrays (process_planes); the resident frame is that of upload_yuv() on the packed frame."""
         h, w = planes[0].shape if len(planes) and isinstance(planes[0], np.ndarray) and planes[0].ndim == 2 else (0, 0)
         a = planes_image(planes, w, h, pixfmt, "planes")
         f = ctypes.c_void_p()
@@ -488,8 +500,8 @@ class RIFE:
         _check(self._L.rife_hip_process_device_image(self._h, ctypes.byref(img0), ctypes.byref(img1), float(timestep), ctypes.byref(out), stream), "process_device_image", self._L)
 
     def process_yuv(self, buf0, buf1, w, h, timestep, pixfmt, out=None):
-        """4:2:0 frames in and out (rife-v4.6, plain mode): flat uint8 (NV12, I420) or uint16 (P010, I420P10) arrays of yuv_frame_bytes(w, h, pixfmt) bytes;
-        pixfmt = PIX_NV12 .. PIX_I420P10, OR-ed with CSP_BT709 / CSP_BT601 / CSP_BT2020NCL and CSP_FULL.  The result has the inputs' format."""
+        """YUV frames in and out (rife-v4.6, plain mode): flat uint8 (NV12, I420, I422, I444) or uint16 (P010, I420P10, I422P10, I444P10) arrays of
+        yuv_frame_bytes(w, h, pixfmt) bytes; pixfmt = PIX_NV12 .. PIX_I444P10, OR-ed with CSP_BT709 / CSP_BT601 / CSP_BT2020NCL and CSP_FULL.  The result has the inputs' format."""
         a = _yuv_buf(buf0, w, h, pixfmt, "buf0"); b = _yuv_buf(buf1, w, h, pixfmt, "buf1")
         o = _yuv_buf(out if out is not None else np.empty_like(a), w, h, pixfmt, "out")
         if not o.flags.writeable:
@@ -498,7 +510,7 @@ class RIFE:
         return o
 
     def upload_yuv(self, buf, w, h, pixfmt):
-        """Stream mode for 4:2:0 frames: the frame stays in device memory in its own format and is converted at each use; process_frames() returns a flat array."""
+        """Stream mode for YUV frames: the frame stays in device memory in its own format and is converted at each use; process_frames() returns a flat array."""
         a = _yuv_buf(buf, w, h, pixfmt, "buf")
         f = ctypes.c_void_p()
         _check(self._L.rife_hip_frame_upload_px(self._h, _p(a), int(w), int(h), int(pixfmt), ctypes.byref(f)), "frame_upload_px", self._L)
@@ -716,7 +728,7 @@ def op_warp(image, flow, gpuid=0):
 
 
 def op_yuv_to_rgb10(buf, w, h, pixfmt, gpuid=0):
-    """k_preproc_yuv alone: one flat 4:2:0 frame -> the resident form, (hp, wp) uint32 R | G << 10 | B << 20 with zero padding (hp, wp = h, w rounded up to 32n)."""
+    """k_preproc_yuv / k_preproc_yuvc alone: one flat YUV frame -> the resident form, (hp, wp) uint32 R | G << 10 | B << 20 with zero padding (hp, wp = h, w rounded up to 32n)."""
     a = _yuv_buf(buf, w, h, pixfmt, "buf")
     out = np.empty(((h + 31) // 32 * 32, (w + 31) // 32 * 32), np.uint32)
     _check(testlib().rife_hip_op_yuv_to_rgb10(gpuid, _p(a), int(w), int(h), int(pixfmt), _p(out)), "op_yuv_to_rgb10", testlib())
@@ -738,7 +750,7 @@ def op_resident_to_image(tight, img, force_scalar=0, gpuid=0):
 
 
 def op_rgb10_to_yuv(packed, pixfmt, gpuid=0):
-    """k_postproc_yuv alone: an (h, w) uint32 A2B10G10R10 frame -> one flat 4:2:0 frame of `pixfmt`."""
+    """k_postproc_yuv / k_postproc_yuvc alone: an (h, w) uint32 A2B10G10R10 frame -> one flat YUV frame of `pixfmt`."""
     a = np.ascontiguousarray(packed, np.uint32)
     if a.ndim != 2 or a.size == 0:
         raise ValueError("packed must be an (h, w) uint32 array")

@@ -160,7 +160,7 @@ static int pixfmt_supported(const rife_hip* E, int pixfmt) {
     if (pixfmt == RIFE_HIP_PIX_RGB8) return 0;
     const char* what = not_plain_v46(E);
     if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : pix_yuv(pixfmt) ? "4:2:0 YUV" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
+    return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : pix_yuv(pixfmt) ? "YUV" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
 }
 // argument checks of the _px entry points that need no engine; then "no HIP device at all" before anything looks at the engine
 // a pixfmt argument = format | colour description (include/rife_hip.h RIFE_HIP_CSP_*): both must be something the library knows
@@ -178,7 +178,7 @@ static int px_precheck(int pixfmt, bool ptrs_ok, int w, int h) {
     return 0;
 }
 // timestep 0 / 1 at depth 10: the input frame in canonical form (samples clamped to 1023, alpha bits 3) - what a pass over identical frames would write
-// (4:2:0: the samples' codes - P010 low bits cleared, I420P10 samples clamped to 1023, 8-bit frames unchanged)
+// (YUV: the samples' codes - P010 low bits cleared, the planar 10-bit samples clamped to 1023, 8-bit frames unchanged)
 static void canon10_host(void* out, const void* in, int w, int h, int pixfmt) {
     const size_t npix = (size_t)w * h;
     if (pix_yuv(pixfmt)) {
@@ -208,7 +208,7 @@ static int copy_frame_device(hipStream_t st, const void* src, void* dst, int w, 
         if (pix_base(pixfmt) == RIFE_HIP_PIX_P010) hipLaunchKernelGGL(k_canon_yuv10<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), n);
         else hipLaunchKernelGGL(k_canon_yuv10<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), n);
     }
-    else { HIPCHK(hipMemcpyAsync(dst, src, frame_bytes(w, h, pixfmt), hipMemcpyDeviceToDevice, st)); return 0; }      // RGB8, RGBA8, NV12, I420: the bytes unchanged
+    else { HIPCHK(hipMemcpyAsync(dst, src, frame_bytes(w, h, pixfmt), hipMemcpyDeviceToDevice, st)); return 0; }      // RGB8, RGBA8 and 8-bit YUV: the bytes unchanged
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1264,12 +1264,12 @@ int rife_hip_op_warp(int gpuid, const float* image, const float* flow, int c, in
     return 0;
 }
 
-// the two 4:2:0 kernels alone (yuv.h), in the form the host would pick for a frame at an aligned address: planes -> zero-padded 10:10:10 dwords (hp x wp),
+// the YUV kernels alone (yuv.h), in the form the host would pick for a frame at an aligned address: planes -> zero-padded 10:10:10 dwords (hp x wp),
 // A2B10G10R10 (h x w) -> planes
 int rife_hip_op_yuv_to_rgb10(int gpuid, const void* yuv, int w, int h, int pixfmt, uint32_t* out_padded) {
     int rc;
     if ((rc = pixfmt_check(pixfmt))) return rc;
-    if (!pix_yuv(pixfmt) || !yuv || !out_padded || w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "op_yuv_to_rgb10: a 4:2:0 format, two arrays and a frame size");
+    if (!pix_yuv(pixfmt) || !yuv || !out_padded || w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "op_yuv_to_rgb10: a YUV format, two arrays and a frame size");
     if ((rc = check_device(gpuid))) return rc;
     const int wp = (w + 31) / 32 * 32, hp = (h + 31) / 32 * 32;
     const size_t nin = frame_bytes(w, h, pixfmt), nout = (size_t)wp * hp * 4;
@@ -1289,7 +1289,7 @@ int rife_hip_op_yuv_to_rgb10(int gpuid, const void* yuv, int w, int h, int pixfm
 int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int h, int pixfmt, void* yuv_out) {
     int rc;
     if ((rc = pixfmt_check(pixfmt))) return rc;
-    if (!pix_yuv(pixfmt) || !a2b10g10r10 || !yuv_out || w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "op_rgb10_to_yuv: a 4:2:0 format, two arrays and a frame size");
+    if (!pix_yuv(pixfmt) || !a2b10g10r10 || !yuv_out || w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "op_rgb10_to_yuv: a YUV format, two arrays and a frame size");
     if ((rc = check_device(gpuid))) return rc;
     const size_t nin = (size_t)w * h * 4, nout = frame_bytes(w, h, pixfmt);
     void *d_i = nullptr, *d_o = nullptr;

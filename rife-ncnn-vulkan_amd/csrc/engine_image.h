@@ -28,7 +28,7 @@ static int image_supported(const rife_hip* E) {
 // byte offset of plane p in the tight frame of the _px calls
 static size_t image_tight_offset(int w, int h, int pixfmt, int p) {
     size_t off = 0;
-    for (int q = 0; q < p; q++) off += rife_img::row_bytes(w, pixfmt, q) * (size_t)rife_img::plane_rows(h, q);
+    for (int q = 0; q < p; q++) off += rife_img::row_bytes(w, pixfmt, q) * (size_t)rife_img::plane_rows(h, pixfmt, q);
     return off;
 }
 // 2-D copies per plane between an image and a tight frame (either side host or device, `kind` says which)
@@ -36,7 +36,7 @@ static hipError_t image_copy_to_tight(void* tight, const rife_hip_image_t& im, h
     hipError_t e = hipSuccess;
     for (int p = 0; p < rife_img::planes(im.pixfmt) && e == hipSuccess; p++) {
         const size_t rb = rife_img::row_bytes(im.w, im.pixfmt, p);
-        e = hipMemcpy2DAsync(static_cast<uint8_t*>(tight) + image_tight_offset(im.w, im.h, im.pixfmt, p), rb, im.plane[p], (size_t)im.pitch[p], rb, (size_t)rife_img::plane_rows(im.h, p), kind, st);
+        e = hipMemcpy2DAsync(static_cast<uint8_t*>(tight) + image_tight_offset(im.w, im.h, im.pixfmt, p), rb, im.plane[p], (size_t)im.pitch[p], rb, (size_t)rife_img::plane_rows(im.h, im.pixfmt, p), kind, st);
     }
     return e;
 }
@@ -44,7 +44,7 @@ static hipError_t image_copy_from_tight(const rife_hip_image_t& im, const void* 
     hipError_t e = hipSuccess;
     for (int p = 0; p < rife_img::planes(im.pixfmt) && e == hipSuccess; p++) {
         const size_t rb = rife_img::row_bytes(im.w, im.pixfmt, p);
-        e = hipMemcpy2DAsync(im.plane[p], (size_t)im.pitch[p], static_cast<const uint8_t*>(tight) + image_tight_offset(im.w, im.h, im.pixfmt, p), rb, rb, (size_t)rife_img::plane_rows(im.h, p), kind, st);
+        e = hipMemcpy2DAsync(im.plane[p], (size_t)im.pitch[p], static_cast<const uint8_t*>(tight) + image_tight_offset(im.w, im.h, im.pixfmt, p), rb, rb, (size_t)rife_img::plane_rows(im.h, im.pixfmt, p), kind, st);
     }
     return e;
 }
@@ -53,7 +53,7 @@ static void image_canon_host(const rife_hip_image_t& out, const rife_hip_image_t
     const CanonMode mode = canon_mode(in.pixfmt);
     for (int p = 0; p < rife_img::planes(in.pixfmt); p++) {
         const size_t rb = rife_img::row_bytes(in.w, in.pixfmt, p);
-        for (int y = 0; y < rife_img::plane_rows(in.h, p); y++) {
+        for (int y = 0; y < rife_img::plane_rows(in.h, in.pixfmt, p); y++) {
             const uint8_t* s = static_cast<const uint8_t*>(in.plane[p]) + (size_t)y * in.pitch[p];
             uint8_t* d = static_cast<uint8_t*>(out.plane[p]) + (size_t)y * out.pitch[p];
             if (mode == CANON_BYTES) std::memmove(d, s, rb);
@@ -67,7 +67,7 @@ static int image_canon_device(hipStream_t st, const rife_hip_image_t& in, const 
     const CanonMode mode = canon_mode(in.pixfmt);
     for (int p = 0; p < rife_img::planes(in.pixfmt); p++) {
         const size_t rb = rife_img::row_bytes(in.w, in.pixfmt, p);
-        const int rows = rife_img::plane_rows(in.h, p);
+        const int rows = rife_img::plane_rows(in.h, in.pixfmt, p);
         const uint8_t* s = static_cast<const uint8_t*>(in.plane[p]); uint8_t* d = static_cast<uint8_t*>(out.plane[p]);
         const size_t sp = (size_t)in.pitch[p], dp = (size_t)out.pitch[p];
         if (mode == CANON_BYTES) { HIPCHK(hipMemcpy2DAsync(d, dp, s, sp, rb, (size_t)rows, hipMemcpyDeviceToDevice, st)); continue; }
@@ -208,7 +208,7 @@ static int rife_hip_process_device_image_impl(const rife_hip_t* E, const rife_hi
     } else {
         if ((rc = ensure_ctx(*c, w, h, pixfmt))) return rc;
         const PlaneIO pio{plane_set(*in0), plane_set(*in1), plane_set(*out)};
-        rc = run_v4(*E, *c, nullptr, nullptr, timestep, c->d_out, nullptr, &pio);      // 4:2:0: k_postproc_yuv_pitch writes the caller's planes; RGB formats: the tight frame c->d_out
+        rc = run_v4(*E, *c, nullptr, nullptr, timestep, c->d_out, nullptr, &pio);      // YUV: the pitched post-processing kernel writes the caller's planes; RGB formats: the tight frame c->d_out
         if (rc) return rc;
         if (!pix_yuv(pixfmt)) {
             Timed t(E->prof, "store_rows", 0, c->stream);
@@ -260,7 +260,7 @@ struct ImageMirror {
         size_t cur = 0;
         const int np = rife_img::planes(im.pixfmt);
         for (int p = 0; p < np; p++) {
-            span[p] = (size_t)(rife_img::plane_rows(im.h, p) - 1) * (size_t)im.pitch[p] + rife_img::row_bytes(im.w, im.pixfmt, p);
+            span[p] = (size_t)(rife_img::plane_rows(im.h, im.pixfmt, p) - 1) * (size_t)im.pitch[p] + rife_img::row_bytes(im.w, im.pixfmt, p);
             off[p] = (cur + 15) / 16 * 16 + (reinterpret_cast<uintptr_t>(im.plane[p]) & 15);
             cur = off[p] + span[p];
         }

@@ -81,23 +81,26 @@ static int ensure_ctx_dims(Ctx& c, int w, int h, int wp, int hp, const Ctx* scra
 static inline int pix_bpp(int pixfmt) {
     return pixfmt == RIFE_HIP_PIX_RGB8 ? 3 : pixfmt == RIFE_HIP_PIX_RGB10_U16 ? 6 : (pixfmt == RIFE_HIP_PIX_A2B10G10R10 || pixfmt == RIFE_HIP_PIX_RGBA8) ? 4 : 0;
 }
-// a pixfmt = format (bits 0-7) | colour description (bits 8-12, 4:2:0 formats only)
+// a pixfmt = format (bits 0-7) | colour description (bits 8-12, YUV formats only)
 static inline int pix_base(int pixfmt) { return pixfmt & 0xff; }
-static inline bool pix_yuv(int pixfmt) { return pix_base(pixfmt) >= RIFE_HIP_PIX_NV12 && pix_base(pixfmt) <= RIFE_HIP_PIX_I420P10; }
-// size of a tightly packed w x h frame; 0 = unknown format.  4:2:0: a luma plane and two chroma planes of (w + 1) / 2 x (h + 1) / 2 samples
+static inline bool pix_yuv(int pixfmt) { return rife_img::is_yuv(pixfmt); }      // NV12 .. I420P10, I422, I422P10, I444, I444P10 (image_check.h)
+// size of a tightly packed w x h frame; 0 = unknown format.  YUV: a luma plane and two chroma planes of cw x ch samples - 4:2:0 (w + 1) / 2 x (h + 1) / 2,
+// 4:2:2 (w + 1) / 2 x h, 4:4:4 w x h
 static inline size_t frame_bytes(int w, int h, int pixfmt) {
     if (!pix_yuv(pixfmt)) return (size_t)w * h * pix_bpp(pixfmt);
-    return ((size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2)) * (yuv_depth(pix_base(pixfmt)) == 10 ? 2 : 1);
+    const int cls = yuv_class(pix_base(pixfmt));
+    const size_t cw = cls == 3 ? (size_t)w : (size_t)((w + 1) / 2), ch = cls == 1 ? (size_t)((h + 1) / 2) : (size_t)h;
+    return ((size_t)w * h + 2 * cw * ch) * (yuv_depth(pix_base(pixfmt)) == 10 ? 2 : 1);
 }
 // the resident frames of this format are 10:10:10 dwords (the D = 10 instantiations of everything that reads a frame); RGB8 and RGBA8 frames are depth 8.
-// 4:2:0 frames of either depth are converted to 10-bit RGB on the way in (exactly invertible, include/rife_hip.h) and ride the depth-10 schedule.
+// YUV frames of either depth are converted to 10-bit RGB on the way in (exactly invertible, include/rife_hip.h) and ride the depth-10 schedule.
 static inline bool pix_deep(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB10_U16 || pixfmt == RIFE_HIP_PIX_A2B10G10R10 || pix_yuv(pixfmt); }
-// the format the quantising kernels of a pass write: the caller's, or for 4:2:0 the internal A2B10G10R10 frame k_postproc_yuv reads (Ctx::yuv_rgb)
+// the format the quantising kernels of a pass write: the caller's, or for YUV the internal A2B10G10R10 frame k_postproc_yuv / k_postproc_yuvc reads (Ctx::yuv_rgb)
 static inline int pix_inner(int pixfmt) { return pix_yuv(pixfmt) ? RIFE_HIP_PIX_A2B10G10R10 : pixfmt; }
 // the workspace serves frames of `pixfmt` from here on: staging buffers of that size, c.pixfmt for every launch site that reads or writes a frame
 static int ensure_ctx(Ctx& c, int w, int h, int pixfmt = RIFE_HIP_PIX_RGB8) {
     int rc = ensure_ctx_dims(c, w, h, (w + 31) / 32 * 32, (h + 31) / 32 * 32, nullptr, true, false, frame_bytes(w, h, pixfmt));   // pad to 32n, rife.cpp:2499-2500
-    if (!rc && pix_yuv(pixfmt) && !c.yuv_rgb && (rc = dalloc(c, c.yuv_rgb, (size_t)c.wp * c.hp))) reset_ctx(c);      // only once a 4:2:0 format is served
+    if (!rc && pix_yuv(pixfmt) && !c.yuv_rgb && (rc = dalloc(c, c.yuv_rgb, (size_t)c.wp * c.hp))) reset_ctx(c);      // only once a YUV format is served
     if (!rc) c.pixfmt = pixfmt;
     return rc;
 }
@@ -115,7 +118,7 @@ static inline dim3 tta_block(int elem_bytes) { return elem_bytes >= 16 ? dim3(8,
 static inline dim3 tta_grid(int w, int h, int elem_bytes) { const dim3 b = tta_block(elem_bytes); return dim3((w + b.x - 1) / b.x, (h + b.y - 1) / b.y); }
 // rife_preproc.comp: u8 HWC RGB -> zero-padded RGBX; four pixels per lane when the frame allows 4-byte loads
 static inline void launch_preproc(hipStream_t st, const uint8_t* rgb, int w, int h, uint32_t* out, int wp, int hp, int pixfmt = RIFE_HIP_PIX_RGB8) {
-    if (pix_yuv(pixfmt)) { launch_preproc_yuv(st, rgb, w, h, out, wp, hp, pixfmt); return; }      // 4:2:0 planes -> 10:10:10 dwords (yuv.h)
+    if (pix_yuv(pixfmt)) { launch_preproc_yuv(st, rgb, w, h, out, wp, hp, pixfmt); return; }      // YUV planes -> 10:10:10 dwords (yuv.h)
     if (pixfmt == RIFE_HIP_PIX_RGB10_U16) {
         const uint16_t* p = reinterpret_cast<const uint16_t*>(rgb);
         if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 7) == 0) hipLaunchKernelGGL(k_preproc10_u16x4, dim3((wp / 4 + 255) / 256, hp), dim3(256), 0, st, p, w, h, out, wp, hp);

@@ -12,7 +12,12 @@
 namespace rife_img {
 
 static inline int base(int pixfmt) { return pixfmt & 0xff; }
-static inline bool is_yuv(int pixfmt) { return base(pixfmt) >= RIFE_HIP_PIX_NV12 && base(pixfmt) <= RIFE_HIP_PIX_I420P10; }
+// YUV formats are 16 * class + 2 * (10 bits) + planar; class 1 = 4:2:0 (all four), 2 = 4:2:2 and 3 = 4:4:4 (planar only)
+static inline int yuv_class(int pixfmt) { return base(pixfmt) >> 4; }
+static inline bool is_yuv(int pixfmt) {
+    const int b = base(pixfmt);
+    return (b >= RIFE_HIP_PIX_NV12 && b <= RIFE_HIP_PIX_I420P10) || b == RIFE_HIP_PIX_I422 || b == RIFE_HIP_PIX_I422P10 || b == RIFE_HIP_PIX_I444 || b == RIFE_HIP_PIX_I444P10;
+}
 static inline bool known(int pixfmt) {
     const int b = base(pixfmt);
     return pixfmt >= 0 && (b == RIFE_HIP_PIX_RGB8 || b == RIFE_HIP_PIX_RGB10_U16 || b == RIFE_HIP_PIX_A2B10G10R10 || b == RIFE_HIP_PIX_RGBA8 || is_yuv(pixfmt));
@@ -21,29 +26,31 @@ static inline bool known(int pixfmt) {
 static inline const char* pixfmt_fault(int pixfmt) {
     const int csp = pixfmt & ~0xff;
     if (!known(pixfmt) || (csp & ~0x1f00)) return "unknown pixel format";
-    if (!is_yuv(pixfmt)) return csp ? "a colour description (RIFE_HIP_CSP_*) goes with a 4:2:0 YUV format, not with an RGB format" : nullptr;
+    if (!is_yuv(pixfmt)) return csp ? "a colour description (RIFE_HIP_CSP_*) goes with a YUV format, not with an RGB format" : nullptr;
     if (((csp >> 8) & 15) > 2) return "unknown colour matrix";
-    if ((csp & RIFE_HIP_CSP_FULL) && (base(pixfmt) == RIFE_HIP_PIX_P010 || base(pixfmt) == RIFE_HIP_PIX_I420P10))
+    if ((csp & RIFE_HIP_CSP_FULL) && is_yuv(pixfmt) && (base(pixfmt) & 2))
         return "full-range YUV is served at 8 bits only (the 10-bit full-range round trip through 10-bit RGB is not exact)";
     return nullptr;
 }
 // bytes of one sample group the kernels address as a unit: 1 for the u8 formats, 2 for the u16 formats, 4 for A2B10G10R10
 static inline int elem_size(int pixfmt) {
     const int b = base(pixfmt);
-    return b == RIFE_HIP_PIX_A2B10G10R10 ? 4 : (b == RIFE_HIP_PIX_RGB10_U16 || b == RIFE_HIP_PIX_P010 || b == RIFE_HIP_PIX_I420P10) ? 2 : 1;
+    return b == RIFE_HIP_PIX_A2B10G10R10 ? 4 : (b == RIFE_HIP_PIX_RGB10_U16 || (is_yuv(pixfmt) && (b & 2))) ? 2 : 1;
 }
 static inline int planes(int pixfmt) {
     const int b = base(pixfmt);
     return !known(pixfmt) ? 0 : !is_yuv(pixfmt) ? 1 : (b == RIFE_HIP_PIX_NV12 || b == RIFE_HIP_PIX_P010) ? 2 : 3;
 }
-// rows of plane p of a frame h rows high: h for the first plane, ch = (h + 1) / 2 for chroma
+// rows of plane p of a 4:2:0 frame h rows high: h for the first plane, ch = (h + 1) / 2 for chroma
 static inline int plane_rows(int h, int p) { return p == 0 ? h : (h + 1) / 2; }
+// the same for any format: the chroma planes of 4:2:2 and 4:4:4 have h rows
+static inline int plane_rows(int h, int pixfmt, int p) { return yuv_class(pixfmt) >= 2 ? h : plane_rows(h, p); }
 // bytes of one row of plane p, 0 for a plane the format does not have (or w <= 0, an unknown format)
 static inline size_t row_bytes(int w, int pixfmt, int p) {
     if (w <= 0 || p < 0 || p >= planes(pixfmt)) return 0;
     const int b = base(pixfmt);
     if (!is_yuv(pixfmt)) return (size_t)w * (b == RIFE_HIP_PIX_RGB8 ? 3 : b == RIFE_HIP_PIX_RGB10_U16 ? 6 : 4);
-    const size_t cw = ((size_t)w + 1) / 2, es = (size_t)elem_size(pixfmt);
+    const size_t cw = yuv_class(pixfmt) == 3 ? (size_t)w : ((size_t)w + 1) / 2, es = (size_t)elem_size(pixfmt);
     return p == 0 ? (size_t)w * es : planes(pixfmt) == 2 ? 2 * cw * es : cw * es;
 }
 
@@ -78,7 +85,7 @@ static inline bool is_tight(const rife_hip_image_t* im) {
     for (int p = 0; p < planes(im->pixfmt); p++) {
         const size_t rb = row_bytes(im->w, im->pixfmt, p);
         if (static_cast<const uint8_t*>(im->plane[p]) != at || (size_t)im->pitch[p] != rb) return false;
-        at += rb * (size_t)plane_rows(im->h, p);
+        at += rb * (size_t)plane_rows(im->h, im->pixfmt, p);
     }
     return true;
 }

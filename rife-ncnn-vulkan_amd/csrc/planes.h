@@ -5,6 +5,7 @@
 //   k_preproc_pitch<PX, WIDE>            RGB8 / RGB10_U16 / A2B10G10R10 / RGBA8 plane -> resident dwords, zero (alpha: edge) padded
 //   k_preproc_yuv_pitch / _x8            Y, Cb, Cr (or Y, CbCr) planes -> resident 10:10:10 dwords
 //   k_postproc_yuv_pitch / _x8           the pass's tight A2B10G10R10 frame -> Y, Cb, Cr (or Y, CbCr) planes
+//   (4:2:2 / 4:4:4: yuv.h k_preproc_yuvc / k_postproc_yuvc take pitched planes to begin with; the launchers below pass the caller's planes to them)
 //   k_store_rows<T>                      the pass's tight RGB-format frame (Ctx::d_out) -> the caller's strided plane, row_bytes of each row and nothing else
 //   k_canon_rows<MODE>                   timestep 0 / 1 at depth 10: strided plane -> strided plane in canonical form
 // Wide forms (four pixels / a run of eight samples per lane): every plane pointer AND every pitch the kernel touches is aligned to the access width, and
@@ -19,17 +20,12 @@
 
 namespace rife {
 
-// one frame's planes as the kernels take them (pitches in bytes; entries the format does not use are null / 0)
-struct PlaneSet {
-    uint8_t* p[3];
-    size_t pitch[3];
-};
+// one frame's planes as the kernels take them (PlaneSet: yuv.h)
 static inline PlaneSet plane_set(const rife_hip_image_t& im) {
     PlaneSet s;
     for (int i = 0; i < 3; i++) { s.p[i] = static_cast<uint8_t*>(im.plane[i]); s.pitch[i] = (size_t)im.pitch[i]; }
     return s;
 }
-static inline bool planes_aligned(const PlaneSet& s, int p, unsigned a) { return ((reinterpret_cast<uintptr_t>(s.p[p]) | s.pitch[p]) & (a - 1)) == 0; }
 
 // ---- in, RGB formats: PX = RIFE_HIP_PIX_RGB8 / RGB10_U16 / A2B10G10R10 / RGBA8.  scalar: one pixel per lane, grid2d(wp, hp); WIDE: four, grid ((wp / 4 + 255) / 256, hp) ----
 template <int PX, bool WIDE>
@@ -224,12 +220,12 @@ __global__ void k_store_rows(const uint8_t* __restrict__ src, size_t row_bytes, 
 }
 // timestep 0 / 1: what the canonical copy of a format does to a sample (host and device state it from this one enum)
 enum CanonMode { CANON_BYTES = 0,      // the 8-bit formats: bytes unchanged (2-D copies, no kernel)
-                 CANON_U16_CLAMP,      // RGB10_U16, I420P10: u16 clamped to 1023
+                 CANON_U16_CLAMP,      // RGB10_U16, I420P10, I422P10, I444P10: u16 clamped to 1023
                  CANON_PACKED_ALPHA,   // A2B10G10R10: dword | alpha bits 3
                  CANON_P010 };         // P010: low six bits cleared
 static inline CanonMode canon_mode(int pixfmt) {
     const int b = pixfmt & 0xff;
-    return (b == RIFE_HIP_PIX_RGB10_U16 || b == RIFE_HIP_PIX_I420P10) ? CANON_U16_CLAMP : b == RIFE_HIP_PIX_A2B10G10R10 ? CANON_PACKED_ALPHA : b == RIFE_HIP_PIX_P010 ? CANON_P010 : CANON_BYTES;
+    return (b == RIFE_HIP_PIX_RGB10_U16 || b == RIFE_HIP_PIX_I420P10 || b == RIFE_HIP_PIX_I422P10 || b == RIFE_HIP_PIX_I444P10) ? CANON_U16_CLAMP : b == RIFE_HIP_PIX_A2B10G10R10 ? CANON_PACKED_ALPHA : b == RIFE_HIP_PIX_P010 ? CANON_P010 : CANON_BYTES;
 }
 // strided in and out, one element per lane; n = elements per row; grid ((n + 255) / 256, rows).  MODE != CANON_BYTES
 template <CanonMode MODE>
@@ -247,6 +243,7 @@ __global__ void k_canon_rows(const uint8_t* __restrict__ src, size_t spitch, uin
 // ---- host side.  force_scalar: the single-kernel tests run both forms on one frame ----
 static inline void launch_preproc_planes(hipStream_t st, const PlaneSet& s, int w, int h, uint32_t* out, int wp, int hp, int pixfmt, bool force_scalar = false) {
     const int fmt = pixfmt & 0xff;
+    if (fmt >= RIFE_HIP_PIX_I422) { launch_preproc_yuvc(st, s, w, h, out, wp, hp, pixfmt, force_scalar); return; }      // 4:2:2 / 4:4:4: yuv.h, one kernel set for tight and pitched planes
     if (fmt >= RIFE_HIP_PIX_NV12) {
         const YuvCsp k = yuv_csp(pixfmt & ~0xff, yuv_depth(fmt));
         const bool x8 = !force_scalar && planes_yuv_x8(s, w, fmt);
@@ -267,6 +264,7 @@ static inline void launch_preproc_planes(hipStream_t st, const PlaneSet& s, int 
 }
 static inline void launch_postproc_yuv_planes(hipStream_t st, const uint32_t* rgb, int w, int h, const PlaneSet& d, int pixfmt, bool force_scalar = false) {
     const int fmt = pixfmt & 0xff;
+    if (fmt >= RIFE_HIP_PIX_I422) { launch_postproc_yuvc(st, rgb, w, h, d, pixfmt, force_scalar); return; }
     const YuvCsp k = yuv_csp(pixfmt & ~0xff, yuv_depth(fmt));
     const bool x8 = !force_scalar && planes_yuv_x8(d, w, fmt);
     const int cw = (w + 1) / 2, ch = (h + 1) / 2;

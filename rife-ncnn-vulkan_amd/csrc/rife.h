@@ -34,8 +34,8 @@ public:
     int process(const rife_hip_frame* frame0, const rife_hip_frame* frame1, float timestep, ncnn::Mat& outimage) const;
     static void release(rife_hip_frame* frame);
 
-    // Extension, not in the reference (include/rife_hip.h "video"): 4:2:0 Y'CbCr frames.  An ncnn::Mat has no natural 4:2:0 shape, so these take plain pointers
-    // to tightly packed frames of `pixfmt` (RIFE_HIP_PIX_NV12 .. I420P10 | RIFE_HIP_CSP_*), rife_hip_frame_bytes(w, h, pixfmt) bytes each.  rife-v4.6, plain mode.
+    // Extension, not in the reference (include/rife_hip.h "video"): planar Y'CbCr frames (4:2:0, 4:2:2, 4:4:4).  An ncnn::Mat has no natural shape for them, so these take plain pointers
+    // to tightly packed frames of `pixfmt` (RIFE_HIP_PIX_NV12 .. I420P10, I422, I422P10, I444, I444P10 | RIFE_HIP_CSP_*), rife_hip_frame_bytes(w, h, pixfmt) bytes each.  rife-v4.6, plain mode.
     // A frame of upload_yuv() goes through process(frame0, frame1, timestep, outimage) above, whose outimage.data then points at a frame of that size.
     int process_yuv(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt) const;
     rife_hip_frame* upload_yuv(const void* frame, int w, int h, int pixfmt) const;

@@ -4,6 +4,10 @@
 //   k_postproc_yuv<PLANAR, DEPTH>  the pass's A2B10G10R10 frame (tight, pitch w) -> the caller's planes, chroma from the 2x2 sum
 // Each has a scalar form (one 2x2 block per lane, element loads and stores: any size, any element-aligned pointer) and an x8 form (a run of four 2x2 blocks per
 // lane, dword and wider accesses: w % 8 == 0 and an 8- / 16-byte aligned frame, which makes every plane and every row start aligned).  The host picks the form.
+// 4:2:2 and 4:4:4 (RIFE_HIP_PIX_I422 .. I444P10, planar only) have sibling kernels below: the same per-pixel device functions on 2x1 / 1x1 blocks.
+//   k_preproc_yuvc<SUBX, DEPTH> / _x8    Y, Cb, Cr planes -> resident 10:10:10 dwords; SUBX = 1: a chroma row is (w + 1) / 2 samples (4:2:2), 0: w samples (4:4:4)
+//   k_postproc_yuvc<SUBX, DEPTH> / _x8   the pass's tight A2B10G10R10 frame -> Y, Cb, Cr planes, chroma from the 2x1 sum or the pixel itself
+// They take their planes as a PlaneSet (pointer and pitch per plane), so ONE set serves tight frames (yuv_tight_planes) and the caller's pitched planes (planes.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,6 +16,13 @@
 #include "../../include/rife_hip.h"
 
 namespace rife {
+
+// one frame's planes as the kernels take them (pitches in bytes; entries the format does not use are null / 0)
+struct PlaneSet {
+    uint8_t* p[3];
+    size_t pitch[3];
+};
+static inline bool planes_aligned(const PlaneSet& s, int p, unsigned a) { return ((reinterpret_cast<uintptr_t>(s.p[p]) | s.pitch[p]) & (a - 1)) == 0; }
 
 // Q16 coefficients of both directions and the offsets, in codes of the format's depth (tests/yuv_ref.py coefs())
 struct YuvCsp {
@@ -236,21 +247,147 @@ __global__ void k_postproc_yuv_x8(const uint32_t* __restrict__ rgb, int w, int h
     }
 }
 
-// timestep 0 / 1 at depth 10: the frame's samples as codes (P010: low six bits cleared; I420P10: clamped to 1023); n = samples of all three planes
+// ---- 4:2:2 / 4:4:4, planar.  Chroma planes have h rows; a pixel's chroma is the sample of its 2x1 block (SUBX = 1) or its own (SUBX = 0) ----
+// in, scalar: two columns of one row of the PADDED frame per lane; grid ((wp / 2 + 255) / 256, hp)
+template <int SUBX, int DEPTH>
+__global__ void k_preproc_yuvc(PlaneSet s, int w, int h, uint32_t* __restrict__ out, int wp, int hp, YuvCsp k) {
+    typedef typename YuvElem<DEPTH>::T T;
+    const int x = (blockIdx.x * blockDim.x + threadIdx.x) * 2, y = blockIdx.y;
+    if (x >= wp) return;
+    uint2 r = make_uint2(0u, 0u);
+    if (x < w && y < h) {
+        const T* p = reinterpret_cast<const T*>(s.p[0] + (size_t)y * s.pitch[0]) + x;
+        const T* c0 = reinterpret_cast<const T*>(s.p[1] + (size_t)y * s.pitch[1]) + (SUBX ? x / 2 : x);
+        const T* c1 = reinterpret_cast<const T*>(s.p[2] + (size_t)y * s.pitch[2]) + (SUBX ? x / 2 : x);
+        int cb = yuv_code<true, DEPTH>(c0[0]), cr = yuv_code<true, DEPTH>(c1[0]);
+        r.x = yuv_to_pk10(k, yuv_code<true, DEPTH>(p[0]), cb, cr);
+        if (x + 1 < w) {
+            if (!SUBX) { cb = yuv_code<true, DEPTH>(c0[1]); cr = yuv_code<true, DEPTH>(c1[1]); }
+            r.y = yuv_to_pk10(k, yuv_code<true, DEPTH>(p[1]), cb, cr);
+        }
+    }
+    *reinterpret_cast<uint2*>(out + (size_t)y * wp + x) = r;                  // wp is a multiple of 32, x is even
+}
+// in, x8: eight columns of one row of the PADDED frame per lane (w % 8 == 0, planes and pitches aligned to the loads); grid ((wp / 8 + 255) / 256, hp)
+template <int SUBX, int DEPTH>
+__global__ void k_preproc_yuvc_x8(PlaneSet s, int w, int h, uint32_t* __restrict__ out, int wp, int hp, YuvCsp k) {
+    typedef typename YuvElem<DEPTH>::T T;
+    const int x = (blockIdx.x * blockDim.x + threadIdx.x) * 8, y = blockIdx.y;
+    if (x >= wp) return;
+    uint32_t o[8];
+    for (int i = 0; i < 8; i++) o[i] = 0u;
+    if (x < w && y < h) {
+        int cb[8], cr[8], yv[8];
+        const T* c0 = reinterpret_cast<const T*>(s.p[1] + (size_t)y * s.pitch[1]);
+        const T* c1 = reinterpret_cast<const T*>(s.p[2] + (size_t)y * s.pitch[2]);
+        if (SUBX) { yuv_load4<true, DEPTH>(c0 + x / 2, cb); yuv_load4<true, DEPTH>(c1 + x / 2, cr); }
+        else { yuv_load8<true, DEPTH>(c0 + x, cb); yuv_load8<true, DEPTH>(c1 + x, cr); }
+        yuv_load8<true, DEPTH>(reinterpret_cast<const T*>(s.p[0] + (size_t)y * s.pitch[0]) + x, yv);
+        for (int i = 0; i < 8; i++) o[i] = yuv_to_pk10(k, yv[i], cb[SUBX ? i / 2 : i], cr[SUBX ? i / 2 : i]);
+    }
+    uint4* d = reinterpret_cast<uint4*>(out + (size_t)y * wp + x);
+    d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+// out, scalar: two columns of one row of the frame per lane; rgb = A2B10G10R10, tight (pitch w); grid (((w + 1) / 2 + 255) / 256, h)
+template <int SUBX, int DEPTH>
+__global__ void k_postproc_yuvc(const uint32_t* __restrict__ rgb, int w, int h, PlaneSet d, YuvCsp k) {
+    typedef typename YuvElem<DEPTH>::T T;
+    const int bx = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    const int x = 2 * bx;
+    if (x >= w || y >= h) return;
+    const bool right = x + 1 < w;
+    const uint32_t* s = rgb + (size_t)y * w + x;
+    T* p = reinterpret_cast<T*>(d.p[0] + (size_t)y * d.pitch[0]) + x;
+    T* c0 = reinterpret_cast<T*>(d.p[1] + (size_t)y * d.pitch[1]) + (SUBX ? bx : x);
+    T* c1 = reinterpret_cast<T*>(d.p[2] + (size_t)y * d.pitch[2]) + (SUBX ? bx : x);
+    int sr = 0, sg = 0, sb = 0, cb, cr;
+    p[0] = (T)yuv_sample<true, DEPTH>(yuv_luma<DEPTH>(k, s[0], sr, sg, sb));
+    if (!SUBX) {
+        yuv_chroma<DEPTH>(k, sr, sg, sb, 0, cb, cr);
+        c0[0] = (T)yuv_sample<true, DEPTH>(cb); c1[0] = (T)yuv_sample<true, DEPTH>(cr);
+        sr = sg = sb = 0;
+    }
+    if (right) p[1] = (T)yuv_sample<true, DEPTH>(yuv_luma<DEPTH>(k, s[1], sr, sg, sb));
+    if (SUBX || right) {
+        yuv_chroma<DEPTH>(k, sr, sg, sb, (SUBX && right) ? 1 : 0, cb, cr);
+        c0[SUBX ? 0 : 1] = (T)yuv_sample<true, DEPTH>(cb); c1[SUBX ? 0 : 1] = (T)yuv_sample<true, DEPTH>(cr);
+    }
+}
+// out, x8: eight columns of one row per lane (w % 8 == 0, planes and pitches aligned to the stores); grid ((w / 8 + 255) / 256, h)
+template <int SUBX, int DEPTH>
+__global__ void k_postproc_yuvc_x8(const uint32_t* __restrict__ rgb, int w, int h, PlaneSet d, YuvCsp k) {
+    typedef typename YuvElem<DEPTH>::T T;
+    const int x = (blockIdx.x * blockDim.x + threadIdx.x) * 8, y = blockIdx.y;
+    if (x >= w || y >= h) return;
+    const uint4* s = reinterpret_cast<const uint4*>(rgb + (size_t)y * w + x);
+    const uint4 a = s[0], b = s[1];
+    const uint32_t px[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    int sr[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int yv[8], cb[8], cr[8];
+    for (int i = 0; i < 8; i++) { const int j = SUBX ? i / 2 : i; yv[i] = yuv_luma<DEPTH>(k, px[i], sr[j], sg[j], sb[j]); }
+    yuv_store8<true, DEPTH>(reinterpret_cast<T*>(d.p[0] + (size_t)y * d.pitch[0]) + x, yv);
+    for (int i = 0; i < (SUBX ? 4 : 8); i++) yuv_chroma<DEPTH>(k, sr[i], sg[i], sb[i], SUBX, cb[i], cr[i]);      // every block is inside the frame: n = 2 or 1
+    T* c0 = reinterpret_cast<T*>(d.p[1] + (size_t)y * d.pitch[1]);
+    T* c1 = reinterpret_cast<T*>(d.p[2] + (size_t)y * d.pitch[2]);
+    if (SUBX) { yuv_store4<true, DEPTH>(c0 + x / 2, cb); yuv_store4<true, DEPTH>(c1 + x / 2, cr); }
+    else { yuv_store8<true, DEPTH>(c0 + x, cb); yuv_store8<true, DEPTH>(c1 + x, cr); }
+}
+
+// timestep 0 / 1 at depth 10: the frame's samples as codes (P010: low six bits cleared; I420P10, I422P10, I444P10: clamped to 1023); n = samples of all three planes
 template <bool PLANAR>
 __global__ void k_canon_yuv10(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (uint16_t)yuv_sample<PLANAR, 10>(yuv_code<PLANAR, 10>(in[i]));
 }
 
-// host side: fmt = the format bits of a pixfmt (RIFE_HIP_PIX_NV12 .. I420P10), csp its colour bits.  The x8 forms need w % 8 == 0 and a frame aligned to 8 bytes (16 at depth 10):
-// the planes follow each other at w * h elements, so that is what aligns every row of every plane.
-static inline bool yuv_planar(int fmt) { return fmt == RIFE_HIP_PIX_I420 || fmt == RIFE_HIP_PIX_I420P10; }
-static inline int yuv_depth(int fmt) { return (fmt == RIFE_HIP_PIX_P010 || fmt == RIFE_HIP_PIX_I420P10) ? 10 : 8; }
+// host side: fmt = the format bits of a pixfmt (RIFE_HIP_PIX_NV12 .. I444P10 = 16 * class + 2 * (10 bits) + planar; class 1 = 4:2:0, 2 = 4:2:2, 3 = 4:4:4), csp its colour bits.
+// The 4:2:0 x8 forms need w % 8 == 0 and a frame aligned to 8 bytes (16 at depth 10): the planes follow each other at w * h elements, so that is what aligns every row of every plane.
+static inline int yuv_class(int fmt) { return fmt >> 4; }
+static inline bool yuv_planar(int fmt) { return (fmt & 1) != 0; }
+static inline int yuv_depth(int fmt) { return (fmt & 2) ? 10 : 8; }
 static inline bool yuv_x8_ok(const void* frame, int w, int fmt) { return (w & 7) == 0 && (reinterpret_cast<uintptr_t>(frame) & (yuv_depth(fmt) == 10 ? 15 : 7)) == 0; }
+
+// 4:2:2 / 4:4:4: the planes of a tight frame (Y w x h, Cb and Cr cw x h one after the other)
+static inline PlaneSet yuv_tight_planes(const void* frame, int w, int h, int fmt) {
+    const size_t es = yuv_depth(fmt) == 10 ? 2 : 1, cw = yuv_class(fmt) == 2 ? ((size_t)w + 1) / 2 : (size_t)w;
+    PlaneSet s;
+    s.p[0] = static_cast<uint8_t*>(const_cast<void*>(frame)); s.pitch[0] = (size_t)w * es;
+    s.p[1] = s.p[0] + (size_t)w * h * es; s.pitch[1] = cw * es;
+    s.p[2] = s.p[1] + cw * h * es; s.pitch[2] = cw * es;
+    return s;
+}
+// the x8 forms load / store 8 luma samples (8 bytes at depth 8, 16 at depth 10) and, per chroma plane, 4 samples (4:2:2: 4 / 8 bytes) or 8 (4:4:4: 8 / 16 bytes): every
+// plane pointer and pitch is aligned to its own access.  A tight frame with w % 8 == 0 at an 8- / 16-byte aligned address qualifies: its 4:2:2 chroma rows are w / 2 samples,
+// a multiple of the 4-sample access, and the chroma planes start w * h and w * h + (w / 2) * h samples in.
+static inline bool yuvc_x8_ok(const PlaneSet& s, int w, int fmt) {
+    const unsigned a = yuv_depth(fmt) == 10 ? 16u : 8u, ac = yuv_class(fmt) == 2 ? a / 2 : a;
+    return (w & 7) == 0 && planes_aligned(s, 0, a) && planes_aligned(s, 1, ac) && planes_aligned(s, 2, ac);
+}
+static inline void launch_preproc_yuvc(hipStream_t st, const PlaneSet& s, int w, int h, uint32_t* out, int wp, int hp, int pixfmt, bool force_scalar = false) {
+    const int fmt = pixfmt & 0xff;
+    const YuvCsp k = yuv_csp(pixfmt & ~0xff, yuv_depth(fmt));
+    const bool x8 = !force_scalar && yuvc_x8_ok(s, w, fmt);
+    const dim3 g = x8 ? dim3((wp / 8 + 255) / 256, hp) : dim3((wp / 2 + 255) / 256, hp);
+#define RIFE_YUVC_IN(S, D) do { if (x8) hipLaunchKernelGGL((k_preproc_yuvc_x8<S, D>), g, dim3(256), 0, st, s, w, h, out, wp, hp, k); \
+                                else hipLaunchKernelGGL((k_preproc_yuvc<S, D>), g, dim3(256), 0, st, s, w, h, out, wp, hp, k); } while (0)
+    if (fmt == RIFE_HIP_PIX_I422) RIFE_YUVC_IN(1, 8); else if (fmt == RIFE_HIP_PIX_I422P10) RIFE_YUVC_IN(1, 10); else if (fmt == RIFE_HIP_PIX_I444) RIFE_YUVC_IN(0, 8); else RIFE_YUVC_IN(0, 10);
+#undef RIFE_YUVC_IN
+}
+static inline void launch_postproc_yuvc(hipStream_t st, const uint32_t* rgb, int w, int h, const PlaneSet& d, int pixfmt, bool force_scalar = false) {
+    const int fmt = pixfmt & 0xff;
+    const YuvCsp k = yuv_csp(pixfmt & ~0xff, yuv_depth(fmt));
+    const bool x8 = !force_scalar && yuvc_x8_ok(d, w, fmt);
+    const dim3 g = x8 ? dim3((w / 8 + 255) / 256, h) : dim3(((w + 1) / 2 + 255) / 256, h);
+#define RIFE_YUVC_OUT(S, D) do { if (x8) hipLaunchKernelGGL((k_postproc_yuvc_x8<S, D>), g, dim3(256), 0, st, rgb, w, h, d, k); \
+                                 else hipLaunchKernelGGL((k_postproc_yuvc<S, D>), g, dim3(256), 0, st, rgb, w, h, d, k); } while (0)
+    if (fmt == RIFE_HIP_PIX_I422) RIFE_YUVC_OUT(1, 8); else if (fmt == RIFE_HIP_PIX_I422P10) RIFE_YUVC_OUT(1, 10); else if (fmt == RIFE_HIP_PIX_I444) RIFE_YUVC_OUT(0, 8); else RIFE_YUVC_OUT(0, 10);
+#undef RIFE_YUVC_OUT
+}
 
 static inline void launch_preproc_yuv(hipStream_t st, const void* frame, int w, int h, uint32_t* out, int wp, int hp, int pixfmt) {
     const int fmt = pixfmt & 0xff;
+    if (yuv_class(fmt) != 1) { launch_preproc_yuvc(st, yuv_tight_planes(frame, w, h, fmt), w, h, out, wp, hp, pixfmt); return; }
     const YuvCsp k = yuv_csp(pixfmt & ~0xff, yuv_depth(fmt));
     const bool x8 = yuv_x8_ok(frame, w, fmt);
     const dim3 g = x8 ? dim3((wp / 8 + 255) / 256, hp / 2) : dim3((wp / 2 + 255) / 256, hp / 2);
@@ -261,6 +398,7 @@ static inline void launch_preproc_yuv(hipStream_t st, const void* frame, int w, 
 }
 static inline void launch_postproc_yuv(hipStream_t st, const uint32_t* rgb, int w, int h, void* frame, int pixfmt) {
     const int fmt = pixfmt & 0xff;
+    if (yuv_class(fmt) != 1) { launch_postproc_yuvc(st, rgb, w, h, yuv_tight_planes(frame, w, h, fmt), pixfmt); return; }
     const YuvCsp k = yuv_csp(pixfmt & ~0xff, yuv_depth(fmt));
     const bool x8 = yuv_x8_ok(frame, w, fmt);
     const int cw = (w + 1) / 2, ch = (h + 1) / 2;
