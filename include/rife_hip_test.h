@@ -66,6 +66,21 @@ int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int 
 int rife_hip_op_image_to_resident(int gpuid, const rife_hip_image_t* host_img, int force_scalar, uint32_t* out_padded);
 int rife_hip_op_resident_to_image(int gpuid, const uint32_t* tight_frame, const rife_hip_image_t* host_img_out, int force_scalar);
 
+/* ---- the pre-split {hi, lo} f16 ("S16") trunk kernels alone (csrc/conv_t64.h, conv_rs.h, conv_rs2.h, conv_row.h, conv_ks.h), one launch per layer, on RAW S16
+ * tensors in host memory: 2 C / 16 planes [16-channel chunk][hi | lo] of rows x pitch pixels of 32 bytes, pixel (y, x) at (y + 1, x + 1), zero borders.
+ * op_s16_geom: the geometry of the tensor of a C x H x W trunk (S16Geom, csrc/engine_dispatch.h); needs no device. */
+int rife_hip_op_s16_geom(int C, int H, int W, int* pitch, int* rows, unsigned* plane_bytes, size_t* bytes);
+/* n_layers (1, 2) residual layers y = leaky(conv3x3(x) + bias + x) through the product's launcher of `kernel`, built by the product's layer upload as the engine
+ * builds a trunk layer.  weight [n][C][C][3][3] (exactly fp16 values), bias [n][C], slope [n] (one slope per layer).  in_s16[nb] / out_s16[nb]: tensors of `bytes`
+ * each; out_s16 is uploaded as given, the launches run in_s16 -> out_s16 (-> in_s16 for the second layer; RIFE_HIP_TRUNK_RS2: both layers in one launch), and the
+ * final tensor comes back in out_s16.  flip: the walking direction of the first launch (conv_t64: reverse, conv_rs / conv_rs2: descend), alternating per launch.
+ * cus > 0: persistent grids sized for that many compute units during the call (0 = the chip).  nb = 1 .. 4 tensors; nb > 1: the batched form of ROW / KS only.
+ * Shapes a launcher refuses (conv_rs below 7 rows, conv_rs2 below RS2_MIN_ROWS rows per segment, a channel count the kernel does not serve, weights that are not
+ * fp16, nb > 4) return -RIFE_HIP_EINVAL before anything is launched. */
+enum { RIFE_HIP_TRUNK_T64 = 0, RIFE_HIP_TRUNK_RS = 1, RIFE_HIP_TRUNK_RS2 = 2, RIFE_HIP_TRUNK_ROW = 3, RIFE_HIP_TRUNK_KS = 4 };
+int rife_hip_op_trunk(int gpuid, int kernel, int C, int H, int W, int n_layers, const float* weight, const float* bias, const float* slope, int flip, int cus,
+                      int nb, const void* const* in_s16, void* const* out_s16);
+
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */
 int rife_hip_pool_state(const rife_hip_t* r, int* pooled, int* leased, int* high_water);

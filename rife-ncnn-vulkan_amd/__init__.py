@@ -48,7 +48,10 @@ ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
-                    "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image"]
+                    "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk"]
+# rife_hip_op_trunk: which S16 trunk kernel (include/rife_hip_test.h RIFE_HIP_TRUNK_*)
+TRUNK_T64, TRUNK_RS, TRUNK_RS2, TRUNK_ROW, TRUNK_KS = 0, 1, 2, 3, 4
+EINVAL = 1      # RIFE_HIP_EINVAL: calls return its negative
 
 
 class rife_hip_image(ctypes.Structure):
@@ -130,6 +133,8 @@ def _load(path, with_test_surface):
         L.rife_hip_v4_tap_px.argtypes = [vp, vp, vp, ci, ci, cf, ci, ci, vp, ci, vp, ci]
         L.rife_hip_op_yuv_to_rgb10.argtypes = [ci, vp, ci, ci, ci, vp]
         L.rife_hip_op_rgb10_to_yuv.argtypes = [ci, vp, ci, ci, ci, vp]
+        L.rife_hip_op_s16_geom.argtypes = [ci, ci, ci, vp, vp, vp, vp]
+        L.rife_hip_op_trunk.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp]
     return L
 
 
@@ -154,7 +159,7 @@ def testlib():
 
 class _TestBuild:
     """`amd.test_build()`: the same Python surface on librife_hip_test.so - RIFE(...) engines with the parity taps and the RIFE_HIP_* kernel-selection switches,
-    op_conv3x3 / op_deconv4x4 / op_warp.  Everything else resolves to the package itself."""
+    op_conv3x3 / op_deconv4x4 / op_warp / op_trunk.  Everything else resolves to the package itself."""
 
     def __init__(self, mod):
         self._mod = mod
@@ -725,6 +730,38 @@ def op_warp(image, flow, gpuid=0):
     out = np.empty_like(image)
     _check(testlib().rife_hip_op_warp(gpuid, _p(image), _p(flow), c, h, w, _p(out)), "op_warp", testlib())
     return out
+
+
+def op_s16_geom(C, H, W):
+    """(pitch, rows, plane_bytes, bytes) of the S16 tensor of a C x H x W trunk (csrc/engine_dispatch.h S16Geom); needs no device."""
+    pitch, rows, plane, nbytes = ctypes.c_int(), ctypes.c_int(), ctypes.c_uint(), ctypes.c_size_t()
+    _check(testlib().rife_hip_op_s16_geom(int(C), int(H), int(W), ctypes.byref(pitch), ctypes.byref(rows), ctypes.byref(plane), ctypes.byref(nbytes)), "op_s16_geom", testlib())
+    return pitch.value, rows.value, plane.value, nbytes.value
+
+
+def op_trunk(kernel, C, H, W, weight, bias, slope, in_s16, out_s16, flip=0, cus=0, gpuid=0):
+    """One (weight (C, C, 3, 3)) or two (weight (2, C, C, 3, 3)) residual trunk layers through ONE S16 kernel's own launcher (kernel = TRUNK_T64 .. TRUNK_KS) on
+    raw S16 tensors: uint8 arrays of op_s16_geom(C, H, W)[3] bytes, or lists of up to four of them (the batched form of TRUNK_ROW / TRUNK_KS).  out_s16 goes to the
+    device as given (what the kernel does not write comes back unchanged); returns the final tensor(s) as new arrays.  slope: one value per layer."""
+    weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32)
+    n = 1 if weight.ndim == 4 else weight.shape[0]
+    if weight.size != n * C * C * 9 or bias.size != n * C:
+        raise ValueError("weight must be ([2,] C, C, 3, 3) and bias ([2,] C)")
+    sl = np.ascontiguousarray(np.broadcast_to(np.asarray(slope, np.float32), (n,)))
+    single = isinstance(in_s16, np.ndarray)
+    ins = [in_s16] if single else list(in_s16)
+    outs = [out_s16] if single else list(out_s16)
+    nbytes = op_s16_geom(C, H, W)[3]
+    if len(ins) != len(outs) or not ins:
+        raise ValueError("as many output tensors as input tensors, at least one")
+    ins = [np.ascontiguousarray(a, np.uint8).reshape(-1) for a in ins]
+    outs = [np.array(a, np.uint8).reshape(-1) for a in outs]      # copies: the call writes into them
+    if any(a.size != nbytes for a in ins + outs):
+        raise ValueError("an S16 tensor of this geometry has %d bytes" % nbytes)
+    pi = (ctypes.c_void_p * len(ins))(*[a.ctypes.data for a in ins])
+    po = (ctypes.c_void_p * len(outs))(*[a.ctypes.data for a in outs])
+    _check(testlib().rife_hip_op_trunk(gpuid, int(kernel), int(C), int(H), int(W), n, _p(weight), _p(bias), _p(sl), int(flip), int(cus), len(ins), pi, po), "op_trunk", testlib())
+    return outs[0] if single else outs
 
 
 def op_yuv_to_rgb10(buf, w, h, pixfmt, gpuid=0):

@@ -1305,6 +1305,97 @@ int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int 
     return 0;
 }
 
+// ---- the S16 trunk kernels alone: raw S16 tensors in and out, the product's layer upload and the product's launchers (tests/test_gpu_trunk_ops.py) ----
+int rife_hip_op_s16_geom(int C, int H, int W, int* pitch, int* rows, unsigned* plane_bytes, size_t* bytes) {
+    if (C <= 0 || C % 16 || H <= 0 || W <= 0) return fail(RIFE_HIP_EINVAL, "op_s16_geom: whole 16-channel chunks of a non-empty pixel grid");
+    const S16Geom G(H, W);
+    if ((unsigned long long)G.rows * G.pitch * 32ull * (C / 8) >= (1ull << 32)) return fail(RIFE_HIP_EINVAL, "op_s16_geom: S16 tensors stay below 4 GB");
+    if (pitch) *pitch = G.pitch;
+    if (rows) *rows = G.rows;
+    if (plane_bytes) *plane_bytes = G.plane();
+    if (bytes) *bytes = G.bytes(C);
+    return 0;
+}
+
+int rife_hip_op_trunk(int gpuid, int kernel, int C, int H, int W, int n_layers, const float* weight, const float* bias, const float* slope, int flip, int cus,
+                      int nb, const void* const* in_s16, void* const* out_s16) {
+    int rc;
+    size_t bytes = 0;
+    if ((rc = rife_hip_op_s16_geom(C, H, W, nullptr, nullptr, nullptr, &bytes))) return rc;
+    if (!weight || !bias || !slope || !in_s16 || !out_s16) return fail(RIFE_HIP_EINVAL, "op_trunk: null argument");
+    if (n_layers < 1 || n_layers > 2 || cus < 0) return fail(RIFE_HIP_EINVAL, "op_trunk: one or two layers, a CU budget >= 0");
+    if (nb < 1 || nb > 4) return fail(RIFE_HIP_EINVAL, "op_trunk: one to four tensors");
+    for (int k = 0; k < nb; k++)
+        if (!in_s16[k] || !out_s16[k]) return fail(RIFE_HIP_EINVAL, "op_trunk: null tensor");
+    const bool batched = kernel == RIFE_HIP_TRUNK_ROW || kernel == RIFE_HIP_TRUNK_KS;
+    if (nb > 1 && !batched) return fail(RIFE_HIP_EINVAL, "op_trunk: only conv_row and conv_ks have a batched form");
+    // what the launchers refuse, before anything is uploaded or launched
+    switch (kernel) {
+        case RIFE_HIP_TRUNK_T64: if (C != 64 && C != 96) return fail(RIFE_HIP_EINVAL, "conv_t64 serves 64 and 96 channels"); break;
+        case RIFE_HIP_TRUNK_RS:
+            if (C != 64) return fail(RIFE_HIP_EINVAL, "conv_rs serves 64 channels");
+            if ((H + 1) / 2 < RS_MIN_PAIRS) return fail(RIFE_HIP_EINVAL, "conv_rs needs at least " + std::to_string(2 * RS_MIN_PAIRS - 1) + " rows");
+            break;
+        case RIFE_HIP_TRUNK_RS2:
+            if (C != 64) return fail(RIFE_HIP_EINVAL, "conv_rs2 serves 64 channels");
+            if (n_layers != 2) return fail(RIFE_HIP_EINVAL, "conv_rs2 is two layers in one launch");
+            break;
+        case RIFE_HIP_TRUNK_ROW: if (C != 96 && C != 128 && C != 192) return fail(RIFE_HIP_EINVAL, "conv_row serves 96, 128 and 192 channels"); break;
+        case RIFE_HIP_TRUNK_KS: if (C != 96 && C != 128) return fail(RIFE_HIP_EINVAL, "conv_ks serves 96 and 128 channels"); break;
+        default: return fail(RIFE_HIP_EINVAL, "op_trunk: unknown kernel");
+    }
+    for (size_t i = 0; i < (size_t)n_layers * C * C * 9; i++)
+        if (!((float)(_Float16)weight[i] == weight[i])) return fail(RIFE_HIP_EINVAL, "op_trunk: the S16 kernels need weights that are exactly fp16");
+    if ((rc = check_device(gpuid))) return rc;
+    struct BudgetGuard { int keep; ~BudgetGuard() { tl_cu_budget = keep; } } budget_guard{tl_cu_budget};
+    tl_cu_budget = cus;
+    if (kernel == RIFE_HIP_TRUNK_RS2 && !rs2_applies(H, W)) return fail(RIFE_HIP_EINVAL, "conv_rs2 does not apply to this tensor");
+
+    ConvLayer L[2];
+    unsigned char* d[2][4] = {};                                         // [in | out][tensor]
+    auto cleanup = [&]() {
+        for (auto& s : d) for (unsigned char* p : s) (void)hipFree(p);
+        free_layer(L[0]); free_layer(L[1]);
+    };
+    for (int i = 0; i < n_layers; i++) {                                 // a trunk layer as rife_hip_load sets it up (engine_abi.h: setup(..., fold_skip = true))
+        L[i].cin = L[i].cout = C; L[i].stride = 1; L[i].deconv = false; L[i].epi = EPI_STORE; L[i].cls = "trunk";
+        L[i].tag = C == 64 ? 3 : 0;
+        L[i].skip = true; L[i].want_t64 = true; L[i].want_s16out = false;
+        if ((rc = upload_layer(L[i], weight + (size_t)i * C * C * 9, bias + (size_t)i * C, nullptr, slope[i]))) { cleanup(); return rc; }
+        if (!L[i].d_t64 || (C == 96 && !L[i].d_row)) { cleanup(); return fail(RIFE_HIP_EINVAL, "op_trunk: the layer upload made no S16 weight image"); }
+    }
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < nb && e == hipSuccess; k++) {
+        e = hipMalloc(&d[0][k], bytes);
+        if (e == hipSuccess) e = hipMalloc(&d[1][k], bytes);
+        if (e == hipSuccess) e = hipMemcpy(d[0][k], in_s16[k], bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d[1][k], out_s16[k], bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { cleanup(); return fail(RIFE_HIP_EHIP, std::string("op_trunk: ") + hipGetErrorString(e)); }
+    int cur = 0;                                                         // which of the two buffers holds the layer's input
+    const int nlaunch = kernel == RIFE_HIP_TRUNK_RS2 ? 1 : n_layers;
+    for (int i = 0; i < nlaunch && !rc; i++, cur ^= 1) {
+        const bool dir = ((flip != 0) ^ (i & 1)) != 0;
+        const unsigned char* const* pin = d[cur];
+        unsigned char* const* pout = d[cur ^ 1];
+        switch (kernel) {
+            case RIFE_HIP_TRUNK_T64: rc = launch_t64(L[i], pin[0], pout[0], H, W, 0, dir); break;
+            case RIFE_HIP_TRUNK_RS: rc = launch_rs(L[i], pin[0], pout[0], H, W, 0, dir); break;
+            case RIFE_HIP_TRUNK_RS2: rc = launch_rs2(L[0], L[1], pin[0], pout[0], H, W, 0, dir); break;
+            case RIFE_HIP_TRUNK_ROW: rc = nb > 1 ? launch_row(L[i], nullptr, nullptr, H, W, 0, nb, pin, pout) : launch_row(L[i], pin[0], pout[0], H, W, 0); break;
+            default: rc = nb > 1 ? launch_ks(L[i], nullptr, nullptr, H, W, 0, nb, pin, pout) : launch_ks(L[i], pin[0], pout[0], H, W, 0); break;
+        }
+    }
+    e = hipDeviceSynchronize();
+    if (!rc && e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("op_trunk: ") + hipGetErrorString(e));
+    for (int k = 0; k < nb && !rc; k++) {
+        e = hipMemcpy(out_s16[k], d[cur][k], bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("op_trunk: ") + hipGetErrorString(e));
+    }
+    cleanup();
+    return rc;
+}
+
 #endif  // RIFE_HIP_TEST_BUILD
 
 #ifdef RIFE_HIP_BENCH_BUILD
