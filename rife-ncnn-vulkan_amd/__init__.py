@@ -670,7 +670,8 @@ class RIFE:
     def v4_tap(self, in0image, in1image, timestep, what, b, inject, pixfmt=None):
         """what 0 / 1: 12-channel input of IFBlock b (unfused kernel / through the fused stem kernel); 2: blob out0 before the postproc;
         4 / 3: F (4 channels) and M as block b's stem finds them, after k_flow_update / as written by the stem that applies the last update itself;
-        5 (b = 3): the block input through the row-streaming stem kernel of the product."""
+        5 (b = 3): the block input through the row-streaming stem kernel of the product;
+        6 (b = 2, 3): F and M, (5, hp, wp), as k_flow_cascade<b> writes them from the b injected flows alone (4 is its sequential reference)."""
         self._need_taps()
         px = _pix_of(in0image, pixfmt)
         if px is not None and _pix_of(in1image, px) != px:
@@ -682,7 +683,7 @@ class RIFE:
         h, w = a.shape[:2]
         wp, hp = (w + 31) // 32 * 32, (h + 31) // 32 * 32
         s = {1: 4, 2: 2, 3: 1}.get(b, 1)
-        out = np.empty((4 if px == PIX_RGBA8 else 3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4) else (12, hp // s, wp // s), np.float32)
+        out = np.empty((4 if px == PIX_RGBA8 else 3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4, 6) else (12, hp // s, wp // s), np.float32)
         inj = [np.ascontiguousarray(f, dtype=np.float32) for f in inject]
         arr = (ctypes.c_void_p * max(1, len(inj)))(*[f.ctypes.data for f in inj])
         if px is not None:

@@ -272,6 +272,7 @@ __device__ __forceinline__ void up_coeff(int d, int S, int in, int& s0, float& a
 // One full-resolution pixel of the flow update after a block (flownet.param:47-58, 99-105, 152-158): u = Interp(S)(flow_b) at (x, y);
 // F = F * 1 + u[0:4] * S (Eltwise with coefficients), M = M + u[4].  flow_b is kept as [hp / S][wp / S][8] fp32 {x, y, z, w, mask, unused, 0, 0}.
 // Shared by k_flow_update<S> and by the fused stems that apply the update of the block before them while they gather (stem_fused.h).
+#define RIFE_UP(c00, c01, c10, c11) (((c00) * a0 + (c01) * a1) * b0 + ((c10) * a0 + (c11) * a1) * b1)
 template <int S>
 __device__ __forceinline__ void flow_upsampled(const float* __restrict__ flow, int wp, int hp, int x, int y, float4& u, float& um) {
     const int Wb = wp / S, Hb = hp / S;
@@ -283,22 +284,37 @@ __device__ __forceinline__ void flow_upsampled(const float* __restrict__ flow, i
     const float4 q00 = *reinterpret_cast<const float4*>(p00), q01 = *reinterpret_cast<const float4*>(p00 + 8);
     const float4 q10 = *reinterpret_cast<const float4*>(p10), q11 = *reinterpret_cast<const float4*>(p10 + 8);
     const float m00 = p00[4], m01 = p00[12], m10 = p10[4], m11 = p10[12];
-#define RIFE_UP(c00, c01, c10, c11) (((c00) * a0 + (c01) * a1) * b0 + ((c10) * a0 + (c11) * a1) * b1)
     u.x = RIFE_UP(q00.x, q01.x, q10.x, q11.x);
     u.y = RIFE_UP(q00.y, q01.y, q10.y, q11.y);
     u.z = RIFE_UP(q00.z, q01.z, q10.z, q11.z);
     u.w = RIFE_UP(q00.w, q01.w, q10.w, q11.w);
     um = RIFE_UP(m00, m01, m10, m11);
-#undef RIFE_UP
 }
+// The same interpolation with the cell pair rows handed in: p00 -> records (sy, sx), (sy, sx + 1), p10 -> (sy + 1, sx), (sy + 1, sx + 1), from any address
+// space (k_flow_cascade reads them from LDS); a0, a1, b0, b1 are up_coeff's for the pixel.  Same expression, same order: the bits of flow_upsampled.
+__device__ __forceinline__ void flow_upsampled_cells(const float* p00, const float* p10, float a0, float a1, float b0, float b1, float4& u, float& um) {
+    const float4 q00 = *reinterpret_cast<const float4*>(p00), q01 = *reinterpret_cast<const float4*>(p00 + 8);
+    const float4 q10 = *reinterpret_cast<const float4*>(p10), q11 = *reinterpret_cast<const float4*>(p10 + 8);
+    const float m00 = p00[4], m01 = p00[12], m10 = p10[4], m11 = p10[12];
+    u.x = RIFE_UP(q00.x, q01.x, q10.x, q11.x);
+    u.y = RIFE_UP(q00.y, q01.y, q10.y, q11.y);
+    u.z = RIFE_UP(q00.z, q01.z, q10.z, q11.z);
+    u.w = RIFE_UP(q00.w, q01.w, q10.w, q11.w);
+    um = RIFE_UP(m00, m01, m10, m11);
+}
+#undef RIFE_UP
 // the FIRST update (after block 0): F = u[0:4] * S, M = u[4] (k_flow_update<S, true>)
+template <int S>
+__device__ __forceinline__ void flow_first_of(const float4 u, const float um, float4& f, float& m) {
+    const float s = (float)S;
+    f = make_float4(u.x * s, u.y * s, u.z * s, u.w * s);
+    m = um;
+}
 template <int S>
 __device__ __forceinline__ void flow_first(const float* __restrict__ flow, int wp, int hp, int x, int y, float4& f, float& m) {
     float4 u; float um;
     flow_upsampled<S>(flow, wp, hp, x, y, u, um);
-    const float s = (float)S;
-    f = make_float4(u.x * s, u.y * s, u.z * s, u.w * s);
-    m = um;
+    flow_first_of<S>(u, um, f, m);
 }
 template <int S>
 __device__ __forceinline__ void flow_accumulate(const float4 u, const float um, float4& f, float& m) {

@@ -38,6 +38,7 @@
 #include "conv_mfma.h"
 #include "conv_img.h"
 #include "elementwise.h"
+#include "flow_cascade.h"
 #include "yuv.h"
 #include "planes.h"
 #include "image_check.h"

@@ -918,8 +918,9 @@ int rife_hip_v4_extract_flow_px(const rife_hip_t* E, const void* in0, const void
 // k_flow_update into F, M (flownet.param:47-58, 99-105, 152-158).
 // `pending` != null: as in run_v4, the update of the LAST injected flow is left to the fused stem of the next block where the product does so
 // (flow_update_fused_into); *pending is then that flow.
+// `updates` false (tap 6): the injected flows are placed and F, M are left to the caller.
 static int tap_prologue(const rife_hip_t* E, Ctx& c, const uint8_t* in0, const uint8_t* in1, int w, int h, const float* const* inject, int n_inject, float*& tmp,
-                        const float** pending = nullptr, int pixfmt = RIFE_HIP_PIX_RGB8) {
+                        const float** pending = nullptr, int pixfmt = RIFE_HIP_PIX_RGB8, bool updates = true) {
     int rc;
     if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
     c.own_stream = true;
@@ -934,6 +935,7 @@ static int tap_prologue(const rife_hip_t* E, Ctx& c, const uint8_t* in0, const u
         const int s = E->blk[k].scale, Hb = c.hp / s, Wb = c.wp / s;
         HIPCHK(hipMemcpyAsync(tmp, inject[k], (size_t)Hb * Wb * 6 * 4, hipMemcpyHostToDevice, c.stream));
         hipLaunchKernelGGL(k_chw_to_nhwc, grid2d(Wb, Hb), dim3(256), 0, c.stream, tmp, c.flow[k], 6, Hb, Wb, 8);
+        if (!updates) continue;
         if (pending && k == n_inject - 1 && k < 3 && flow_update_fused_into(*E, c, k + 1)) { *pending = c.flow[k]; continue; }
         if (k < 3 && (rc = run_flow_update(*E, c, k))) return rc;
     }
@@ -950,6 +952,7 @@ static int tap_prologue(const rife_hip_t* E, Ctx& c, const uint8_t* in0, const u
 // what = 2: blob out0 (flownet.param:217) before the postproc, from the unfused float tail k_final_float (b ignored; n_inject = 4);
 // what = 4 / 3: F, M as block b's stem reads them: after k_flow_update / written by the stem that applies the update of flow{b-1} itself.
 // what = 5: block 3's input through stem_rs_kernel, the product's kernel for that block (see below).
+// what = 6: F, M as k_flow_cascade<b> (flow_cascade.h) writes them from the b injected flows alone, b = 2 / 3; what = 4 is its sequential reference.
 // out: planar CHW fp32, 12 x hp/S x wp/S (what 0, 1) or 3 x hp x wp (what 2).  n_inject must be b (what 0, 1) or 4 (what 2).
 static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, int what, int b,
                                 const float* const* inject, int n_inject, float* out, int pixfmt = RIFE_HIP_PIX_RGB8) {
@@ -959,13 +962,14 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
     if (pix_bpp(pixfmt) == 0) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
     if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if (pixfmt && what == 3) return fail(RIFE_HIP_EINVAL, "tap 3 (an A/B form the product does not run) is served for RGB8 frames only");
-    if (what < 0 || what > 5) return fail(RIFE_HIP_EINVAL, "bad tap");
+    if (what < 0 || what > 6) return fail(RIFE_HIP_EINVAL, "bad tap");
+    if (what == 6 && b != 2 && b != 3) return fail(RIFE_HIP_EINVAL, "the flow cascade runs after block 1 (b = 2) or block 2 (b = 3)");
     if (what == 5 && b != 3) return fail(RIFE_HIP_EINVAL, "the row-streaming stem kernel serves block 3");
     if (what == 2 ? n_inject != 4 : (b < 1 || b > 3 || n_inject != b)) return fail(RIFE_HIP_EINVAL, "bad block / injection count");
     if ((rc = check_device(E->gpuid))) return rc;
     Ctx c; float* tmp = nullptr;
     const float* pending = nullptr;
-    if ((rc = tap_prologue(E, c, in0, in1, w, h, inject, n_inject, tmp, (what == 1 || what == 3) ? &pending : nullptr, pixfmt))) return rc;
+    if ((rc = tap_prologue(E, c, in0, in1, w, h, inject, n_inject, tmp, (what == 1 || what == 3) ? &pending : nullptr, pixfmt, what != 6))) return rc;
     hipStream_t st = c.stream;
     // what = 3 / 4: F (4 channels) and M as block b's stem finds them, [5][hp][wp]: 4 = after k_flow_update, 3 = as written by the stem that applies
     // the last update itself (only where the product fuses it: EINVAL otherwise)
@@ -979,6 +983,12 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
         return 0;
     };
     if (what == 4) return copy_fm(c.F, c.M);
+    if (what == 6) {
+        if (b == 2) launch_flow_cascade<2>(st, c.flow[0], c.flow[1], nullptr, c.F, c.M, c.wp, c.hp);
+        else launch_flow_cascade<3>(st, c.flow[0], c.flow[1], c.flow[2], c.F, c.M, c.wp, c.hp);
+        HIPCHK(hipGetLastError());
+        return copy_fm(c.F, c.M);
+    }
     if (what == 5) {
         // Block 3's input THROUGH THE PRODUCT'S ROW-STREAMING STEM KERNEL stem_rs_kernel (stem_rs.h): both of its convolutions run with one-hot
         // weights.  Stem 0: output channel 12 j + k = input channel k under tap (1 + g, 1 + j) (pixel parity p = 2 g + j of the block input; two

@@ -185,6 +185,8 @@ struct rife_hip {
     // instead of two k_flow_update launches.  Bit-identical, and measured SLOWER at 4K (432 vs 442 frames/s, same call): the update kernels
     // run at 6 - 7 TB/s, the stems are bound by gather latency and VALU issue and every load added to them costs more than the pass it removes
     // (stem0_b3 0.210 -> 0.285, stem0_b2 0.161 -> 0.272, flow_update 0.191 -> 0.034 ms per pair).  Off in the product.
+    // The product's update passes no longer re-read F, M either: after blocks 1 and 2 k_flow_cascade (flow_cascade.h) writes them from flow0..flow2 alone,
+    // staged through LDS (run_v4; RIFE_HIP_FLOW_CASCADE=0 in the test build: k_flow_update2 + k_flow_update<2, false>, which read F, M back after block 2).
     bool fuse_flow = false;
     int flow_div(int b) const { return v40 ? 2 * blk[b].scale : blk[b].scale; }
     // rife-v2.x schedule (IFNet + ContextNet + FusionNet)

@@ -471,16 +471,30 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
     // The update after block 0 never reaches HBM on its own (round 5): block 1's scale-4 stem samples it from flow0 (assemble_pixel UPD = 2) and ONE pass after
     // block 1 writes F, M with both updates applied (k_flow_update2) - bit for bit the tensors of the two-kernel sequence, one launch and 20 B / pixel of writes +
     // 20 B / pixel of reads less.  RIFE_HIP_MERGE_FLOW0=0 (A/B, test build): the three separate updates.
-    const bool merge_env = read_switches().merge_flow0;      // per call
+    const Switches sw = read_switches();                     // per call
+    const bool merge_env = sw.merge_flow0;
     const bool merge0 = merge_env && !E.v40 && trunk_h2() && g_fuse_stem && E.blk[1].stem0.d_wh != nullptr && E.blk[1].scale == 4 && !flow_update_fused_into(E, c, 1) &&
                         !flow_update_fused_into(E, c, 2);
+    // Both passes over F, M as cascades over the coarse flows (flow_cascade.h): F, M after block 2 are a function of flow0, flow1, flow2, so the pass after
+    // block 2 writes them again from the flows instead of reading them back to add one term - the same per-pixel expressions in the same order, the same bits.
+    // This needs flow0 and flow1 unchanged until the end of block 2: c.flow[b] is an allocation of its own (ensure_ctx_dims_impl), written by block b's head
+    // (run_block_convs) and by nothing else in this schedule - the stems and trunks write X, S1, T0..T2 / the S16 planes, the updates write F, M.
+    // RIFE_HIP_FLOW_CASCADE=0 (A/B, test build): k_flow_update2 and k_flow_update<2, false>.
+    const bool cascade = merge0 && sw.flow_cascade && !flow_update_fused_into(E, c, 3);
     for (int b = 0; b < 4; b++) {
         if ((rc = run_block_convs(E, c, b, timestep, (b == 3 && fuse_tail) ? &fin : nullptr, tsp, PH_ALL, pending, (merge0 && b == 1) ? c.flow[0] : nullptr))) return rc;
         pending = nullptr;
         if (merge0 && b == 0) continue;
         if (merge0 && b == 1) {
             Timed t(E.prof, "flow_update", 0, st);
-            hipLaunchKernelGGL((k_flow_update2<8, 4>), grid2d(c.wp, c.hp), dim3(256), 0, st, c.flow[0], c.flow[1], c.F, c.M, c.wp, c.hp);
+            if (cascade) launch_flow_cascade<2>(st, c.flow[0], c.flow[1], nullptr, c.F, c.M, c.wp, c.hp);
+            else hipLaunchKernelGGL((k_flow_update2<8, 4>), grid2d(c.wp, c.hp), dim3(256), 0, st, c.flow[0], c.flow[1], c.F, c.M, c.wp, c.hp);
+            HIPCHK(hipGetLastError());
+            continue;
+        }
+        if (cascade && b == 2) {
+            Timed t(E.prof, "flow_update", 0, st);
+            launch_flow_cascade<3>(st, c.flow[0], c.flow[1], c.flow[2], c.F, c.M, c.wp, c.hp);
             HIPCHK(hipGetLastError());
             continue;
         }
