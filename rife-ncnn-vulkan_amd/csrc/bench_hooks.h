@@ -20,11 +20,10 @@ int rife_hip_bench_conv8(int gpuid, int c, int h, int w, int variant, int iters,
     a.Ho = h; a.Wo = w; a.Cout = c; a.nchunks = L.nchunks8; a.nz = 1; a.tiles_x = (w + 31) / 32; a.ntiles_xy = a.tiles_x * ((h + 7) / 8);
     constexpr int lds = conv8_lds_bytes<2, 8>();
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    auto run = [&](auto kfn) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        for (int i = 0; i < 3; i++) hipLaunchKernelGGL(kfn, dim3(a.ntiles_xy), dim3(512), lds, 0, a);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 3; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(a.ntiles_xy), dim3(512), lds, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
-        for (int i = 0; i < iters; i++) hipLaunchKernelGGL(kfn, dim3(a.ntiles_xy), dim3(512), lds, 0, a);
+        for (int i = 0; i < iters; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(a.ntiles_xy), dim3(512), lds, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
         float t = 0; HIPCHK(hipEventElapsedTime(&t, e0, e1));
@@ -32,12 +31,12 @@ int rife_hip_bench_conv8(int gpuid, int c, int h, int w, int variant, int iters,
         return 0;
     };
     switch (variant) {
-        case 0: rc = run(conv_mfma8_kernel<2, 8, 4, 4096>); break;
-        case 256: rc = run(conv_mfma8_kernel<2, 8, 4, 4096 + 256>); break;
-        case 512: rc = run(conv_mfma8_kernel<2, 8, 4, 4096 + 512>); break;
-        case 1024: rc = run(conv_mfma8_kernel<2, 8, 4, 4096 + 1024>); break;
-        case 768: rc = run(conv_mfma8_kernel<2, 8, 4, 4096 + 768>); break;
-        case 1792: rc = run(conv_mfma8_kernel<2, 8, 4, 4096 + 1792>); break;
+        case 0: rc = run(constant<conv_mfma8_kernel<2, 8, 4, 4096>>{}); break;
+        case 256: rc = run(constant<conv_mfma8_kernel<2, 8, 4, 4096 + 256>>{}); break;
+        case 512: rc = run(constant<conv_mfma8_kernel<2, 8, 4, 4096 + 512>>{}); break;
+        case 1024: rc = run(constant<conv_mfma8_kernel<2, 8, 4, 4096 + 1024>>{}); break;
+        case 768: rc = run(constant<conv_mfma8_kernel<2, 8, 4, 4096 + 768>>{}); break;
+        case 1792: rc = run(constant<conv_mfma8_kernel<2, 8, 4, 4096 + 1792>>{}); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
     }
     (void)hipFree(x); (void)hipFree(y); free_layer(L);
@@ -301,13 +300,12 @@ int rife_hip_bench_h2b(int gpuid, int h, int w, int variant, int iters, float* m
     constexpr int lds = convh2b_lds_bytes<2, 10>();
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     const bool pingpong = variant == 8192;
-    auto run = [&](auto kfn) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        for (int i = 0; i < 3; i++) hipLaunchKernelGGL(kfn, dim3(a.ntiles_xy), dim3(512), lds, 0, a);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 3; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(a.ntiles_xy), dim3(512), lds, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
         for (int i = 0; i < iters; i++) {
             if (pingpong) { a.in = (i & 1) ? y : x; a.out = (i & 1) ? x : y; }     // like consecutive trunk layers: read what the last launch wrote
-            hipLaunchKernelGGL(kfn, dim3(a.ntiles_xy), dim3(512), lds, 0, a);
+            if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(a.ntiles_xy), dim3(512), lds, 0, a)) return lrc;
         }
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
@@ -321,8 +319,7 @@ int rife_hip_bench_h2b(int gpuid, int h, int w, int variant, int iters, float* m
         HIPCHK(hipMalloc(&stamps, nst * 8));
         HIPCHK(hipMemset(stamps, 0, nst * 8));
         a.partial = reinterpret_cast<float*>(stamps);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_h2b_kernel<2, 10, 4096 + 32768>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        for (int i = 0; i < 3; i++) hipLaunchKernelGGL((conv_h2b_kernel<2, 10, 4096 + 32768>), dim3(a.ntiles_xy), dim3(512), lds, 0, a);
+        for (int i = 0; i < 3; i++) if (int lrc = launch<conv_h2b_kernel<2, 10, 4096 + 32768>>("bench launch", dim3(a.ntiles_xy), dim3(512), lds, 0, a)) return lrc;
         HIPCHK(hipDeviceSynchronize());
         std::vector<long long> hs(nst);
         HIPCHK(hipMemcpy(hs.data(), stamps, nst * 8, hipMemcpyDeviceToHost));
@@ -332,15 +329,15 @@ int rife_hip_bench_h2b(int gpuid, int h, int w, int variant, int iters, float* m
         return 0;
     }
     switch (variant) {
-        case 8192: rc = run(conv_h2b_kernel<2, 10, 4096>); break;
-        case 0: rc = run(conv_h2b_kernel<2, 10, 4096>); break;
-        case 256: rc = run(conv_h2b_kernel<2, 10, 4096 + 256>); break;
-        case 512: rc = run(conv_h2b_kernel<2, 10, 4096 + 512>); break;
-        case 1024: rc = run(conv_h2b_kernel<2, 10, 4096 + 1024>); break;
-        case 2048: rc = run(conv_h2b_kernel<2, 10, 4096 + 2048>); break;
-        case 2560: rc = run(conv_h2b_kernel<2, 10, 4096 + 2560>); break;
-        case 2816: rc = run(conv_h2b_kernel<2, 10, 4096 + 2816>); break;
-        case 3840: rc = run(conv_h2b_kernel<2, 10, 4096 + 3840>); break;
+        case 8192: rc = run(constant<conv_h2b_kernel<2, 10, 4096>>{}); break;
+        case 0: rc = run(constant<conv_h2b_kernel<2, 10, 4096>>{}); break;
+        case 256: rc = run(constant<conv_h2b_kernel<2, 10, 4096 + 256>>{}); break;
+        case 512: rc = run(constant<conv_h2b_kernel<2, 10, 4096 + 512>>{}); break;
+        case 1024: rc = run(constant<conv_h2b_kernel<2, 10, 4096 + 1024>>{}); break;
+        case 2048: rc = run(constant<conv_h2b_kernel<2, 10, 4096 + 2048>>{}); break;
+        case 2560: rc = run(constant<conv_h2b_kernel<2, 10, 4096 + 2560>>{}); break;
+        case 2816: rc = run(constant<conv_h2b_kernel<2, 10, 4096 + 2816>>{}); break;
+        case 3840: rc = run(constant<conv_h2b_kernel<2, 10, 4096 + 3840>>{}); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
     }
     (void)hipFree(x); (void)hipFree(y); free_layer(L);
@@ -385,15 +382,14 @@ int rife_hip_bench_t64(int gpuid, int h, int w, int variant, int iters, float* m
     const int nwg = std::min(t64_wg_per_cu(2) * (cus / 8 * 8), (a.ntiles + 7) / 8 * 8);
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     long long* clk_base = nullptr;
-    auto run = [&](auto kfn) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, T64_LDS));
-        for (int i = 0; i < 3; i++) hipLaunchKernelGGL(kfn, dim3(nwg), dim3(T64_NTHR), T64_LDS, 0, a);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 3; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(T64_NTHR), T64_LDS, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
         for (int i = 0; i < iters; i++) {
             a.in = (i & 1) ? y : x; a.out = (i & 1) ? x : y;
             a.reverse = alternate ? (i & 1) : 0;
             if (clk_base) a.stamps = clk_base + (size_t)std::min(i, 255) * nwg * 4;     // clock probe: launches 0 .. 254 keep their own records
-            hipLaunchKernelGGL(kfn, dim3(nwg), dim3(T64_NTHR), T64_LDS, 0, a);
+            if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(T64_NTHR), T64_LDS, 0, a)) return lrc;
         }
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
@@ -406,13 +402,13 @@ int rife_hip_bench_t64(int gpuid, int h, int w, int variant, int iters, float* m
         HIPCHK(hipMemset(clk_base, 0, (size_t)nwg * 32 * 256));
         a.stamps = clk_base;
         switch (variant & ~T64_CLK) {
-            case 0: rc = run(conv_t64_kernel<T64_CLK>); break;
-            case T64_NOSTORE: rc = run(conv_t64_kernel<T64_CLK | T64_NOSTORE>); break;
-            case T64_NODMA: rc = run(conv_t64_kernel<T64_CLK | T64_NODMA>); break;
-            case T64_NOMATH: rc = run(conv_t64_kernel<T64_CLK | T64_NOMATH>); break;
-            case T64_NODMA | T64_NOSTORE: rc = run(conv_t64_kernel<T64_CLK | T64_NODMA | T64_NOSTORE>); break;
-            case T64_NOMATH | T64_NOSTORE: rc = run(conv_t64_kernel<T64_CLK | T64_NOMATH | T64_NOSTORE>); break;
-            case T64_NOMATH | T64_NODMA: rc = run(conv_t64_kernel<T64_CLK | T64_NOMATH | T64_NODMA>); break;
+            case 0: rc = run(constant<conv_t64_kernel<T64_CLK>>{}); break;
+            case T64_NOSTORE: rc = run(constant<conv_t64_kernel<T64_CLK | T64_NOSTORE>>{}); break;
+            case T64_NODMA: rc = run(constant<conv_t64_kernel<T64_CLK | T64_NODMA>>{}); break;
+            case T64_NOMATH: rc = run(constant<conv_t64_kernel<T64_CLK | T64_NOMATH>>{}); break;
+            case T64_NODMA | T64_NOSTORE: rc = run(constant<conv_t64_kernel<T64_CLK | T64_NODMA | T64_NOSTORE>>{}); break;
+            case T64_NOMATH | T64_NOSTORE: rc = run(constant<conv_t64_kernel<T64_CLK | T64_NOMATH | T64_NOSTORE>>{}); break;
+            case T64_NOMATH | T64_NODMA: rc = run(constant<conv_t64_kernel<T64_CLK | T64_NOMATH | T64_NODMA>>{}); break;
             default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
         }
         const int nl = std::min(iters, 255);
@@ -440,20 +436,20 @@ int rife_hip_bench_t64(int gpuid, int h, int w, int variant, int iters, float* m
         const size_t nst = (size_t)nwg * T64_TH * 32 * 4;
         HIPCHK(hipMalloc(&a.stamps, nst * 8));
         HIPCHK(hipMemset(a.stamps, 0, nst * 8));
-        rc = run(conv_t64_kernel<T64_STAMPS>);
+        rc = run(constant<conv_t64_kernel<T64_STAMPS>>{});
         std::vector<long long> hs(nst);
         HIPCHK(hipMemcpy(hs.data(), a.stamps, nst * 8, hipMemcpyDeviceToHost));
         if (FILE* f = fopen("gpurun_out/t64_stamps.bin", "wb")) { fwrite(hs.data(), 8, nst, f); fclose(f); }
         (void)hipFree(a.stamps);
     } else switch (variant) {
-        case 0: rc = run(conv_t64_kernel<0>); break;
-        case T64_NOSTORE: rc = run(conv_t64_kernel<T64_NOSTORE>); break;
-        case T64_NODMA: rc = run(conv_t64_kernel<T64_NODMA>); break;
-        case T64_NOMATH: rc = run(conv_t64_kernel<T64_NOMATH>); break;
-        case T64_NOVMWAIT: rc = run(conv_t64_kernel<T64_NOVMWAIT>); break;
-        case T64_NODMA | T64_NOSTORE: rc = run(conv_t64_kernel<T64_NODMA | T64_NOSTORE>); break;
-        case T64_NOMATH | T64_NOSTORE: rc = run(conv_t64_kernel<T64_NOMATH | T64_NOSTORE>); break;
-        case T64_NOMATH | T64_NODMA: rc = run(conv_t64_kernel<T64_NOMATH | T64_NODMA>); break;
+        case 0: rc = run(constant<conv_t64_kernel<0>>{}); break;
+        case T64_NOSTORE: rc = run(constant<conv_t64_kernel<T64_NOSTORE>>{}); break;
+        case T64_NODMA: rc = run(constant<conv_t64_kernel<T64_NODMA>>{}); break;
+        case T64_NOMATH: rc = run(constant<conv_t64_kernel<T64_NOMATH>>{}); break;
+        case T64_NOVMWAIT: rc = run(constant<conv_t64_kernel<T64_NOVMWAIT>>{}); break;
+        case T64_NODMA | T64_NOSTORE: rc = run(constant<conv_t64_kernel<T64_NODMA | T64_NOSTORE>>{}); break;
+        case T64_NOMATH | T64_NOSTORE: rc = run(constant<conv_t64_kernel<T64_NOMATH | T64_NOSTORE>>{}); break;
+        case T64_NOMATH | T64_NODMA: rc = run(constant<conv_t64_kernel<T64_NOMATH | T64_NODMA>>{}); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
     }
     (void)hipFree(x); (void)hipFree(y); (void)hipFree(dimg); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -511,13 +507,12 @@ static int bench_ks_cfg(int gpuid, int h, int w, int variant, int iters, int div
     HIPCHK(hipMemset(dst, 0, (size_t)nwg * 16 * 8));
     a.stamps = dst;
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    auto run = [&](auto kfn) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS));
-        for (int i = 0; i < 3; i++) hipLaunchKernelGGL(kfn, dim3(nwg), dim3(K::NTHR), K::LDS, 0, a);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 3; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(K::NTHR), K::LDS, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
         for (int i = 0; i < iters; i++) {
             a.in = (i & 1) ? y : x; a.out = (i & 1) ? x : y;
-            hipLaunchKernelGGL(kfn, dim3(nwg), dim3(K::NTHR), K::LDS, 0, a);
+            if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(K::NTHR), K::LDS, 0, a)) return lrc;
         }
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
@@ -527,14 +522,14 @@ static int bench_ks_cfg(int gpuid, int h, int w, int variant, int iters, int div
     };
     int rc;
     switch (variant) {
-        case 0: rc = run(conv_ks_kernel<C, NB, CPW, 0>); break;
-        case KS_CLK: rc = run(conv_ks_kernel<C, NB, CPW, KS_CLK>); break;
-        case KS_NOMATH: rc = run(conv_ks_kernel<C, NB, CPW, KS_NOMATH>); break;
-        case KS_NODMA: rc = run(conv_ks_kernel<C, NB, CPW, KS_NODMA>); break;
-        case KS_NOSTORE: rc = run(conv_ks_kernel<C, NB, CPW, KS_NOSTORE>); break;
-        case KS_NOWEIGHTS: rc = run(conv_ks_kernel<C, NB, CPW, KS_NOWEIGHTS>); break;
-        case KS_NOMATH | KS_NODMA | KS_NOSTORE | KS_NOWEIGHTS: rc = run(conv_ks_kernel<C, NB, CPW, KS_NOMATH | KS_NODMA | KS_NOSTORE | KS_NOWEIGHTS>); break;
-        case KS_NODMA | KS_NOSTORE: rc = run(conv_ks_kernel<C, NB, CPW, KS_NODMA | KS_NOSTORE>); break;
+        case 0: rc = run(constant<conv_ks_kernel<C, NB, CPW, 0>>{}); break;
+        case KS_CLK: rc = run(constant<conv_ks_kernel<C, NB, CPW, KS_CLK>>{}); break;
+        case KS_NOMATH: rc = run(constant<conv_ks_kernel<C, NB, CPW, KS_NOMATH>>{}); break;
+        case KS_NODMA: rc = run(constant<conv_ks_kernel<C, NB, CPW, KS_NODMA>>{}); break;
+        case KS_NOSTORE: rc = run(constant<conv_ks_kernel<C, NB, CPW, KS_NOSTORE>>{}); break;
+        case KS_NOWEIGHTS: rc = run(constant<conv_ks_kernel<C, NB, CPW, KS_NOWEIGHTS>>{}); break;
+        case KS_NOMATH | KS_NODMA | KS_NOSTORE | KS_NOWEIGHTS: rc = run(constant<conv_ks_kernel<C, NB, CPW, KS_NOMATH | KS_NODMA | KS_NOSTORE | KS_NOWEIGHTS>>{}); break;
+        case KS_NODMA | KS_NOSTORE: rc = run(constant<conv_ks_kernel<C, NB, CPW, KS_NODMA | KS_NOSTORE>>{}); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown conv_ks bench variant");
     }
     if (!rc && stamps_out) HIPCHK(hipMemcpy(stamps_out, dst, (size_t)nwg * 16 * 8, hipMemcpyDeviceToHost));
@@ -590,22 +585,20 @@ int rife_hip_bench_rs(int gpuid, int h, int w, int variant, int iters, float* ms
     const int nwg = std::min(gover ? gover : cus, a.nunits);
     const bool alternate = (variant & 0x10000) != 0, up = (variant & 0x20000) != 0;
     variant &= 0xffff | RS_CLK;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_rs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS));
     if (stats) {
         for (int i = 0; i < 8; i++) stats[i] = -1;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_t64_kernel<3, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, T64_LDS));
         T64Args t;
         t.in = x; t.out = yr; t.img = dimg; t.H = h; t.W = w; t.pitch = G.pitch; t.plane = G.plane(); t.tiles_x = G.tiles_x; t.ntiles = G.tiles_x * G.tiles_y; t.reverse = 0; t.nchunks = 4; t.nnt = 1;
         const int twg = std::min(t64_wg_per_cu(2) * (cus / 8 * 8), (t.ntiles + 7) / 8 * 8);
         HIPCHK(hipMemset(yr, 0, nb));
-        hipLaunchKernelGGL((conv_t64_kernel<3, 2>), dim3(twg), dim3(T64_NTHR), T64_LDS, 0, t);
+        if (int lrc = launch<conv_t64_kernel<3, 2>>("bench launch", dim3(twg), dim3(T64_NTHR), T64_LDS, 0, t)) return lrc;
         HIPCHK(hipDeviceSynchronize());
         std::vector<unsigned char> ref(nb), got(nb);
         HIPCHK(hipMemcpy(ref.data(), yr, nb, hipMemcpyDeviceToHost));
         for (int dir = 0; dir < 2; dir++) {
             HIPCHK(hipMemset(y, 0, nb));
             a.descend = dir;
-            hipLaunchKernelGGL((conv_rs_kernel<0>), dim3(nwg), dim3(RS_NTHR), RS_LDS, 0, a);
+            if (int lrc = launch<conv_rs_kernel<0>>("bench launch", dim3(nwg), dim3(RS_NTHR), RS_LDS, 0, a)) return lrc;
             HIPCHK(hipDeviceSynchronize());
             HIPCHK(hipMemcpy(got.data(), y, nb, hipMemcpyDeviceToHost));
             // bytes that differ, and the largest difference of the values hi + lo the two kernels stored (another summation order only
@@ -633,15 +626,14 @@ int rife_hip_bench_rs(int gpuid, int h, int w, int variant, int iters, float* ms
     }
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     long long* clk_base = nullptr;
-    auto run = [&](auto kfn) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS));
-        for (int i = 0; i < 3; i++) hipLaunchKernelGGL(kfn, dim3(nwg), dim3(RS_NTHR), RS_LDS, 0, a);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 3; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(RS_NTHR), RS_LDS, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
         for (int i = 0; i < iters; i++) {
             a.in = (i & 1) ? y : x; a.out = (i & 1) ? x : y;
             a.descend = up ? 1 : (alternate ? (i & 1) : 0);
             if (clk_base) a.stamps = clk_base + (size_t)std::min(i, 255) * nwg * 4;
-            hipLaunchKernelGGL(kfn, dim3(nwg), dim3(RS_NTHR), RS_LDS, 0, a);
+            if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(RS_NTHR), RS_LDS, 0, a)) return lrc;
         }
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
@@ -654,9 +646,9 @@ int rife_hip_bench_rs(int gpuid, int h, int w, int variant, int iters, float* ms
         HIPCHK(hipMemset(clk_base, 0, (size_t)nwg * 32 * 256));
         a.stamps = clk_base;
         switch (variant & ~RS_CLK) {
-            case 0: rc = run(conv_rs_kernel<RS_CLK>); break;
-            case RS_NOMATH: rc = run(conv_rs_kernel<RS_CLK | RS_NOMATH>); break;
-            case RS_NODMA | RS_NOSTORE: rc = run(conv_rs_kernel<RS_CLK | RS_NODMA | RS_NOSTORE>); break;
+            case 0: rc = run(constant<conv_rs_kernel<RS_CLK>>{}); break;
+            case RS_NOMATH: rc = run(constant<conv_rs_kernel<RS_CLK | RS_NOMATH>>{}); break;
+            case RS_NODMA | RS_NOSTORE: rc = run(constant<conv_rs_kernel<RS_CLK | RS_NODMA | RS_NOSTORE>>{}); break;
             default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
         }
         const int nl = std::min(iters, 255);
@@ -679,17 +671,17 @@ int rife_hip_bench_rs(int gpuid, int h, int w, int variant, int iters, float* ms
         }
         (void)hipFree(clk_base);
     } else switch (variant) {
-        case 0: rc = run(conv_rs_kernel<0>); break;
-        case RS_NOSTORE: rc = run(conv_rs_kernel<RS_NOSTORE>); break;
-        case RS_NODMA: rc = run(conv_rs_kernel<RS_NODMA>); break;
-        case RS_NOMATH: rc = run(conv_rs_kernel<RS_NOMATH>); break;
-        case RS_PRIO: rc = run(conv_rs_kernel<RS_PRIO>); break;
-        case RS_NTLOAD: rc = run(conv_rs_kernel<RS_NTLOAD>); break;
-        case RS_NTSTORE: rc = run(conv_rs_kernel<RS_NTSTORE>); break;
-        case RS_NTLOAD | RS_NTSTORE: rc = run(conv_rs_kernel<RS_NTLOAD | RS_NTSTORE>); break;
-        case RS_NODMA | RS_NOSTORE: rc = run(conv_rs_kernel<RS_NODMA | RS_NOSTORE>); break;
-        case RS_NOMATH | RS_NOSTORE: rc = run(conv_rs_kernel<RS_NOMATH | RS_NOSTORE>); break;
-        case RS_NOMATH | RS_NODMA: rc = run(conv_rs_kernel<RS_NOMATH | RS_NODMA>); break;
+        case 0: rc = run(constant<conv_rs_kernel<0>>{}); break;
+        case RS_NOSTORE: rc = run(constant<conv_rs_kernel<RS_NOSTORE>>{}); break;
+        case RS_NODMA: rc = run(constant<conv_rs_kernel<RS_NODMA>>{}); break;
+        case RS_NOMATH: rc = run(constant<conv_rs_kernel<RS_NOMATH>>{}); break;
+        case RS_PRIO: rc = run(constant<conv_rs_kernel<RS_PRIO>>{}); break;
+        case RS_NTLOAD: rc = run(constant<conv_rs_kernel<RS_NTLOAD>>{}); break;
+        case RS_NTSTORE: rc = run(constant<conv_rs_kernel<RS_NTSTORE>>{}); break;
+        case RS_NTLOAD | RS_NTSTORE: rc = run(constant<conv_rs_kernel<RS_NTLOAD | RS_NTSTORE>>{}); break;
+        case RS_NODMA | RS_NOSTORE: rc = run(constant<conv_rs_kernel<RS_NODMA | RS_NOSTORE>>{}); break;
+        case RS_NOMATH | RS_NOSTORE: rc = run(constant<conv_rs_kernel<RS_NOMATH | RS_NOSTORE>>{}); break;
+        case RS_NOMATH | RS_NODMA: rc = run(constant<conv_rs_kernel<RS_NOMATH | RS_NODMA>>{}); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
     }
     (void)hipFree(x); (void)hipFree(y); (void)hipFree(yr); (void)hipFree(dimg); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -755,19 +747,17 @@ int rife_hip_bench_rs2(int gpuid, int h, int w, int variant, int iters, float* m
         HIPCHK(hipMalloc(&xs[k], nb)); HIPCHK(hipMalloc(&ys[k], nb));
         HIPCHK(hipMemcpy(xs[k], x, nb, hipMemcpyDeviceToDevice)); HIPCHK(hipMemset(ys[k], 0, nb));
     }
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_rs2_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, RS2_LDS));
     if (stats) {
         for (int i = 0; i < 8; i++) stats[i] = -1;
         std::vector<unsigned char> ref(nb), got(nb);
         if ((h + 1) / 2 >= RS_MIN_PAIRS) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_rs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS));
             RsArgs r;
             r.in = x; r.out = tm; r.img = dimg[0]; r.H = h; r.W = w; r.pitch = G.pitch; r.plane = G.plane(); r.npairs = (h + 1) / 2; r.nunits = G.tiles_x * r.npairs; r.descend = 0;
             const int rwg = std::min(cus, r.nunits);
             HIPCHK(hipMemset(tm, 0, nb)); HIPCHK(hipMemset(yr, 0, nb));
-            hipLaunchKernelGGL((conv_rs_kernel<0>), dim3(rwg), dim3(RS_NTHR), RS_LDS, 0, r);
+            if (int lrc = launch<conv_rs_kernel<0>>("bench launch", dim3(rwg), dim3(RS_NTHR), RS_LDS, 0, r)) return lrc;
             r.in = tm; r.out = yr; r.img = dimg[1];
-            hipLaunchKernelGGL((conv_rs_kernel<0>), dim3(rwg), dim3(RS_NTHR), RS_LDS, 0, r);
+            if (int lrc = launch<conv_rs_kernel<0>>("bench launch", dim3(rwg), dim3(RS_NTHR), RS_LDS, 0, r)) return lrc;
         } else {                                                         // tiny tensors: conv_t64 twice (conv_rs needs 7 rows) - another summation order, bytes differ
             return fail(RIFE_HIP_EINVAL, "conv_rs2 bench check needs at least 7 rows");
         }
@@ -776,7 +766,7 @@ int rife_hip_bench_rs2(int gpuid, int h, int w, int variant, int iters, float* m
         for (int dir = 0; dir < 2; dir++) {
             HIPCHK(hipMemset(y, 0, nb));
             a.descend = dir;
-            hipLaunchKernelGGL((conv_rs2_kernel<0>), dim3(nwg), dim3(RS2_NTHR), RS2_LDS, 0, a);
+            if (int lrc = launch<conv_rs2_kernel<0>>("bench launch", dim3(nwg), dim3(RS2_NTHR), RS2_LDS, 0, a)) return lrc;
             HIPCHK(hipDeviceSynchronize());
             HIPCHK(hipMemcpy(got.data(), y, nb, hipMemcpyDeviceToHost));
             long long bad = 0;
@@ -791,16 +781,15 @@ int rife_hip_bench_rs2(int gpuid, int h, int w, int variant, int iters, float* m
         a.descend = 0;
     }
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    auto run = [&](auto kfn) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, RS2_LDS));
-        for (int i = 0; i < 3; i++) hipLaunchKernelGGL(kfn, dim3(nwg), dim3(RS2_NTHR), RS2_LDS, 0, a);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 3; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(RS2_NTHR), RS2_LDS, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
         for (int i = 0; i < iters; i++) {
             if (cold) { a.in = xs[i & 3]; a.out = ys[i & 3]; }
             else if (fixed) { a.in = x; a.out = y; }
             else { a.in = (i & 1) ? y : x; a.out = (i & 1) ? x : y; }
             a.descend = up ? 1 : (alternate ? (i & 1) : 0);
-            hipLaunchKernelGGL(kfn, dim3(nwg), dim3(RS2_NTHR), RS2_LDS, 0, a);
+            if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(RS2_NTHR), RS2_LDS, 0, a)) return lrc;
         }
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
@@ -813,7 +802,7 @@ int rife_hip_bench_rs2(int gpuid, int h, int w, int variant, int iters, float* m
         long long* dst = nullptr;
         HIPCHK(hipMalloc(&dst, (size_t)nwg * 32)); HIPCHK(hipMemset(dst, 0, (size_t)nwg * 32));
         a.stamps = dst;
-        rc = run(conv_rs2_kernel<RS_CLK>);
+        rc = run(constant<conv_rs2_kernel<RS_CLK>>{});
         std::vector<long long> hs((size_t)nwg * 4);
         HIPCHK(hipMemcpy(hs.data(), dst, hs.size() * 8, hipMemcpyDeviceToHost));
         (void)hipFree(dst);
@@ -832,22 +821,22 @@ int rife_hip_bench_rs2(int gpuid, int h, int w, int variant, int iters, float* m
             if (!v.empty()) fprintf(stderr, "   XCD %d: life median %.1f max %.1f us\n", x, pct(v, 0.5), pct(v, 1));
         }
     } else if (iters > 0) switch (variant) {
-        case 0: rc = run(conv_rs2_kernel<0>); break;
-        case RS_NOSTORE: rc = run(conv_rs2_kernel<RS_NOSTORE>); break;
-        case RS_NODMA: rc = run(conv_rs2_kernel<RS_NODMA>); break;
-        case RS_NOMATH: rc = run(conv_rs2_kernel<RS_NOMATH>); break;
-        case RS_NODMA | RS_NOSTORE: rc = run(conv_rs2_kernel<RS_NODMA | RS_NOSTORE>); break;
-        case RS_NOMATH | RS_NOSTORE: rc = run(conv_rs2_kernel<RS_NOMATH | RS_NOSTORE>); break;
-        case RS_NOMATH | RS_NODMA: rc = run(conv_rs2_kernel<RS_NOMATH | RS_NODMA>); break;
-        case RS_NODMA | RS_NOSTORE | RS2_NOFRAG: rc = run(conv_rs2_kernel<RS_NODMA | RS_NOSTORE | RS2_NOFRAG>); break;
-        case RS_NODMA | RS_NOSTORE | RS2_NOLO: rc = run(conv_rs2_kernel<RS_NODMA | RS_NOSTORE | RS2_NOLO>); break;
+        case 0: rc = run(constant<conv_rs2_kernel<0>>{}); break;
+        case RS_NOSTORE: rc = run(constant<conv_rs2_kernel<RS_NOSTORE>>{}); break;
+        case RS_NODMA: rc = run(constant<conv_rs2_kernel<RS_NODMA>>{}); break;
+        case RS_NOMATH: rc = run(constant<conv_rs2_kernel<RS_NOMATH>>{}); break;
+        case RS_NODMA | RS_NOSTORE: rc = run(constant<conv_rs2_kernel<RS_NODMA | RS_NOSTORE>>{}); break;
+        case RS_NOMATH | RS_NOSTORE: rc = run(constant<conv_rs2_kernel<RS_NOMATH | RS_NOSTORE>>{}); break;
+        case RS_NOMATH | RS_NODMA: rc = run(constant<conv_rs2_kernel<RS_NOMATH | RS_NODMA>>{}); break;
+        case RS_NODMA | RS_NOSTORE | RS2_NOFRAG: rc = run(constant<conv_rs2_kernel<RS_NODMA | RS_NOSTORE | RS2_NOFRAG>>{}); break;
+        case RS_NODMA | RS_NOSTORE | RS2_NOLO: rc = run(constant<conv_rs2_kernel<RS_NODMA | RS_NOSTORE | RS2_NOLO>>{}); break;
         case RS2_STAMPS: case RS2_STAMPS | RS_NODMA | RS_NOSTORE: {
             // barrier trace of one workgroup (the middle one), last launch: per barrier, cycles from the previous release to each wave's arrival, and who came last
             long long* dst = nullptr;
             const size_t ns = (size_t)8 * RS2_NSTAMP * 2;
             HIPCHK(hipMalloc(&dst, ns * 8)); HIPCHK(hipMemset(dst, 0, ns * 8));
             a.stamps = dst; a.stamp_wg = nwg / 2;
-            rc = variant == RS2_STAMPS ? run(conv_rs2_kernel<RS2_STAMPS>) : run(conv_rs2_kernel<RS2_STAMPS | RS_NODMA | RS_NOSTORE>);
+            rc = variant == RS2_STAMPS ? run(constant<conv_rs2_kernel<RS2_STAMPS>>{}) : run(constant<conv_rs2_kernel<RS2_STAMPS | RS_NODMA | RS_NOSTORE>>{});
             std::vector<long long> hs(ns);
             HIPCHK(hipMemcpy(hs.data(), dst, ns * 8, hipMemcpyDeviceToHost));
             (void)hipFree(dst);
@@ -958,9 +947,8 @@ int rife_hip_probe_stem_det(int gpuid, int variant, int wp, int hp, int reps, lo
     fa.img0 = i0; fa.img1 = i1; fa.F = F; fa.M = M; fa.wpk = wh; fa.bias = bias; fa.slope = slope; fa.timestep = 0.5f; fa.tsp = nullptr;
     fa.wp = wp; fa.hp = hp; fa.Ho = Ho; fa.Wo = Wo; fa.out_ld = cout; fa.Cout = cout; fa.tiles_x = (Wo + 31) / 32;
     const int nb = fa.tiles_x * ((Ho + 3) / 4);
-    auto run = [&](auto kfn, int lds) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        for (int r = 0; r < reps; r++) { fa.out = outs[r]; fa.dbg = dbgs[r]; hipLaunchKernelGGL(kfn, dim3(nb), dim3(512), lds, 0, fa); }
+    auto run = [&](auto kern, int lds) -> int {
+        for (int r = 0; r < reps; r++) { fa.out = outs[r]; fa.dbg = dbgs[r]; if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nb), dim3(512), lds, 0, fa)) return lrc; }
         HIPCHK(hipDeviceSynchronize());
         return 0;
     };
@@ -972,14 +960,14 @@ int rife_hip_probe_stem_det(int gpuid, int variant, int wp, int hp, int reps, lo
         HIPCHK(hipModuleGetFunction(&fn, mod, fname.c_str()));
         const Switches psw = read_switches();
         const int ldsb_ext = psw.probe_lds >= 0 ? psw.probe_lds : stemf_lds_bytes<2>();      // > 80 KB: one workgroup per CU
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb_ext));
         const char* scrub = psw.probe_scrub;
         uint32_t* sink = nullptr;
-        if (scrub) { HIPCHK(hipMalloc(&sink, 4)); HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lds_scrub), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
+        HIPCHK(lds_opt_in(reinterpret_cast<const void*>(fn), ldsb_ext));
+        if (scrub) HIPCHK(hipMalloc(&sink, 4));
         for (int r = 0; r < reps; r++) {
             if (scrub) {      // every CU's LDS (one 160 KB workgroup per CU at a time, many rounds) <- pattern, alternating if "alt"
                 const uint32_t pat = std::strcmp(scrub, "alt") == 0 ? ((r & 1) ? 0x7fc00000u : 0u) : (uint32_t)std::strtoul(scrub, nullptr, 16);
-                hipLaunchKernelGGL(k_lds_scrub, dim3(2048), dim3(512), 160 * 1024, 0, pat, 160 * 1024 / 4, sink);
+                if (int lrc = launch<k_lds_scrub>("bench launch", dim3(2048), dim3(512), 160 * 1024, 0, pat, 160 * 1024 / 4, sink)) return lrc;
             }
             fa.out = outs[r]; fa.dbg = dbgs[r];
             size_t sz = sizeof(fa);
@@ -1001,8 +989,8 @@ int rife_hip_probe_stem_det(int gpuid, int variant, int wp, int hp, int reps, lo
             float* refo = nullptr;
             HIPCHK(hipMalloc(&refo, nout * 4)); HIPCHK(hipMemset(refo, 0, nout * 4));
             fa.out = refo; fa.dbg = nullptr;
-            if (S == 4) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>())); hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), 0, fa); }
-            else { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>())); hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), 0, fa); }
+            if (S == 4) { if (int lrc = launch<stem0_fused_kernel<4, 2, 0>>("bench launch", dim3(nb), dim3(512), stemf_lds_bytes<2>(), 0, fa)) return lrc; }
+            else { if (int lrc = launch<stem0_fused_kernel<2, 2, 0>>("bench launch", dim3(nb), dim3(512), stemf_lds_bytes<2>(), 0, fa)) return lrc; }
             HIPCHK(hipDeviceSynchronize());
             std::vector<float> a0(nout), a1(nout);
             HIPCHK(hipMemcpy(a0.data(), outs[0], nout * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(a1.data(), refo, nout * 4, hipMemcpyDeviceToHost));
@@ -1012,13 +1000,13 @@ int rife_hip_probe_stem_det(int gpuid, int variant, int wp, int hp, int reps, lo
         }
     } else
     switch (variant) {
-        case 4: rc = run(stem0_fused_kernel<4, 2, 0>, stemf_lds_bytes<2>()); break;
-        case 2: rc = run(stem0_fused_kernel<2, 2, 0>, stemf_lds_bytes<2>()); break;
-        case 1 + 16 * 256: rc = run(stem0_fused_kernel<1, 1, 256>, (stemf_lds_bytes<1, 256>())); break;
-        case 1: rc = run(stem0_fused_kernel<1, 1, 0>, stemf_lds_bytes<1>()); break;
-        case 4 + 16 * 1024: rc = run(stem0_fused_kernel<4, 2, 1024>, stemf_lds_bytes<2>()); break;
-        case 4 + 16 * 4096: rc = run(stem0_fused_kernel<4, 2, 4096>, stemf_lds_bytes<2>()); break;
-        case 2 + 16 * 4096: rc = run(stem0_fused_kernel<2, 2, 4096>, stemf_lds_bytes<2>()); break;
+        case 4: rc = run(constant<stem0_fused_kernel<4, 2, 0>>{}, stemf_lds_bytes<2>()); break;
+        case 2: rc = run(constant<stem0_fused_kernel<2, 2, 0>>{}, stemf_lds_bytes<2>()); break;
+        case 1 + 16 * 256: rc = run(constant<stem0_fused_kernel<1, 1, 256>>{}, (stemf_lds_bytes<1, 256>())); break;
+        case 1: rc = run(constant<stem0_fused_kernel<1, 1, 0>>{}, stemf_lds_bytes<1>()); break;
+        case 4 + 16 * 1024: rc = run(constant<stem0_fused_kernel<4, 2, 1024>>{}, stemf_lds_bytes<2>()); break;
+        case 4 + 16 * 4096: rc = run(constant<stem0_fused_kernel<4, 2, 4096>>{}, stemf_lds_bytes<2>()); break;
+        case 2 + 16 * 4096: rc = run(constant<stem0_fused_kernel<2, 2, 4096>>{}, stemf_lds_bytes<2>()); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
     }
     if (!rc) {
@@ -1090,11 +1078,10 @@ int rife_hip_bench_tail_rs(int gpuid, int wp, int hp, int variant, int iters, fl
     HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, gpuid));
     const int nwg = std::min(2 * cus, a.nunits);
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    auto run = [&](auto kfn) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
-        for (int i = 0; i < 2; i++) hipLaunchKernelGGL(kfn, dim3(nwg), dim3(TRS_NTHR), TRS_LDS, 0, a);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 2; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(TRS_NTHR), TRS_LDS, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
-        for (int i = 0; i < iters; i++) hipLaunchKernelGGL(kfn, dim3(nwg), dim3(TRS_NTHR), TRS_LDS, 0, a);
+        for (int i = 0; i < iters; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(TRS_NTHR), TRS_LDS, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
         float t = 0; HIPCHK(hipEventElapsedTime(&t, e0, e1));
@@ -1102,16 +1089,16 @@ int rife_hip_bench_tail_rs(int gpuid, int wp, int hp, int variant, int iters, fl
         return 0;
     };
     switch (variant) {
-        case 0: rc = run(tail_rs_kernel<0>); break;
-        case TRS_NOTAPS: rc = run(tail_rs_kernel<TRS_NOTAPS>); break;
-        case TRS_NOFM: rc = run(tail_rs_kernel<TRS_NOFM>); break;
-        case TRS_NOROW: rc = run(tail_rs_kernel<TRS_NOROW>); break;
-        case TRS_NOTAPS | TRS_NOFM | TRS_NOROW: rc = run(tail_rs_kernel<TRS_NOTAPS | TRS_NOFM | TRS_NOROW>); break;
-        case TRS_NOMATH: rc = run(tail_rs_kernel<TRS_NOMATH>); break;
-        case TRS_NOSTORE: rc = run(tail_rs_kernel<TRS_NOSTORE>); break;
-        case TRS_NOPIX: rc = run(tail_rs_kernel<TRS_NOPIX>); break;
-        case TRS_NOTAPS | TRS_NOFM | TRS_NOROW | TRS_NOPIX: rc = run(tail_rs_kernel<TRS_NOTAPS | TRS_NOFM | TRS_NOROW | TRS_NOPIX>); break;
-        case TRS_NOTAPS | TRS_NOFM | TRS_NOROW | TRS_NOMATH | TRS_NOSTORE: rc = run(tail_rs_kernel<TRS_NOTAPS | TRS_NOFM | TRS_NOROW | TRS_NOMATH | TRS_NOSTORE>); break;
+        case 0: rc = run(constant<tail_rs_kernel<0>>{}); break;
+        case TRS_NOTAPS: rc = run(constant<tail_rs_kernel<TRS_NOTAPS>>{}); break;
+        case TRS_NOFM: rc = run(constant<tail_rs_kernel<TRS_NOFM>>{}); break;
+        case TRS_NOROW: rc = run(constant<tail_rs_kernel<TRS_NOROW>>{}); break;
+        case TRS_NOTAPS | TRS_NOFM | TRS_NOROW: rc = run(constant<tail_rs_kernel<TRS_NOTAPS | TRS_NOFM | TRS_NOROW>>{}); break;
+        case TRS_NOMATH: rc = run(constant<tail_rs_kernel<TRS_NOMATH>>{}); break;
+        case TRS_NOSTORE: rc = run(constant<tail_rs_kernel<TRS_NOSTORE>>{}); break;
+        case TRS_NOPIX: rc = run(constant<tail_rs_kernel<TRS_NOPIX>>{}); break;
+        case TRS_NOTAPS | TRS_NOFM | TRS_NOROW | TRS_NOPIX: rc = run(constant<tail_rs_kernel<TRS_NOTAPS | TRS_NOFM | TRS_NOROW | TRS_NOPIX>>{}); break;
+        case TRS_NOTAPS | TRS_NOFM | TRS_NOROW | TRS_NOMATH | TRS_NOSTORE: rc = run(constant<tail_rs_kernel<TRS_NOTAPS | TRS_NOFM | TRS_NOROW | TRS_NOMATH | TRS_NOSTORE>>{}); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
     }
     (void)hipFree(i0); (void)hipFree(i1); (void)hipFree(F); (void)hipFree(M); (void)hipFree(bias); (void)hipFree(w); (void)hipFree(x); (void)hipFree(out);
@@ -1158,11 +1145,10 @@ int rife_hip_bench_stem_rs(int gpuid, int wp, int hp, int variant, int iters, fl
     HIPCHK(hipMemset(dst, 0, (size_t)nwg * 64 * 8));
     a.stamps = dst;
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    auto run = [&](auto kfn) -> int {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, SRS_LDS));
-        for (int i = 0; i < 2; i++) hipLaunchKernelGGL(kfn, dim3(nwg), dim3(SRS_NTHR), SRS_LDS, 0, a);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 2; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(SRS_NTHR), SRS_LDS, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
-        for (int i = 0; i < iters; i++) hipLaunchKernelGGL(kfn, dim3(nwg), dim3(SRS_NTHR), SRS_LDS, 0, a);
+        for (int i = 0; i < iters; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nwg), dim3(SRS_NTHR), SRS_LDS, 0, a)) return lrc;
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
         float t = 0; HIPCHK(hipEventElapsedTime(&t, e0, e1));
@@ -1170,18 +1156,18 @@ int rife_hip_bench_stem_rs(int gpuid, int wp, int hp, int variant, int iters, fl
         return 0;
     };
     switch (variant & 0xff) {
-        case 0: rc = run(stem_rs_kernel<0>); break;
-        case SRS_NOTAPS: rc = run(stem_rs_kernel<SRS_NOTAPS>); break;
-        case SRS_NOFM: rc = run(stem_rs_kernel<SRS_NOFM>); break;
-        case SRS_NOTAPS | SRS_NOFM: rc = run(stem_rs_kernel<SRS_NOTAPS | SRS_NOFM>); break;
-        case SRS_NOMATH: rc = run(stem_rs_kernel<SRS_NOMATH>); break;
-        case SRS_NOSTORE: rc = run(stem_rs_kernel<SRS_NOSTORE>); break;
-        case SRS_NOFINISH: rc = run(stem_rs_kernel<SRS_NOFINISH>); break;
-        case SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH: rc = run(stem_rs_kernel<SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH>); break;
-        case SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH | SRS_NOSTORE: rc = run(stem_rs_kernel<SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH | SRS_NOSTORE>); break;
-        case SRS_NOTAPS | SRS_NOFM | SRS_NOMATH | SRS_NOSTORE: rc = run(stem_rs_kernel<SRS_NOTAPS | SRS_NOFM | SRS_NOMATH | SRS_NOSTORE>); break;
-        case SRS_CLK: rc = run(stem_rs_kernel<SRS_CLK>); break;
-        case SRS_CLK | SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH | SRS_NOSTORE: rc = run(stem_rs_kernel<SRS_CLK | SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH | SRS_NOSTORE>); break;
+        case 0: rc = run(constant<stem_rs_kernel<0>>{}); break;
+        case SRS_NOTAPS: rc = run(constant<stem_rs_kernel<SRS_NOTAPS>>{}); break;
+        case SRS_NOFM: rc = run(constant<stem_rs_kernel<SRS_NOFM>>{}); break;
+        case SRS_NOTAPS | SRS_NOFM: rc = run(constant<stem_rs_kernel<SRS_NOTAPS | SRS_NOFM>>{}); break;
+        case SRS_NOMATH: rc = run(constant<stem_rs_kernel<SRS_NOMATH>>{}); break;
+        case SRS_NOSTORE: rc = run(constant<stem_rs_kernel<SRS_NOSTORE>>{}); break;
+        case SRS_NOFINISH: rc = run(constant<stem_rs_kernel<SRS_NOFINISH>>{}); break;
+        case SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH: rc = run(constant<stem_rs_kernel<SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH>>{}); break;
+        case SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH | SRS_NOSTORE: rc = run(constant<stem_rs_kernel<SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH | SRS_NOSTORE>>{}); break;
+        case SRS_NOTAPS | SRS_NOFM | SRS_NOMATH | SRS_NOSTORE: rc = run(constant<stem_rs_kernel<SRS_NOTAPS | SRS_NOFM | SRS_NOMATH | SRS_NOSTORE>>{}); break;
+        case SRS_CLK: rc = run(constant<stem_rs_kernel<SRS_CLK>>{}); break;
+        case SRS_CLK | SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH | SRS_NOSTORE: rc = run(constant<stem_rs_kernel<SRS_CLK | SRS_NOTAPS | SRS_NOFM | SRS_NOFINISH | SRS_NOSTORE>>{}); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
     }
     if (rc == 0 && stamps_out && (variant & SRS_CLK)) {     // mean over the workgroups of the LAST launch, per wave and phase, in cycles per step
@@ -1216,10 +1202,10 @@ int rife_hip_bench_stemf(int gpuid, int wp, int hp, int variant, int iters, floa
     fa.wp = wp; fa.hp = hp; fa.Ho = hp / 2; fa.Wo = wp / 2; fa.out_ld = 32; fa.Cout = 32; fa.tiles_x = (fa.Wo + 31) / 32;
     const int nb = fa.tiles_x * ((fa.Ho + 3) / 4);
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    auto run = [&](auto kfn) -> int {
-        for (int i = 0; i < 2; i++) hipLaunchKernelGGL(kfn, dim3(nb), dim3(512), stemf_lds_bytes<1>(), 0, fa);
+    auto run = [&](auto kern) -> int {
+        for (int i = 0; i < 2; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nb), dim3(512), stemf_lds_bytes<1>(), 0, fa)) return lrc;
         HIPCHK(hipEventRecord(e0, 0));
-        for (int i = 0; i < iters; i++) hipLaunchKernelGGL(kfn, dim3(nb), dim3(512), stemf_lds_bytes<1>(), 0, fa);
+        for (int i = 0; i < iters; i++) if (int lrc = launch<decltype(kern)::value>("bench launch", dim3(nb), dim3(512), stemf_lds_bytes<1>(), 0, fa)) return lrc;
         HIPCHK(hipEventRecord(e1, 0));
         HIPCHK(hipEventSynchronize(e1));
         float t = 0; HIPCHK(hipEventElapsedTime(&t, e0, e1));
@@ -1227,10 +1213,10 @@ int rife_hip_bench_stemf(int gpuid, int wp, int hp, int variant, int iters, floa
         return 0;
     };
     switch (variant) {
-        case 0: rc = run(stem0_fused_kernel<1, 1, 0>); break;
-        case 1: rc = run(stem0_fused_kernel<1, 1, 1>); break;
-        case 16: rc = run(stem0_fused_kernel<1, 1, 16>); break;
-        case 32: rc = run(stem0_fused_kernel<1, 1, 32>); break;
+        case 0: rc = run(constant<stem0_fused_kernel<1, 1, 0>>{}); break;
+        case 1: rc = run(constant<stem0_fused_kernel<1, 1, 1>>{}); break;
+        case 16: rc = run(constant<stem0_fused_kernel<1, 1, 16>>{}); break;
+        case 32: rc = run(constant<stem0_fused_kernel<1, 1, 32>>{}); break;
         default: rc = fail(RIFE_HIP_EINVAL, "unknown variant");
     }
     (void)hipFree(i0); (void)hipFree(i1); (void)hipFree(F); (void)hipFree(M); (void)hipFree(out); (void)hipFree(bias); (void)hipFree(wh);

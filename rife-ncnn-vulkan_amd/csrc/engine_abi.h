@@ -5,6 +5,16 @@
 // ================================================================================================
 // C-ABI
 // ================================================================================================
+namespace rife {
+// the exception guard of the extern "C" entry points: nothing may throw across the C boundary (malformed model files, std::bad_alloc)
+template <typename F>
+static int guarded(const char* entry, F&& f) {
+    try { return f(); }
+    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string(entry) + ": " + e.what()); }
+    catch (...) { return fail(RIFE_HIP_EIO, std::string(entry) + ": unknown exception"); }
+}
+}  // namespace rife
+
 extern "C" {
 
 const char* rife_hip_last_error(void) { return g_err.c_str(); }
@@ -130,10 +140,8 @@ static int rife_hip_load_impl(rife_hip_t* E, const char* modeldir) {
     E->loaded = true;
     return 0;
 }
-int rife_hip_load(rife_hip_t* E, const char* modeldir) {      // nothing may throw across the C boundary (malformed model files, std::bad_alloc)
-    try { return rife_hip_load_impl(E, modeldir); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_load: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_load: unknown exception"); }
+int rife_hip_load(rife_hip_t* E, const char* modeldir) {
+    return guarded("rife_hip_load", [&] { return rife_hip_load_impl(E, modeldir); });
 }
 
 static int process_common(const rife_hip* E, int w, int h, float timestep) {
@@ -232,6 +240,16 @@ static int pool_layout(int callers, int w, int h) {
     if (forced != 3 || callers < 4) return 1;
     return (long long)w * h >= 4000000ll ? 2 : 4;
 }
+// the stream of part `part` of `parts` of the chip: CU-masked (the CUs with cu % parts == part) or, for one part, an ordinary non-blocking stream; *cus = the CUs it owns
+static hipError_t create_part_stream(int part, int parts, hipStream_t* st, int* cus) {
+    const int ncu = device_cus(true);
+    *cus = ncu;
+    if (parts == 1) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
+    *cus = 0;
+    for (int cu = 0; cu < ncu; cu++) if (cu % parts == part) { mask[cu / 32] |= 1u << (cu % 32); (*cus)++; }
+    return hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data());
+}
 // force_parts = 1: a whole-chip stream whatever the callers in flight (the lockstep groups of process_batch: a group's batched coarse-block launches ride on ONE
 // of its two streams and must see the whole chip)
 static int lease_ctx(const rife_hip* E, std::unique_ptr<Ctx>& c, int w, int h, int force_parts = 0, int pixfmt = RIFE_HIP_PIX_RGB8) {
@@ -259,14 +277,9 @@ static int lease_ctx(const rife_hip* E, std::unique_ptr<Ctx>& c, int w, int h, i
     if (!c) {
         c.reset(new Ctx);
         c->pool_parts = parts; c->pool_part = part;
-        if (parts > 1) {
-            const int ncu = device_cus(true);
-            std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-            int mine = 0;
-            for (int cu = 0; cu < ncu; cu++) if (cu % parts == part) { mask[cu / 32] |= 1u << (cu % 32); mine++; }
-            if (hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)mask.size(), mask.data()) != hipSuccess) c->stream = nullptr;
-            c->cu_budget = mine;
-        } else if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) c->stream = nullptr;
+        int mine = 0;
+        if (create_part_stream(part, parts, &c->stream, &mine) != hipSuccess) c->stream = nullptr;
+        if (parts > 1) c->cu_budget = mine;
         if (!c->stream) {                                                // no stream: the lease never happened (a workspace without one must not reach the pool through the caller's release)
             std::lock_guard<std::mutex> g(E->mu);
             E->leased--; E->part_live[parts][part]--;
@@ -298,6 +311,18 @@ static void release_ctx(const rife_hip* E, std::unique_ptr<Ctx>& c) {
     }
 }
 
+// the pass of the engine's model family on workspace c (the caller has made it fit: lease_ctx / ensure_ctx*)
+static int run_pass(const rife_hip* E, Ctx& c, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out) {
+    if (E->v1) return run_v1(*E, c, in0, in1, out);
+    if (!E->v4) return run_v2(*E, c, in0, in1, out);
+    if (!E->tta && !E->tta_temporal) return run_v4_replay(*E, c, in0, in1, timestep, out);
+    // the TTA workspaces are shared by all callers: serialise, and drain before the next caller may reuse them
+    std::lock_guard<std::mutex> g(E->tta_mu);
+    int rc = run_v4_tta(*E, c.stream, in0, in1, w, h, timestep, out);
+    if (!rc && hipStreamSynchronize(c.stream) != hipSuccess) rc = fail(RIFE_HIP_EHIP, "TTA stream sync failed");
+    return rc;
+}
+
 // H2D of both frames, the whole pass and the D2H of the result, all enqueued on the workspace's stream (no host wait)
 static int enqueue_host_pair(const rife_hip* E, Ctx& c, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out) {
     const size_t nbytes = frame_bytes(w, h, c.pixfmt);      // c.pixfmt: set by lease_ctx (deep colour: rife-v4.6 plain pass only, pixfmt_supported)
@@ -314,16 +339,7 @@ static int enqueue_host_pair(const rife_hip* E, Ctx& c, const uint8_t* in0, cons
         if (e == hipSuccess && token) e = hipStreamSynchronize(c.stream);      // page-locked frames: the copies above only enqueue
     }
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
-    int rc;
-    if (E->v1) rc = run_v1(*E, c, c.d_in0, c.d_in1, c.d_out);
-    else if (!E->v4) rc = run_v2(*E, c, c.d_in0, c.d_in1, c.d_out);
-    else if (E->tta || E->tta_temporal) {
-        // the TTA workspaces are shared by all callers: serialise, and drain before the next caller may reuse them
-        std::lock_guard<std::mutex> g(E->tta_mu);
-        rc = run_v4_tta(*E, c.stream, c.d_in0, c.d_in1, w, h, timestep, c.d_out);
-        if (!rc && hipStreamSynchronize(c.stream) != hipSuccess) rc = fail(RIFE_HIP_EHIP, "TTA stream sync failed");
-    } else rc = run_v4_replay(*E, c, c.d_in0, c.d_in1, timestep, c.d_out);
-    if (rc) return rc;
+    if (int rc = run_pass(E, c, c.d_in0, c.d_in1, w, h, timestep, c.d_out)) return rc;
     e = hipMemcpyAsync(out, c.d_out, nbytes, hipMemcpyDeviceToHost, c.stream);
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
     return 0;
@@ -347,10 +363,8 @@ static int rife_hip_process_impl(const rife_hip_t* E, const uint8_t* in0, const 
     if (c) release_ctx(E, c);
     return rc;
 }
-int rife_hip_process(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out) {      // nothing may throw across the C boundary (malformed model files, std::bad_alloc)
-    try { return rife_hip_process_impl(E, in0, in1, w, h, timestep, out); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_process: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_process: unknown exception"); }
+int rife_hip_process(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out) {
+    return guarded("rife_hip_process", [&] { return rife_hip_process_impl(E, in0, in1, w, h, timestep, out); });
 }
 size_t rife_hip_frame_bytes(int w, int h, int pixfmt) {
     return (w > 0 && h > 0 && pixfmt >= 0) ? frame_bytes(w, h, pix_base(pixfmt)) : 0;      // the colour bits do not change the size
@@ -358,9 +372,7 @@ size_t rife_hip_frame_bytes(int w, int h, int pixfmt) {
 int rife_hip_process_px(const rife_hip_t* E, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt) {
     int rc;
     if ((rc = px_precheck(pixfmt, in0 && in1 && out, w, h))) return rc;
-    try { return rife_hip_process_impl(E, static_cast<const uint8_t*>(in0), static_cast<const uint8_t*>(in1), w, h, timestep, static_cast<uint8_t*>(out), pixfmt); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_process_px: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_process_px: unknown exception"); }
+    return guarded("rife_hip_process_px", [&] { return rife_hip_process_impl(E, static_cast<const uint8_t*>(in0), static_cast<const uint8_t*>(in1), w, h, timestep, static_cast<uint8_t*>(out), pixfmt); });
 }
 
 // n independent frame pairs from host memory in one call.  Copies from / to pageable host memory block the thread that issues
@@ -513,6 +525,28 @@ int rife_hip_process_batch(const rife_hip_t* E, int n, const uint8_t* const* in0
 
 // ---- stream mode: frames resident in device memory across calls (include/rife_hip.h) ----
 
+// a copy stream borrowed from E->upload_streams (a new one when the pool is empty), given back on every exit path; never the legacy stream
+struct CopyStreamLease {
+    const rife_hip* E;
+    hipStream_t st = nullptr;
+    hipError_t err = hipSuccess;
+    explicit CopyStreamLease(const rife_hip* E_) : E(E_) {
+        {
+            std::lock_guard<std::mutex> g(E->mu);
+            if (!E->upload_streams.empty()) { st = E->upload_streams.back(); E->upload_streams.pop_back(); }
+        }
+        if (!st) err = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    }
+    CopyStreamLease(const CopyStreamLease&) = delete;
+    ~CopyStreamLease() { if (st) { std::lock_guard<std::mutex> g(E->mu); E->upload_streams.push_back(st); } }
+    hipError_t copy(void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) const {      // drained: the bytes have landed when it returns
+        hipError_t e = err;
+        if (e == hipSuccess) e = hipMemcpyAsync(dst, src, nbytes, kind, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        return e;
+    }
+};
+
 static int rife_hip_frame_upload_impl(const rife_hip_t* E, const uint8_t* rgb, int w, int h, rife_hip_frame_t** frame, int pixfmt = RIFE_HIP_PIX_RGB8) {
     if (frame) *frame = nullptr;
     if (!E || !rgb || !frame) return fail(RIFE_HIP_EINVAL, "null argument");
@@ -526,31 +560,19 @@ static int rife_hip_frame_upload_impl(const rife_hip_t* E, const uint8_t* rgb, i
     f->nbytes = nbytes; f->pool = E->frame_pool;
     if (!(f->d = f->pool->take(nbytes))) return fail(RIFE_HIP_EHIP, "hipMalloc of a resident frame failed");
     // a copy on its own stream, drained here: the frame is complete before any stream of any caller can see the handle
-    hipStream_t st = nullptr;
-    {
-        std::lock_guard<std::mutex> g(E->mu);
-        if (!E->upload_streams.empty()) { st = E->upload_streams.back(); E->upload_streams.pop_back(); }
-    }
-    hipError_t e = st ? hipSuccess : hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpyAsync(f->d, rgb, nbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (st) { std::lock_guard<std::mutex> g(E->mu); E->upload_streams.push_back(st); }
+    const hipError_t e = CopyStreamLease(E).copy(f->d, rgb, nbytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { f->pool->give(f->d, nbytes); return fail(RIFE_HIP_EHIP, std::string("frame upload: ") + hipGetErrorString(e)); }
     *frame = f.release();
     return 0;
 }
-int rife_hip_frame_upload(const rife_hip_t* E, const uint8_t* rgb, int w, int h, rife_hip_frame_t** frame) {      // nothing may throw across the C boundary (malformed model files, std::bad_alloc)
-    try { return rife_hip_frame_upload_impl(E, rgb, w, h, frame); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_frame_upload: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_frame_upload: unknown exception"); }
+int rife_hip_frame_upload(const rife_hip_t* E, const uint8_t* rgb, int w, int h, rife_hip_frame_t** frame) {
+    return guarded("rife_hip_frame_upload", [&] { return rife_hip_frame_upload_impl(E, rgb, w, h, frame); });
 }
 int rife_hip_frame_upload_px(const rife_hip_t* E, const void* pixels, int w, int h, int pixfmt, rife_hip_frame_t** frame) {
     if (frame) *frame = nullptr;
     int rc;
     if ((rc = px_precheck(pixfmt, pixels && frame, w, h))) return rc;
-    try { return rife_hip_frame_upload_impl(E, static_cast<const uint8_t*>(pixels), w, h, frame, pixfmt); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_frame_upload_px: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_frame_upload_px: unknown exception"); }
+    return guarded("rife_hip_frame_upload_px", [&] { return rife_hip_frame_upload_impl(E, static_cast<const uint8_t*>(pixels), w, h, frame, pixfmt); });
 }
 
 void rife_hip_frame_release(rife_hip_frame_t* f) {
@@ -571,15 +593,7 @@ static int rife_hip_process_frames_impl(const rife_hip_t* E, const rife_hip_fram
     if ((rc = check_device(E->gpuid))) return rc;
     const size_t nbytes = frame_bytes(w, h, pixfmt);
     if (timestep == 0.f || timestep == 1.f) {                 // rife.cpp:2470-2480 (a copy stream of the pool, never the legacy stream)
-        hipStream_t st = nullptr;
-        {
-            std::lock_guard<std::mutex> g(E->mu);
-            if (!E->upload_streams.empty()) { st = E->upload_streams.back(); E->upload_streams.pop_back(); }
-        }
-        hipError_t e = st ? hipSuccess : hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMemcpyAsync(out, timestep == 0.f ? f0->d : f1->d, nbytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (st) { std::lock_guard<std::mutex> g(E->mu); E->upload_streams.push_back(st); }
+        const hipError_t e = CopyStreamLease(E).copy(out, timestep == 0.f ? f0->d : f1->d, nbytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("frame download: ") + hipGetErrorString(e));
         if (pix_deep(pixfmt)) canon10_host(out, out, w, h, pixfmt);
         return 0;
@@ -588,23 +602,15 @@ static int rife_hip_process_frames_impl(const rife_hip_t* E, const rife_hip_fram
     rc = lease_ctx(E, c, w, h, 0, pixfmt);
     if (!rc) {
         Ctx& C = *c;
-        if (E->v1) rc = run_v1(*E, C, f0->d, f1->d, C.d_out);
-        else if (!E->v4) rc = run_v2(*E, C, f0->d, f1->d, C.d_out);
-        else if (E->tta || E->tta_temporal) {
-            std::lock_guard<std::mutex> g(E->tta_mu);
-            rc = run_v4_tta(*E, C.stream, f0->d, f1->d, w, h, timestep, C.d_out);
-            if (!rc && hipStreamSynchronize(C.stream) != hipSuccess) rc = fail(RIFE_HIP_EHIP, "TTA stream sync failed");
-        } else rc = run_v4_replay(*E, C, f0->d, f1->d, timestep, C.d_out);
+        rc = run_pass(E, C, f0->d, f1->d, w, h, timestep, C.d_out);
         if (!rc && hipMemcpyAsync(out, C.d_out, nbytes, hipMemcpyDeviceToHost, C.stream) != hipSuccess) rc = fail(RIFE_HIP_EHIP, "D2H failed");
     }
     if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
     if (c) release_ctx(E, c);
     return rc;
 }
-int rife_hip_process_frames(const rife_hip_t* E, const rife_hip_frame_t* f0, const rife_hip_frame_t* f1, float timestep, uint8_t* out) {      // nothing may throw across the C boundary (malformed model files, std::bad_alloc)
-    try { return rife_hip_process_frames_impl(E, f0, f1, timestep, out); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_process_frames: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_process_frames: unknown exception"); }
+int rife_hip_process_frames(const rife_hip_t* E, const rife_hip_frame_t* f0, const rife_hip_frame_t* f1, float timestep, uint8_t* out) {
+    return guarded("rife_hip_process_frames", [&] { return rife_hip_process_frames_impl(E, f0, f1, timestep, out); });
 }
 
 static int rife_hip_process_device_impl(const rife_hip_t* E, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, void* hip_stream,
@@ -636,36 +642,21 @@ static int rife_hip_process_device_impl(const rife_hip_t* E, const void* d_in0, 
     if (timestep == 0.f || timestep == 1.f) {
         if ((rc = copy_frame_device(c->stream, timestep == 0.f ? d_in0 : d_in1, d_out, w, h, pixfmt))) return rc;
     } else {
-        if (E->v1) {
-            if ((rc = ensure_ctx_v1(*c, w, h, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1))) return rc;
-            if ((rc = run_v1(*E, *c, (const uint8_t*)d_in0, (const uint8_t*)d_in1, (uint8_t*)d_out))) return rc;
-        } else if (!E->v4) {
-            if ((rc = ensure_ctx_v2(*c, w, h, E->uhd, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1, E->v3, ctx_batch_serves(*E)))) return rc;
-            if ((rc = run_v2(*E, *c, (const uint8_t*)d_in0, (const uint8_t*)d_in1, (uint8_t*)d_out))) return rc;
-        } else if (E->tta || E->tta_temporal) {
-            // the TTA workspaces are shared: serialise, and drain before another stream may reuse them
-            std::lock_guard<std::mutex> g(E->tta_mu);
-            if ((rc = run_v4_tta(*E, c->stream, (const uint8_t*)d_in0, (const uint8_t*)d_in1, w, h, timestep, (uint8_t*)d_out))) return rc;
-            HIPCHK(hipStreamSynchronize(c->stream));
-        } else {
-            if ((rc = ensure_ctx(*c, w, h, pixfmt))) return rc;
-            if ((rc = run_v4_replay(*E, *c, (const uint8_t*)d_in0, (const uint8_t*)d_in1, timestep, (uint8_t*)d_out))) return rc;
-        }
+        if (E->v1) rc = ensure_ctx_v1(*c, w, h, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1);
+        else if (!E->v4) rc = ensure_ctx_v2(*c, w, h, E->uhd, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1, E->v3, ctx_batch_serves(*E));
+        else if (!E->tta && !E->tta_temporal) rc = ensure_ctx(*c, w, h, pixfmt);      // the TTA pass has workspaces of its own
+        if (rc || (rc = run_pass(E, *c, (const uint8_t*)d_in0, (const uint8_t*)d_in1, w, h, timestep, (uint8_t*)d_out))) return rc;
     }
     if (!hip_stream) HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
-int rife_hip_process_device(const rife_hip_t* E, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, void* hip_stream) {      // nothing may throw across the C boundary (malformed model files, std::bad_alloc)
-    try { return rife_hip_process_device_impl(E, d_in0, d_in1, w, h, timestep, d_out, hip_stream); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_process_device: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_process_device: unknown exception"); }
+int rife_hip_process_device(const rife_hip_t* E, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, void* hip_stream) {
+    return guarded("rife_hip_process_device", [&] { return rife_hip_process_device_impl(E, d_in0, d_in1, w, h, timestep, d_out, hip_stream); });
 }
 int rife_hip_process_device_px(const rife_hip_t* E, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt, void* hip_stream) {
     int rc;
     if ((rc = px_precheck(pixfmt, d_in0 && d_in1 && d_out, w, h))) return rc;
-    try { return rife_hip_process_device_impl(E, d_in0, d_in1, w, h, timestep, d_out, hip_stream, pixfmt); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_process_device_px: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_process_device_px: unknown exception"); }
+    return guarded("rife_hip_process_device_px", [&] { return rife_hip_process_device_impl(E, d_in0, d_in1, w, h, timestep, d_out, hip_stream, pixfmt); });
 }
 
 // n resident pairs in one call (include/rife_hip.h): lockstep groups of two pairs (run_v4_group: the coarse-block trunks of a group are one
@@ -762,17 +753,13 @@ static int rife_hip_process_device_batch_impl(const rife_hip_t* E, int n, const 
 }
 int rife_hip_process_device_batch(const rife_hip_t* E, int n, const void* const* d_in0, const void* const* d_in1, const float* timestep,
                                   void* const* d_out, int w, int h, void* hip_stream) {
-    try { return rife_hip_process_device_batch_impl(E, n, d_in0, d_in1, timestep, d_out, w, h, hip_stream); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_process_device_batch: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_process_device_batch: unknown exception"); }
+    return guarded("rife_hip_process_device_batch", [&] { return rife_hip_process_device_batch_impl(E, n, d_in0, d_in1, timestep, d_out, w, h, hip_stream); });
 }
 int rife_hip_process_device_batch_px(const rife_hip_t* E, int n, const void* const* d_in0, const void* const* d_in1, const float* timestep,
                                      void* const* d_out, int w, int h, int pixfmt, void* hip_stream) {
     int rc;
     if ((rc = px_precheck(pixfmt, true, w, h))) return rc;
-    try { return rife_hip_process_device_batch_impl(E, n, d_in0, d_in1, timestep, d_out, w, h, hip_stream, pixfmt); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_process_device_batch_px: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_process_device_batch_px: unknown exception"); }
+    return guarded("rife_hip_process_device_batch_px", [&] { return rife_hip_process_device_batch_impl(E, n, d_in0, d_in1, timestep, d_out, w, h, hip_stream, pixfmt); });
 }
 
 // ---- streams that own a part of the chip (include/rife_hip.h) ----
@@ -785,15 +772,9 @@ int rife_hip_stream_create(const rife_hip_t* E, int part, int nparts, void** hip
     if (nparts < 1 || nparts > ncu || part < 0 || part >= nparts) return fail(RIFE_HIP_EINVAL, "bad partition");
     hipStream_t st = nullptr;
     int mine = 0;
-    if (nparts == 1) {
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        mine = ncu;
-    } else {
-        std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-        for (int cu = 0; cu < ncu; cu++)
-            if (cu % nparts == part) { mask[cu / 32] |= 1u << (cu % 32); mine++; }
-        HIPCHK(hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()));
-    }
+    const hipError_t e = create_part_stream(part, nparts, &st, &mine);
+    if (e != hipSuccess)
+        return fail(RIFE_HIP_EHIP, std::string(nparts == 1 ? "hipStreamCreateWithFlags(&st, hipStreamNonBlocking): " : "hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()): ") + hipGetErrorString(e));
     std::lock_guard<std::mutex> g(E->mu);
     E->part_streams[(void*)st] = mine;
     *hip_stream = (void*)st;
@@ -1004,8 +985,6 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
         std::vector<float> hz(64, 0.f), ho(64, 1.f);
         HIPCHK(hipMemcpyAsync(dbias, hz.data(), 256, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(dslope, ho.data(), 256, hipMemcpyHostToDevice, st));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_rs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, SRS_LDS));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_rs_kernel<0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, SRS_LDS));
         std::vector<unsigned char> host(nb);
         int inv[32];                                                     // row of a 32-row block that holds channel ch (pack_weights_h2_perm)
         for (int i = 0; i < 32; i++) inv[s16_row_channel(i)] = i;
@@ -1025,9 +1004,9 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
                     a.out = dout; a.timestep = timestep; a.tsp = nullptr; a.wp = c.wp; a.hp = c.hp; a.Hq = Hq; a.Wq = Wq; a.pitch = G.pitch; a.plane = G.plane();
                     a.nunits = ((Wq + SRS_SW - 1) / SRS_SW) * Hq;
                     const int nwg = std::min(2 * device_cus(), a.nunits);
-                    if (pix_deep(pixfmt)) hipLaunchKernelGGL((stem_rs_kernel<0, 10>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, st, a);
-                    else hipLaunchKernelGGL((stem_rs_kernel<0>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, st, a);
-                    HIPCHK(hipGetLastError());
+                    if (pix_deep(pixfmt)) rc = launch<stem_rs_kernel<0, 10>>("hipGetLastError()", dim3(nwg), dim3(SRS_NTHR), SRS_LDS, st, a);
+                    else rc = launch<stem_rs_kernel<0>>("hipGetLastError()", dim3(nwg), dim3(SRS_NTHR), SRS_LDS, st, a);
+                    if (rc) return rc;
                     HIPCHK(hipMemcpyAsync(host.data(), dout, nb, hipMemcpyDeviceToHost, st));
                     HIPCHK(hipStreamSynchronize(st));
                     for (int j = 0; j < 2; j++)
@@ -1087,30 +1066,25 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
         fa.img0 = c.img0; fa.img1 = c.img1; fa.F = c.F; fa.M = c.M; fa.wpk = dw; fa.bias = dbias; fa.slope = dslope;
         fa.out = c.S1; fa.timestep = timestep; fa.tsp = nullptr; fa.wp = c.wp; fa.hp = c.hp; fa.Ho = Ho; fa.Wo = Wo; fa.out_ld = cout; fa.Cout = cout;
         fa.tiles_x = (Wo + 31) / 32;
-        const int nb = fa.tiles_x * ((Ho + 3) / 4);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0, 0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, 0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, 1, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
+        const dim3 grid(fa.tiles_x * ((Ho + 3) / 4));
+        const char* const lname = "hipGetLastError()";      // the error text this site has always had
         if (pending && pix_deep(pixfmt)) {
             fa.pend.flow = pending; fa.pend.Fw = c.F2; fa.pend.Mw = c.M2;
-            if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 1, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 1, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
+            if (s == 2) rc = launch<stem0_fused_kernel<2, 2, 0, 1, 10>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else rc = launch<stem0_fused_kernel<1, 1, 256, 1, 10>>(lname, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);
         } else if (pix_deep(pixfmt)) {
-            if (s == 4) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 0, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
+            if (s == 4) rc = launch<stem0_fused_kernel<4, 2, 0, 0, 10>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (s == 2) rc = launch<stem0_fused_kernel<2, 2, 0, 0, 10>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else rc = launch<stem0_fused_kernel<1, 1, 256, 0, 10>>(lname, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);
         } else if (pending) {                                                   // every launch reads the old F, M and writes the same new ones
             fa.pend.flow = pending; fa.pend.Fw = c.F2; fa.pend.Mw = c.M2;
-            if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, true>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, true>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
-            if (what == 3) { HIPCHK(hipGetLastError()); return copy_fm(c.F2, c.M2); }
-        } else if (s == 4) hipLaunchKernelGGL((stem0_fused_kernel<4, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-        else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-        else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
-        HIPCHK(hipGetLastError());
+            if (s == 2) rc = launch<stem0_fused_kernel<2, 2, 0, true>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else rc = launch<stem0_fused_kernel<1, 1, 256, true>>(lname, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);
+            if (what == 3) return rc ? rc : copy_fm(c.F2, c.M2);
+        } else if (s == 4) rc = launch<stem0_fused_kernel<4, 2>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+        else if (s == 2) rc = launch<stem0_fused_kernel<2, 2>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+        else rc = launch<stem0_fused_kernel<1, 1, 256>>(lname, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);
+        if (rc) return rc;
         HIPCHK(hipMemcpyAsync(host.data(), c.S1, host.size() * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         for (int q = 0; q < per && l * per + q < 4; q++) {
@@ -1153,7 +1127,7 @@ static int rife_hip_v4_process_injected_impl(const rife_hip_t* E, const uint8_t*
     Ctx c; float* tmp = nullptr;
     const float* pending = nullptr;
     if ((rc = tap_prologue(E, c, in0, in1, w, h, inject, n_inject, tmp, &pending))) return rc;
-    const bool fuse_tail = trunk_h2() && g_head_h2 && g_fuse_tail && E->blk[3].head.d_wh != nullptr;
+    const bool fuse_tail = trunk_h2() && E->blk[3].head.d_wh != nullptr;
     FinalArgs fin{c.img0, c.img1, c.F, c.M, c.d_out, c.w, c.h, c.wp, c.hp};
     for (int b = n_inject; b < 4; b++) {
         if ((rc = run_block_convs(*E, c, b, timestep, (b == 3 && fuse_tail) ? &fin : nullptr, nullptr, PH_ALL, pending))) return rc;
@@ -1183,10 +1157,8 @@ static int rife_hip_graph_check_impl(const char* base) {
     GraphNet n;
     return graph_load(n, base, true);
 }
-int rife_hip_graph_check(const char* base) {      // nothing may throw across the C boundary (malformed model files, std::bad_alloc)
-    try { return rife_hip_graph_check_impl(base); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_graph_check: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_graph_check: unknown exception"); }
+int rife_hip_graph_check(const char* base) {
+    return guarded("rife_hip_graph_check", [&] { return rife_hip_graph_check_impl(base); });
 }
 
 #ifdef RIFE_HIP_TEST_BUILD      // ======== include/rife_hip_test.h (continued) ========
@@ -1419,10 +1391,8 @@ static int rife_hip_param_hash_impl(const char* param_path, const char* blob, ui
     *out = m.structural_hash(blob);
     return *out ? 0 : fail(RIFE_HIP_EMODEL, "no such blob");
 }
-int rife_hip_param_hash(const char* param_path, const char* blob, uint64_t* out) {      // nothing may throw across the C boundary (malformed model files, std::bad_alloc)
-    try { return rife_hip_param_hash_impl(param_path, blob, out); }
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string("rife_hip_param_hash: ") + e.what()); }
-    catch (...) { return fail(RIFE_HIP_EIO, "rife_hip_param_hash: unknown exception"); }
+int rife_hip_param_hash(const char* param_path, const char* blob, uint64_t* out) {
+    return guarded("rife_hip_param_hash", [&] { return rife_hip_param_hash_impl(param_path, blob, out); });
 }
 
 }  // extern "C"

@@ -72,20 +72,7 @@ static bool stem2_fusable(const ConvLayer& L, int S, int wp, int hp) {
 }
 template <int S, typename IMG, bool FSCALE, bool R64 = false>
 static int launch_stem2_cfg(const Stem2Args<IMG>& a, int nwg, hipStream_t st) {
-    auto kfn = stem2_fused_kernel<S, IMG, FSCALE, R64>;
-    {
-        static std::mutex mu; static std::map<int, bool> done;
-        int dev = 0; (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> g(mu);
-        if (!done[dev]) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, stem2_lds_bytes(4)));
-            done[dev] = true;
-        }
-    }
-    hipLaunchKernelGGL(kfn, dim3(nwg), dim3(512), stem2_lds_bytes(a.nsub, R64), st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("stem2_fused launch: ") + hipGetErrorString(e));
-    return 0;
+    return launch<stem2_fused_kernel<S, IMG, FSCALE, R64>>("stem2_fused launch", dim3(nwg), dim3(512), stem2_lds_bytes(a.nsub, R64), st, a);
 }
 template <typename IMG>
 static int launch_stem2_fused(const rife_hip& E, const ConvLayer& L, int S, bool fscale, IMG img0, IMG img1, const float4* acc, int wp, int hp, float* out, int out_ld,

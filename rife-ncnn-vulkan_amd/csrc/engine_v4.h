@@ -166,16 +166,6 @@ static int run_assemble(const rife_hip& E, Ctx& c, int b, float timestep, const 
 
 // block 3 of rife-v4.6: frames + F, M -> the first S16 trunk tensor (stem_rs.h); two workgroups per CU, all resident
 static int launch_stem_rs(const rife_hip& E, Ctx& c, const rife_hip::Block& B, unsigned char* out, int Hq, int Wq, float timestep, const float* tsp) {
-    {
-        int dev = 0; (void)hipGetDevice(&dev);
-        static std::mutex mu; static std::map<int, bool> done;
-        std::lock_guard<std::mutex> g(mu);
-        if (!done[dev]) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_rs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, SRS_LDS));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_rs_kernel<0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, SRS_LDS));
-            done[dev] = true;
-        }
-    }
     const S16Geom G(Hq, Wq);
     StemRsArgs a;
     a.img0 = c.img0; a.img1 = c.img1; a.F = c.F; a.M = c.M;
@@ -184,46 +174,27 @@ static int launch_stem_rs(const rife_hip& E, Ctx& c, const rife_hip::Block& B, u
     a.out = out; a.timestep = timestep; a.tsp = tsp; a.wp = c.wp; a.hp = c.hp; a.Hq = Hq; a.Wq = Wq; a.pitch = G.pitch; a.plane = G.plane();
     a.nunits = ((Wq + SRS_SW - 1) / SRS_SW) * Hq;
     const int nwg = std::min(2 * device_cus(), a.nunits);
-    if (pix_deep(c.pixfmt)) hipLaunchKernelGGL((stem_rs_kernel<0, 10>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
-    else hipLaunchKernelGGL((stem_rs_kernel<0>), dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("stem_rs launch: ") + hipGetErrorString(e));
-    return 0;
+    if (pix_deep(c.pixfmt)) return launch<stem_rs_kernel<0, 10>>("stem_rs launch", dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
+    return launch<stem_rs_kernel<0>>("stem_rs launch", dim3(nwg), dim3(SRS_NTHR), SRS_LDS, c.stream, a);
 }
 // block 3 of rife-v4.6: last S16 trunk tensor + F, M + frames -> u8 frame (tail_rs.h); two workgroups per CU, all resident
 static int launch_tail_rs(const rife_hip::Block& B, const unsigned char* in, int Hq, int Wq, const FinalArgs& fin, hipStream_t st) {
-    {
-        int dev = 0; (void)hipGetDevice(&dev);
-        static std::mutex mu; static std::map<int, bool> done;
-        std::lock_guard<std::mutex> g(mu);
-        if (!done[dev]) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_rs_kernel<0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, TRS_LDS));
-            done[dev] = true;
-        }
-    }
     const S16Geom G(Hq, Wq);
     TailRsArgs a;
     a.in = in; a.w = B.head.d_wh; a.bias = B.head.d_bias; a.img0 = fin.img0; a.img1 = fin.img1; a.F = fin.F; a.M = fin.M; a.out = fin.out;
     a.w_ = fin.w; a.h_ = fin.h; a.wp = fin.wp; a.hp = fin.hp; a.Hq = Hq; a.Wq = Wq; a.pitch = G.pitch; a.plane = G.plane();
     a.nunits = ((Wq + 31) / 32) * Hq;
     const int nwg = std::min(2 * device_cus(), a.nunits);
-    if (fin.pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL((tail_rs_kernel<0, 1>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
-    else if (fin.pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL((tail_rs_kernel<0, 2>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
-    else if (fin.pixfmt == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL((tail_rs_kernel<0, 4>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
-    else hipLaunchKernelGGL((tail_rs_kernel<0>), dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("tail_rs launch: ") + hipGetErrorString(e));
-    return 0;
+    return with_outfmt(fin.pixfmt, [&](auto of) {
+        return launch<tail_rs_kernel<0, decltype(of)::value>>("tail_rs launch", dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
+    });
 }
 
 // can block b's two stems run as one stem_rs launch?  (64-channel block 3 at scale 1 on the S16 trunk, 12 -> 32 -> 64 channels, uniform shapes)
 static bool block_on_stem_rs(const rife_hip& E, const Ctx& c, int b) {
     const rife_hip::Block& B = E.blk[b];
     return E.stem_rs && b == 3 && B.scale == 1 && B.c == 64 && B.stem0.d_wh && B.stem0.cout == 32 && B.stem1.d_whp && B.stem1.cout == 64 &&
-           trunk_h2() && g_fuse_stem && (c.hp % 4) == 0 && (c.wp % 4) == 0 &&
+           trunk_h2() && (c.hp % 4) == 0 && (c.wp % 4) == 0 &&
            (long long)c.wp * c.hp <= (1ll << 27);                       // the kernel addresses F (16 B per pixel) with 32-bit byte offsets; larger frames take the tile stems
 }
 
@@ -280,7 +251,7 @@ enum { PH_STEMS = 1, PH_TRUNK = 2, PH_HEAD = 4, PH_ALL = 7 };
 // Can the flow update after block b - 1 be left to block b's fused stem (stem_fused.h UPD)?  Blocks 2 and 3 of rife-v4.6 only: their stems
 // visit every full-resolution pixel.
 static bool flow_update_fused_into(const rife_hip& E, const Ctx& c, int b) {
-    return E.fuse_flow && !E.v40 && (b == 2 || b == 3) && c.F2 && E.blk[b].stem0.d_wh && trunk_h2() && g_fuse_stem;
+    return E.fuse_flow && !E.v40 && (b == 2 || b == 3) && c.F2 && E.blk[b].stem0.d_wh && trunk_h2();
 }
 
 // upd_flow != null: the flow of block b - 1, whose update of F, M this block's stem applies itself (flow_update_fused_into); F, M swap with F2, M2
@@ -295,51 +266,36 @@ static int run_block_convs(const rife_hip& E, Ctx& c, int b, float timestep, con
     const bool srs = !upd_flow && block_on_stem_rs(E, c, b) && block_on_s16(E, c, b);
     if (!(phases & PH_STEMS) || srs) goto after_stem0;
     if (b == 0 && (rc = run_assemble(E, c, 0, timestep, tsp))) return rc;
-    if (b > 0 && B.stem0.d_wh && trunk_h2() && g_fuse_stem) {
+    if (b > 0 && B.stem0.d_wh && trunk_h2()) {
         // assemble + stem-0 in one kernel (stem_fused.h): the block input never goes to HBM
         Timed t(E.prof, B.stem0.cls, B.stem0.flops_per_pixel * (Hb / 2) * (Wb / 2), st);
         StemFusedArgs fa;
         fa.img0 = c.img0; fa.img1 = c.img1; fa.F = c.F; fa.M = c.M; fa.wpk = B.stem0.d_wh; fa.bias = B.stem0.d_bias; fa.slope = B.stem0.d_slope;
         fa.out = c.S1; fa.timestep = timestep; fa.tsp = tsp; fa.wp = c.wp; fa.hp = c.hp; fa.Ho = Hb / 2; fa.Wo = Wb / 2; fa.out_ld = B.c / 2; fa.Cout = B.c / 2;
         fa.tiles_x = (fa.Wo + 31) / 32;
-        const int nb = fa.tiles_x * ((fa.Ho + 3) / 4);
-        {
-            static std::mutex fmu; static std::map<int, bool> fdone;
-            int dev = 0; (void)hipGetDevice(&dev);
-            std::lock_guard<std::mutex> g(fmu);
-            if (!fdone[dev]) {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0, 0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, 0, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<2, 2, 0, 1, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem0_fused_kernel<4, 2, 0, 2, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, stemf_lds_bytes<2>()));
-                fdone[dev] = true;
-            }
-        }
+        const dim3 grid(fa.tiles_x * ((fa.Ho + 3) / 4));
+        const char* const what = "hipGetLastError()";      // the error text this site has always had
         if (upd_flow) {
             if (s > 2 || !c.F2) return fail(RIFE_HIP_EINVAL, "no fused flow update for this block");
             fa.pend.flow = upd_flow; fa.pend.Fw = c.F2; fa.pend.Mw = c.M2;
-            if (pix_deep(c.pixfmt) && s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 1, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else if (pix_deep(c.pixfmt)) hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 1, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
-            else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, true>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, true>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
+            if (pix_deep(c.pixfmt) && s == 2) rc = launch<stem0_fused_kernel<2, 2, 0, 1, 10>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (pix_deep(c.pixfmt)) rc = launch<stem0_fused_kernel<1, 1, 256, 1, 10>>(what, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);
+            else if (s == 2) rc = launch<stem0_fused_kernel<2, 2, 0, true>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else rc = launch<stem0_fused_kernel<1, 1, 256, true>>(what, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);
             std::swap(c.F, c.F2); std::swap(c.M, c.M2);
         } else if (first_flow) {      // block 1 right after block 0: F, M are not materialised yet, the stem samples the first update itself (first_flow_merged)
             if (s != 4) return fail(RIFE_HIP_EINVAL, "the first flow update is sampled by the scale-4 stem only");
             fa.pend.flow = first_flow;
-            if (pix_deep(c.pixfmt)) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 2, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
+            if (pix_deep(c.pixfmt)) rc = launch<stem0_fused_kernel<4, 2, 0, 2, 10>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else rc = launch<stem0_fused_kernel<4, 2, 0, 2>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
         } else if (pix_deep(c.pixfmt)) {
-            if (s == 4) hipLaunchKernelGGL((stem0_fused_kernel<4, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2, 0, 0, 10>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-            else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256, 0, 10>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);
-        } else if (s == 4) hipLaunchKernelGGL((stem0_fused_kernel<4, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-        else if (s == 2) hipLaunchKernelGGL((stem0_fused_kernel<2, 2>), dim3(nb), dim3(512), stemf_lds_bytes<2>(), st, fa);
-        else hipLaunchKernelGGL((stem0_fused_kernel<1, 1, 256>), dim3(nb), dim3(512), (stemf_lds_bytes<1, 256>()), st, fa);      // 64-byte swizzled records, three workgroups per CU
-        HIPCHK(hipGetLastError());
+            if (s == 4) rc = launch<stem0_fused_kernel<4, 2, 0, 0, 10>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (s == 2) rc = launch<stem0_fused_kernel<2, 2, 0, 0, 10>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else rc = launch<stem0_fused_kernel<1, 1, 256, 0, 10>>(what, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);
+        } else if (s == 4) rc = launch<stem0_fused_kernel<4, 2>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+        else if (s == 2) rc = launch<stem0_fused_kernel<2, 2>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+        else rc = launch<stem0_fused_kernel<1, 1, 256>>(what, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);      // 64-byte swizzled records, three workgroups per CU
+        if (rc) return rc;
     } else {
         if (upd_flow || first_flow) return fail(RIFE_HIP_EINVAL, "fused flow update without the fused stem");
         if (b > 0 && (rc = run_assemble(E, c, b, timestep, tsp))) return rc;
@@ -461,7 +417,7 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         HIPCHK(hipGetLastError());
     }
     if (c.pixfmt && E.v40) return fail(RIFE_HIP_ENOSYS, "10-bit and RGBA frames are served for model family rife-v4.6 only, not rife-v4");
-    const bool fuse_tail = !E.v40 && trunk_h2() && g_head_h2 && g_fuse_tail && E.blk[3].head.d_wh != nullptr;
+    const bool fuse_tail = !E.v40 && trunk_h2() && E.blk[3].head.d_wh != nullptr;
     // 4:2:0: the quantising kernels write the internal A2B10G10R10 frame with the instantiations the packed 10-bit format uses; k_postproc_yuv follows below
     uint8_t* const caller_out = d_out;
     const int opf = pix_inner(c.pixfmt);
@@ -473,7 +429,7 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
     // 20 B / pixel of reads less.  RIFE_HIP_MERGE_FLOW0=0 (A/B, test build): the three separate updates.
     const Switches sw = read_switches();                     // per call
     const bool merge_env = sw.merge_flow0;
-    const bool merge0 = merge_env && !E.v40 && trunk_h2() && g_fuse_stem && E.blk[1].stem0.d_wh != nullptr && E.blk[1].scale == 4 && !flow_update_fused_into(E, c, 1) &&
+    const bool merge0 = merge_env && !E.v40 && trunk_h2() && E.blk[1].stem0.d_wh != nullptr && E.blk[1].scale == 4 && !flow_update_fused_into(E, c, 1) &&
                         !flow_update_fused_into(E, c, 2);
     // Both passes over F, M as cascades over the coarse flows (flow_cascade.h): F, M after block 2 are a function of flow0, flow1, flow2, so the pass after
     // block 2 writes them again from the flows instead of reading them back to add one term - the same per-pixel expressions in the same order, the same bits.
@@ -538,7 +494,7 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
         launch_preproc(c.stream, d_in1[g], c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt);
         HIPCHK(hipGetLastError());
     }
-    const bool fuse_tail = trunk_h2() && g_head_h2 && g_fuse_tail && E.blk[3].head.d_wh != nullptr;
+    const bool fuse_tail = trunk_h2() && E.blk[3].head.d_wh != nullptr;
     const float* pend[4] = {nullptr, nullptr, nullptr, nullptr};         // per pair: flow whose update the next block's stem applies (run_v4)
     auto after_block = [&](Ctx& c, int g, int b) -> int {
         if (b < 3 && flow_update_fused_into(E, c, b + 1)) { pend[g] = c.flow[b]; return 0; }

@@ -87,6 +87,21 @@ def test_env_switches_live_in_one_table():
     assert len(master.splitlines()) < 120
 
 
+def test_lds_opt_in_lives_in_one_launch_helper():
+    """ONE place raises a kernel's dynamic-LDS limit (csrc/engine_dispatch.h: launch<Kern>(), per kernel and device at the kernel's first launch), so no launcher
+    keeps a list of instantiations next to its launch ladder; and the round-1 A/B constants that steered launch_conv are gone, not merely unused.  Comments count."""
+    csrc = os.path.join(ROOT, "rife-ncnn-vulkan_amd", "csrc")
+    hits = []
+    for f in sorted(os.listdir(csrc)):
+        if not os.path.isfile(os.path.join(csrc, f)):
+            continue
+        src = open(os.path.join(csrc, f), errors="replace").read()
+        hits += [f] * src.count("hipFuncAttributeMaxDynamicSharedMemorySize")
+        for name in ("g_fuse_stem", "g_head_h2", "g_s2_h2", "g_splitk", "g_fuse_tail", "g_h2b", "g_use_conv8"):
+            assert re.search(r"(?<![A-Za-z0-9_])%s(?![A-Za-z0-9_])" % name, src) is None, (f, name)
+    assert hits == ["engine_dispatch.h"], hits
+
+
 def test_product_ignores_the_kernel_selection_switches():
     """The A/B and kernel-selection environment switches are compiled out of the product: in the switch table every direct getenv names one of the four
     documented product variables, everything else goes through ab(), which returns null unless RIFE_HIP_TEST_BUILD is defined; the product binary holds
