@@ -219,6 +219,29 @@ int rife_hip_process_device_image(const rife_hip_t* r, const rife_hip_image_t* i
 int rife_hip_frame_upload_image(const rife_hip_t* r, const rife_hip_image_t* img, rife_hip_frame_t** frame);
 int rife_hip_process_frames_image(const rife_hip_t* r, const rife_hip_frame_t* frame0, const rife_hip_frame_t* frame1, float timestep, const rife_hip_image_t* out);
 
+/* ---- UHD / flow scale: flow estimation at half resolution (upstream RIFE's scale=0.5; absent in the reference, whose process_v4 ignores uhd_mode) ----------
+ * Motion in 4K material is large in pixels; with every IFBlock at half its usual resolution the coarse pyramid reaches twice as far and the network does a quarter
+ * of its arithmetic, while the frames are still warped and blended at full resolution.  divisor 1 (the default) is the reference's graph; divisor 2 is that graph
+ * with the block scales 8, 4, 2, 1 doubled to 16, 8, 4, 2 (line numbers of models/rife-v4.6/flownet.param):
+ *   blocks 0..2  every Interp factor below 1 is halved and every factor above 1 doubled; the scalar of the BinaryOp mul / div next to an Interp (:50, :53, :108)
+ *                and the second coefficient of the two Eltwise sums (:102, :155) are doubled;
+ *   block 3      gets the resize layers the other blocks have: Interp(0.5) on its 8-channel concat (:164), Interp(0.5) then / 2 on the flow concatenated to it
+ *                (:165), Interp(2) on flow3, and F = F * 1 + u[0:4] * 2, M = M + u[4] in place of the plain adds (:204, :207); the rest of the tail is unchanged
+ *                (sigmoid, two warps of the full-resolution frames, blend, quantise);
+ *   padding      frames are zero-padded to a multiple of 64 (block 0's trunk runs at 1/64) and the output is cropped with the padded pitch; timestep 0 / 1
+ *                return the input frames as at divisor 1.
+ * tests/flowscale_ref.py states the rewrite on the .param text; a scale-2 frame is within one code per channel of the oracle running that graph.
+ * Every entry point, _px format and image call that plain rife-v4.6 serves is served at divisor 2 with the same bytes as the single call; the batch calls run the
+ * pair schedule once per pair (no lockstep groups), and the opt-in graph replay does not apply.  uhd_mode keeps doing nothing for rife-v4.x.
+ * rife_hip_set_flow_scale returns 0 or, leaving the engine unchanged, with a last-error message:
+ *   -RIFE_HIP_EINVAL  before rife_hip_load (the family is not known yet); divisor <= 0 or not a power of two; while a call on the engine is in flight;
+ *   -RIFE_HIP_ENOSYS  divisor 2 on any family other than rife-v4.6 or on an engine created with tta_mode / tta_temporal_mode (the message names the family or
+ *                     mode); divisor 4 and above (upstream's 0.25).
+ * divisor 1 always succeeds after load.  Call it while no call on the engine is in flight: it drops the engine's workspaces.
+ * Out of scope: divisor 4 (padding to 128), the other model families, -x / -z, lockstep groups and graph replay at divisor 2, any change to what uhd_mode does. */
+int rife_hip_set_flow_scale(rife_hip_t* r, int divisor);
+int rife_hip_flow_scale(const rife_hip_t* r);               /* the divisor in force (1 before load and for a null engine) */
+
 const char* rife_hip_last_error(void);
 
 /* ---- measurement hooks (bench.py / profiles) ---------------------------------------------------------------

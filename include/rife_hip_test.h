@@ -40,6 +40,12 @@ int rife_hip_v4_extract_flow_px(const rife_hip_t* r, const void* in0, const void
                                 int n_inject, float* out6chw, int pixfmt);
 int rife_hip_v4_tap_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, int what, int b, const float* const* inject,
                        int n_inject, float* out_chw, int pixfmt);
+/* Flow scale (include/rife_hip.h rife_hip_set_flow_scale): rife_hip_v4_extract_flow, rife_hip_v4_flow_dims and rife_hip_v4_process_injected honour the engine's
+ * divisor - at 2 the blobs flow0..3 are hp/16 .. hp/2 of the frame padded to 64n.  The gather taps (rife_hip_v4_tap) exist at divisor 1 only.
+ * rife_hip_v4_process_injected_px: flow injection with frames of an RGB format `pixfmt` (out: the same format).  At divisor 2 n_inject may be 4: block 3's update
+ * and the tail then run on the four injected blobs alone, in the product's final kernel (k_final_scaled).  At divisor 1: RGB8 and n_inject <= 3, the call above. */
+int rife_hip_v4_process_injected_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep,
+                                    const float* const* inject, int n_inject, void* out, int pixfmt);
 
 /* ---- single-kernel entry points for per-kernel parity tests (host arrays, planar CHW fp32 like ncnn::Mat) --- */
 /* 3x3 conv, pad 1, stride 1|2, + bias, optional residual add (same shape as output), per-channel negative slope

@@ -33,6 +33,7 @@ C_ABI_SYMBOLS = [
     "rife_hip_graph_check", "rife_hip_param_hash",
     "rife_hip_frame_bytes", "rife_hip_process_px", "rife_hip_process_device_px", "rife_hip_process_device_batch_px", "rife_hip_frame_upload_px",
     "rife_hip_image_check", "rife_hip_image_row_bytes", "rife_hip_process_image", "rife_hip_process_device_image", "rife_hip_frame_upload_image", "rife_hip_process_frames_image",
+    "rife_hip_set_flow_scale", "rife_hip_flow_scale",
 ]
 # pixel formats at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*)
 PIX_RGB8, PIX_RGB10_U16, PIX_A2B10G10R10 = 0, 1, 2
@@ -48,7 +49,7 @@ ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
-                    "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk"]
+                    "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px"]
 # rife_hip_op_trunk: which S16 trunk kernel (include/rife_hip_test.h RIFE_HIP_TRUNK_*)
 TRUNK_T64, TRUNK_RS, TRUNK_RS2, TRUNK_ROW, TRUNK_KS = 0, 1, 2, 3, 4
 EINVAL = 1      # RIFE_HIP_EINVAL: calls return its negative
@@ -118,6 +119,8 @@ def _load(path, with_test_surface):
     L.rife_hip_process_device_image.argtypes = [vp, ip, ip, cf, ip, vp]
     L.rife_hip_frame_upload_image.argtypes = [vp, ip, vp]
     L.rife_hip_process_frames_image.argtypes = [vp, vp, vp, cf, ip]
+    L.rife_hip_set_flow_scale.argtypes = [vp, ci]
+    L.rife_hip_flow_scale.argtypes = [vp]
     if with_test_surface:
         L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
         L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
@@ -125,6 +128,7 @@ def _load(path, with_test_surface):
         L.rife_hip_v4_flow_dims.argtypes = [vp, ci, ci, ci, vp, vp, vp]
         L.rife_hip_v4_tap.argtypes = [vp, vp, vp, ci, ci, cf, ci, ci, vp, ci, vp]
         L.rife_hip_v4_process_injected.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, vp]
+        L.rife_hip_v4_process_injected_px.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, vp, ci]
         L.rife_hip_op_conv3x3.argtypes = [ci, vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp]
         L.rife_hip_op_deconv4x4.argtypes = [ci, vp, ci, ci, ci, vp, vp, ci, vp, vp]
         L.rife_hip_op_warp.argtypes = [ci, vp, vp, ci, ci, ci, vp]
@@ -419,6 +423,18 @@ class RIFE:
         _check(self._L.rife_hip_load(self._h, os.fspath(modeldir).encode()), "load", self._L)
         return 0
 
+    def set_flow_scale(self, divisor):
+        """Estimate flow at 1 / divisor of the usual resolution (include/rife_hip.h: 1 = the reference's graph, 2 = every IFBlock at half resolution, frames
+        padded to 64n; rife-v4.6, plain mode - for UHD material).  Call after load() and while no call on the engine is in flight.  A refusal raises
+        RifeError with the C code (-1 bad divisor / before load, -6 another family or -x / -z) and leaves the engine unchanged."""
+        _check(self._L.rife_hip_set_flow_scale(self._h, int(divisor)), "set_flow_scale", self._L)
+        return 0
+
+    @property
+    def flow_scale(self):
+        """The flow scale divisor in force."""
+        return int(self._L.rife_hip_flow_scale(self._h))
+
     def process(self, in0image, in1image, timestep, outimage=None, pixfmt=None):
         """in0image / in1image: (h, w, 3) uint8 RGB arrays (the ncnn::Mat the CLI builds, src/main.cpp:187).
         Deep colour (rife-v4.6, plain mode): (h, w, 3) uint16 arrays of codes 0..1023 (RGB10_U16) or (h, w) uint32 arrays (A2B10G10R10), selected by the
@@ -692,8 +708,22 @@ class RIFE:
         _check(self._L.rife_hip_v4_tap(self._h, _p(a), _p(bb), w, h, float(timestep), int(what), int(b), arr, len(inj), _p(out)), "v4_tap", self._L)
         return out
 
-    def v4_process_injected(self, in0image, in1image, timestep, inject):
+    def v4_process_injected(self, in0image, in1image, timestep, inject, pixfmt=None):
+        """The plain pass with the first len(inject) flow blobs injected.  pixfmt (an RGB format) or four blobs (flow scale 2): the _px form, which writes the
+        frames' format."""
         self._need_taps()
+        px = _pix_of(in0image, pixfmt)
+        if px is not None or len(inject) > 3:
+            a = np.ascontiguousarray(in0image); bb = np.ascontiguousarray(in1image)
+            if a.shape != bb.shape or a.dtype != bb.dtype:
+                raise ValueError("both frames must have the same pixel format and size")
+            h, w = a.shape[:2]
+            out = np.empty_like(a)
+            inj = [np.ascontiguousarray(f, dtype=np.float32) for f in inject]
+            arr = (ctypes.c_void_p * max(1, len(inj)))(*[f.ctypes.data for f in inj])
+            _check(self._L.rife_hip_v4_process_injected_px(self._h, _p(a), _p(bb), w, h, float(timestep), arr, len(inj), _p(out), px or PIX_RGB8),
+                   "v4_process_injected_px", self._L)
+            return out
         a = np.ascontiguousarray(in0image, dtype=np.uint8); bb = np.ascontiguousarray(in1image, dtype=np.uint8)
         h, w, _ = a.shape
         out = np.empty((h, w, 3), np.uint8)

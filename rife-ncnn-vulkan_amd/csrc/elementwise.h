@@ -228,16 +228,16 @@ __device__ __forceinline__ float down4(float v00, float v01, float v10, float v1
     return r0 * 0.5f + r1 * 0.5f;
 }
 
-// Block-0 input: x = Interp(1/8)(Concat(in0, in1, in2)) -> NHWC8 {in0.rgb, in1.rgb, t, 0}   (flownet.param:9-10)
+// Block-0 input: x = Interp(1/S)(Concat(in0, in1, in2)) -> NHWC8 {in0.rgb, in1.rgb, t, 0}   (flownet.param:9-10; S = 8, flow scale 2: 16)
 // `tsp` != null: the timestep is read from device memory (hipGraph replays need launch parameters that never change)
-template <int D>
+template <int D, int S = 8>
 __device__ __forceinline__ void assemble0_body(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep_arg, const float* __restrict__ tsp,
                                                float* __restrict__ X, int wp, int hp) {
     const float timestep = tsp ? *tsp : timestep_arg;
-    const int Wb = wp / 8, Hb = hp / 8;
+    const int Wb = wp / S, Hb = hp / S;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= Wb || y >= Hb) return;
-    const int sx = 8 * x + 3, sy = 8 * y + 3;
+    const int sx = S * x + S / 2 - 1, sy = S * y + S / 2 - 1;
     const size_t i00 = (size_t)sy * wp + sx, i10 = i00 + wp;
     const float3 a0 = unpack_rgb<D>(img0[i00]), a1 = unpack_rgb<D>(img0[i00 + 1]), a2 = unpack_rgb<D>(img0[i10]), a3 = unpack_rgb<D>(img0[i10 + 1]);
     const float3 b0 = unpack_rgb<D>(img1[i00]), b1 = unpack_rgb<D>(img1[i00 + 1]), b2 = unpack_rgb<D>(img1[i10]), b3 = unpack_rgb<D>(img1[i10 + 1]);
@@ -256,6 +256,12 @@ __global__ void k_assemble0(const uint32_t* __restrict__ img0, const uint32_t* _
 __global__ void k_assemble0_d10(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep_arg, const float* __restrict__ tsp,
                                 float* __restrict__ X, int wp, int hp) {
     assemble0_body<10>(img0, img1, timestep_arg, tsp, X, wp, hp);
+}
+// flow scale 2 (include/rife_hip.h): block 0 reads the frames at 1/16
+template <int S, int D>
+__global__ void k_assemble0_s(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, float timestep_arg, const float* __restrict__ tsp,
+                              float* __restrict__ X, int wp, int hp) {
+    assemble0_body<D, S>(img0, img1, timestep_arg, tsp, X, wp, hp);
 }
 
 // ncnn linear_coeffs for an upscale by S (power of two): fx = (dx + 0.5) / S - 0.5 is exact in fp32 here
@@ -463,18 +469,11 @@ __device__ __forceinline__ void store_px10(uint8_t* __restrict__ out, size_t i, 
         o[0] = (uint16_t)(pk & 0x3ffu); o[1] = (uint16_t)((pk >> 10) & 0x3ffu); o[2] = (uint16_t)((pk >> 20) & 0x3ffu);
     }
 }
+// the tail from the final F (f) and mask logit (mm) of pixel (x, y) on: sigmoid, two warps, blend, quantise, store (shared by final_body and k_final_scaled)
 template <int PX>
-__device__ __forceinline__ void final_body(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
-                                           const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
+__device__ __forceinline__ void final_tail(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4 f, const float mm,
+                                           uint8_t* __restrict__ out, int x, int y, int w, int wp, int hp) {
     constexpr int D = px_depth(PX);
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= w || y >= h) return;
-    const size_t i = (size_t)y * wp + x;
-    const float* fl = flow3 + i * 8;
-    const float4 d = *reinterpret_cast<const float4*>(fl);
-    float4 f = F[i];
-    f.x = f.x + d.x; f.y = f.y + d.y; f.z = f.z + d.z; f.w = f.w + d.w;
-    const float mm = M[i] + fl[4];
     const float m = 1.f / (1.f + expf(-mm));
     const float rm = 1.0f - m;
     if (PX == 4) {      // RGBA8: alpha from the same taps as the colour
@@ -498,6 +497,19 @@ __device__ __forceinline__ void final_body(const uint32_t* __restrict__ img0, co
     o[1] = (uint8_t)min(max((int)(g * 255.f + 0.5f), 0), 255);
     o[2] = (uint8_t)min(max((int)(b * 255.f + 0.5f), 0), 255);
 }
+template <int PX>
+__device__ __forceinline__ void final_body(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                                           const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * wp + x;
+    const float* fl = flow3 + i * 8;
+    const float4 d = *reinterpret_cast<const float4*>(fl);
+    float4 f = F[i];
+    f.x = f.x + d.x; f.y = f.y + d.y; f.z = f.z + d.z; f.w = f.w + d.w;
+    const float mm = M[i] + fl[4];
+    final_tail<PX>(img0, img1, f, mm, out, x, y, w, wp, hp);
+}
 __global__ void k_final(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
                         const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
     final_body<0>(img0, img1, F, M, flow3, out, w, h, wp, hp);
@@ -506,6 +518,24 @@ template <int PX>
 __global__ void k_final_px(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
                            const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
     final_body<PX>(img0, img1, F, M, flow3, out, w, h, wp, hp);
+}
+
+// Flow scale 2 (include/rife_hip.h): block 3 runs at half resolution, so its update of F, M is one like the others' - u = Interp(2)(flow3),
+// F = F * 1 + u[0:4] * 2, M = M + u[4] - and it happens here, per output pixel, in front of the tail: the updated tensors never reach HBM (40 B per
+// pixel and one launch less than k_flow_update<2, false> + a tail).  flow3 is [hp / 2][wp / 2][8]; the expressions are flow_upsampled<2>'s and
+// flow_accumulate<2>'s in their order, then final_tail's.
+template <int PX>
+__global__ void k_final_scaled(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,
+                               const float* __restrict__ M, const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * wp + x;
+    float4 u; float um;
+    flow_upsampled<2>(flow3, wp, hp, x, y, u, um);
+    float4 f = F[i];
+    float mm = M[i];
+    flow_accumulate<2>(u, um, f, mm);
+    final_tail<PX>(img0, img1, f, mm, out, x, y, w, wp, hp);
 }
 
 // rife-v4 (4.0) tail (models/rife-v4/flownet.param:154-168): F and M are final after the block-3 flow update;

@@ -144,12 +144,43 @@ int rife_hip_load(rife_hip_t* E, const char* modeldir) {
     return guarded("rife_hip_load", [&] { return rife_hip_load_impl(E, modeldir); });
 }
 
+// ---- flow scale (include/rife_hip.h): every IFBlock of rife-v4.6 at 1 / divisor of its resolution ----
+int rife_hip_flow_scale(const rife_hip_t* E) { return E ? E->fscale : 1; }
+int rife_hip_set_flow_scale(rife_hip_t* E, int divisor) {
+    if (!E) return fail(RIFE_HIP_EINVAL, "null engine");
+    if (!E->loaded) return fail(RIFE_HIP_EINVAL, "set_flow_scale() before load(): the model family is not known yet");
+    if (divisor <= 0 || (divisor & (divisor - 1))) return fail(RIFE_HIP_EINVAL, "the flow scale divisor must be a power of two (1 or 2)");
+    if (divisor > 1) {
+        const char* what = E->v1 ? "model family rife (v1: rife, rife-HD, rife-UHD, rife-anime)" : (!E->v4 && E->v3) ? "model family rife-v3.x" : !E->v4 ? "model family rife-v2.x"
+                           : E->v40 ? "model family rife-v4 (4.0)" : E->tta ? "TTA mode (-x)" : E->tta_temporal ? "temporal TTA mode (-z)" : nullptr;
+        if (what) return fail(RIFE_HIP_ENOSYS, std::string("flow scale 2 is served for model family rife-v4.6 in plain mode only, not for ") + what);
+        if (divisor > 2) return fail(RIFE_HIP_ENOSYS, "flow scale 4 and above (upstream's scale 0.25) is not implemented");
+    }
+    if (divisor == E->fscale) return 0;
+    return guarded("rife_hip_set_flow_scale", [&] {
+        std::vector<std::unique_ptr<Ctx>> dead;                          // the workspaces were sized for the other padding and block scales; destroyed outside the lock
+        {
+            std::lock_guard<std::mutex> g(E->mu);
+            if (E->leased > 0) return fail(RIFE_HIP_EINVAL, "set_flow_scale() while a call on the engine is in flight");
+            dead.swap(E->free_ctx);
+            for (auto& kv : E->stream_ctx) dead.push_back(std::move(kv.second));
+            E->stream_ctx.clear();
+            static const int SC[4] = {8, 4, 2, 1};
+            for (int b = 0; b < 4; b++) E->blk[b].scale = SC[b] * divisor;
+            E->fscale = divisor;
+        }
+        if (!dead.empty()) (void)hipSetDevice(E->gpuid);
+        return 0;
+    });
+}
+
 static int process_common(const rife_hip* E, int w, int h, float timestep) {
     tl_cu_budget = 0;                                                    // every entry point starts on the whole chip; rife_hip_process_device sets its stream's part
     if (!E) return fail(RIFE_HIP_EINVAL, "null engine");
     if (!E->loaded) return fail(RIFE_HIP_EINVAL, "process() before load()");
     if (w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "bad frame size");
-    if ((long long)((w + 31) / 32 * 32) * ((h + 31) / 32 * 32) > (1ll << 27))      // element indices are ints and the widest full-resolution tensor has 16 channels; (stem_rs has its own gate, block_on_stem_rs)
+    const int pad = E->pad();                                            // 32n, rife.cpp:2499-2500; flow scale 2: 64n
+    if ((long long)((w + pad - 1) / pad * pad) * ((h + pad - 1) / pad * pad) > (1ll << 27))      // element indices are ints and the widest full-resolution tensor has 16 channels; (stem_rs has its own gate, block_on_stem_rs)
         return fail(RIFE_HIP_EINVAL, "frame too large (more than 2^27 padded pixels)");
     (void)timestep;
     if (E->uhd && !E->v4 && (((w + 31) / 32 * 32 / 2) % 32 || ((h + 31) / 32 * 32 / 2) % 32))
@@ -289,7 +320,7 @@ static int lease_ctx(const rife_hip* E, std::unique_ptr<Ctx>& c, int w, int h, i
         c->own_stream = true;
     }
     tl_cu_budget = c->cu_budget;                                         // the caller enqueues on this workspace's stream next
-    return E->v4 ? ensure_ctx(*c, w, h, pixfmt) : E->v1 ? ensure_ctx_v1(*c, w, h, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1)
+    return E->v4 ? ensure_ctx(*c, w, h, pixfmt, E->pad()) : E->v1 ? ensure_ctx_v1(*c, w, h, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1)
                                                 : ensure_ctx_v2(*c, w, h, E->uhd, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1, E->v3, ctx_batch_serves(*E));
 }
 
@@ -644,7 +675,7 @@ static int rife_hip_process_device_impl(const rife_hip_t* E, const void* d_in0, 
     } else {
         if (E->v1) rc = ensure_ctx_v1(*c, w, h, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1);
         else if (!E->v4) rc = ensure_ctx_v2(*c, w, h, E->uhd, E->tta ? 8 : 1, E->tta_temporal ? 2 : 1, E->v3, ctx_batch_serves(*E));
-        else if (!E->tta && !E->tta_temporal) rc = ensure_ctx(*c, w, h, pixfmt);      // the TTA pass has workspaces of its own
+        else if (!E->tta && !E->tta_temporal) rc = ensure_ctx(*c, w, h, pixfmt, E->pad());      // the TTA pass has workspaces of its own
         if (rc || (rc = run_pass(E, *c, (const uint8_t*)d_in0, (const uint8_t*)d_in1, w, h, timestep, (uint8_t*)d_out))) return rc;
     }
     if (!hip_stream) HIPCHK(hipStreamSynchronize(c->stream));
@@ -858,7 +889,7 @@ static int rife_hip_v4_extract_flow_impl(const rife_hip_t* E, const uint8_t* in0
     Ctx c;
     if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
     c.own_stream = true;
-    if ((rc = ensure_ctx(c, w, h, pixfmt))) return rc;
+    if ((rc = ensure_ctx(c, w, h, pixfmt, E->pad()))) return rc;
     const size_t nbytes = frame_bytes(w, h, pixfmt);
     HIPCHK(hipMemcpyAsync(c.d_in0, in0, nbytes, hipMemcpyHostToDevice, c.stream));
     HIPCHK(hipMemcpyAsync(c.d_in1, in1, nbytes, hipMemcpyHostToDevice, c.stream));
@@ -905,7 +936,7 @@ static int tap_prologue(const rife_hip_t* E, Ctx& c, const uint8_t* in0, const u
     int rc;
     if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
     c.own_stream = true;
-    if ((rc = ensure_ctx(c, w, h, pixfmt))) return rc;
+    if ((rc = ensure_ctx(c, w, h, pixfmt, E->pad()))) return rc;
     const size_t nbytes = frame_bytes(w, h, pixfmt);
     HIPCHK(hipMemcpyAsync(c.d_in0, in0, nbytes, hipMemcpyHostToDevice, c.stream));
     HIPCHK(hipMemcpyAsync(c.d_in1, in1, nbytes, hipMemcpyHostToDevice, c.stream));
@@ -940,6 +971,7 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
     int rc;
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (!E->v4 || E->v40) return fail(RIFE_HIP_EINVAL, "the gather taps exist for the rife-v4.6 graph only");
+    if (E->fscale != 1) return fail(RIFE_HIP_EINVAL, "the gather taps exist at flow scale 1 only");
     if (pix_bpp(pixfmt) == 0) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
     if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if (pixfmt && what == 3) return fail(RIFE_HIP_EINVAL, "tap 3 (an A/B form the product does not run) is served for RGB8 frames only");
@@ -1118,16 +1150,20 @@ int rife_hip_v4_tap_px(const rife_hip_t* E, const void* in0, const void* in1, in
 // product's own schedule (fused stems, fused tail of head_h2_kernel<EPI_FINAL>), so that flows which leave the frame by hundreds of pixels
 // reach exactly the gather code a real pass runs.  out: w x h u8 RGB.
 static int rife_hip_v4_process_injected_impl(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep,
-                                             const float* const* inject, int n_inject, uint8_t* out) {
+                                             const float* const* inject, int n_inject, uint8_t* out, int pixfmt = RIFE_HIP_PIX_RGB8) {
     int rc;
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (!E->v4 || E->v40) return fail(RIFE_HIP_EINVAL, "flow injection into the plain pass exists for the rife-v4.6 graph only");
-    if (n_inject < 0 || n_inject > 3) return fail(RIFE_HIP_EINVAL, "bad injection count");
+    // flow scale 2: flow3 may be injected too - block 3's update is applied by k_final_scaled, the kernel under test (blobs at the mode's sizes)
+    if (n_inject < 0 || n_inject > (E->fscale == 2 ? 4 : 3)) return fail(RIFE_HIP_EINVAL, "bad injection count");
+    if (pix_bpp(pixfmt) == 0) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
+    if (pixfmt != RIFE_HIP_PIX_RGB8 && E->fscale != 2) return fail(RIFE_HIP_EINVAL, "flow injection at flow scale 1 writes RGB8 frames only");
+    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
     Ctx c; float* tmp = nullptr;
     const float* pending = nullptr;
-    if ((rc = tap_prologue(E, c, in0, in1, w, h, inject, n_inject, tmp, &pending))) return rc;
-    const bool fuse_tail = trunk_h2() && E->blk[3].head.d_wh != nullptr;
+    if ((rc = tap_prologue(E, c, in0, in1, w, h, inject, n_inject, tmp, &pending, pixfmt))) return rc;
+    const bool fuse_tail = E->fscale == 1 && trunk_h2() && E->blk[3].head.d_wh != nullptr;
     FinalArgs fin{c.img0, c.img1, c.F, c.M, c.d_out, c.w, c.h, c.wp, c.hp};
     for (int b = n_inject; b < 4; b++) {
         if ((rc = run_block_convs(*E, c, b, timestep, (b == 3 && fuse_tail) ? &fin : nullptr, nullptr, PH_ALL, pending))) return rc;
@@ -1135,9 +1171,10 @@ static int rife_hip_v4_process_injected_impl(const rife_hip_t* E, const uint8_t*
         if (b < 3 && flow_update_fused_into(*E, c, b + 1)) pending = c.flow[b];
         else if (b < 3 && (rc = run_flow_update(*E, c, b))) return rc;
     }
-    if (!fuse_tail) hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], c.d_out, c.w, c.h, c.wp, c.hp);
+    if (E->fscale == 2) launch_final_scaled(c.stream, c, pixfmt, c.d_out);
+    else if (!fuse_tail) hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], c.d_out, c.w, c.h, c.wp, c.hp);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, c.d_out, (size_t)w * h * 3, hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipMemcpyAsync(out, c.d_out, frame_bytes(w, h, pixfmt), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
     return 0;
 }
@@ -1148,6 +1185,14 @@ int rife_hip_v4_process_injected(const rife_hip_t* E, const uint8_t* in0, const 
     for (int k = 0; k < n_inject && k < 4; k++) if (!inject[k]) return fail(RIFE_HIP_EINVAL, "null injected blob");
     try { return rife_hip_v4_process_injected_impl(E, in0, in1, w, h, timestep, inject, n_inject, out); }
     catch (const std::exception& e) { return fail(RIFE_HIP_EINVAL, std::string("v4_process_injected: ") + e.what()); }
+}
+int rife_hip_v4_process_injected_px(const rife_hip_t* E, const void* in0, const void* in1, int w, int h, float timestep,
+                                    const float* const* inject, int n_inject, void* out, int pixfmt) {
+    if (!in0 || !in1 || !out) return fail(RIFE_HIP_EINVAL, "null frame / output pointer");
+    if (n_inject > 0 && !inject) return fail(RIFE_HIP_EINVAL, "n_inject > 0 without blobs");
+    for (int k = 0; k < n_inject && k < 4; k++) if (!inject[k]) return fail(RIFE_HIP_EINVAL, "null injected blob");
+    try { return rife_hip_v4_process_injected_impl(E, static_cast<const uint8_t*>(in0), static_cast<const uint8_t*>(in1), w, h, timestep, inject, n_inject, static_cast<uint8_t*>(out), pixfmt); }
+    catch (const std::exception& e) { return fail(RIFE_HIP_EINVAL, std::string("v4_process_injected_px: ") + e.what()); }
 }
 
 #endif  // RIFE_HIP_TEST_BUILD
@@ -1165,7 +1210,7 @@ int rife_hip_graph_check(const char* base) {
 int rife_hip_v4_flow_dims(const rife_hip_t* E, int w, int h, int fi, int* channels, int* fh, int* fw) {
     if (!E || !E->loaded || !E->v4) return fail(RIFE_HIP_EINVAL, "flow blobs exist for a loaded rife-v4 family engine only");
     if (fi < 0 || fi > 3 || w <= 0 || h <= 0 || !channels || !fh || !fw) return fail(RIFE_HIP_EINVAL, "bad argument");
-    const int wp = (w + 31) / 32 * 32, hp = (h + 31) / 32 * 32;
+    const int pad = E->pad(), wp = (w + pad - 1) / pad * pad, hp = (h + pad - 1) / pad * pad;
     *channels = E->v40 ? 5 : 6; *fh = hp / E->flow_div(fi); *fw = wp / E->flow_div(fi);
     return 0;
 }

@@ -189,6 +189,10 @@ struct rife_hip {
     // staged through LDS (run_v4; RIFE_HIP_FLOW_CASCADE=0 in the test build: k_flow_update2 + k_flow_update<2, false>, which read F, M back after block 2).
     bool fuse_flow = false;
     int flow_div(int b) const { return v40 ? 2 * blk[b].scale : blk[b].scale; }
+    // rife_hip_set_flow_scale (rife-v4.6, plain mode): 2 = every IFBlock at half its resolution - blk[b].scale is then 16, 8, 4, 2, the frames are padded
+    // to 64n and block 3's update happens in k_final_scaled (run_v4)
+    int fscale = 1;
+    int pad() const { return 32 * fscale; }
     // rife-v2.x schedule (IFNet + ContextNet + FusionNet)
     struct V2Block { ConvLayer stem0, stem1, conv[6], head; int c = 0, scale = 1; } fblk[4];
     // rife-v3.x: same ContextNet / FusionNet, IFNet of 3 blocks (scales 4, 2, 1; 160 channels; trunk = 3 x [conv, conv, + skip])

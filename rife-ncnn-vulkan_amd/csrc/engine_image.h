@@ -206,7 +206,7 @@ static int rife_hip_process_device_image_impl(const rife_hip_t* E, const rife_hi
     if (timestep == 0.f || timestep == 1.f) {
         if ((rc = image_canon_device(c->stream, timestep == 0.f ? *in0 : *in1, *out))) return rc;
     } else {
-        if ((rc = ensure_ctx(*c, w, h, pixfmt))) return rc;
+        if ((rc = ensure_ctx(*c, w, h, pixfmt, E->pad()))) return rc;
         const PlaneIO pio{plane_set(*in0), plane_set(*in1), plane_set(*out)};
         rc = run_v4(*E, *c, nullptr, nullptr, timestep, c->d_out, nullptr, &pio);      // YUV: the pitched post-processing kernel writes the caller's planes; RGB formats: the tight frame c->d_out
         if (rc) return rc;

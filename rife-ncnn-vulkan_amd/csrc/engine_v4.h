@@ -98,8 +98,8 @@ static inline bool pix_deep(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB10_U1
 // the format the quantising kernels of a pass write: the caller's, or for YUV the internal A2B10G10R10 frame k_postproc_yuv / k_postproc_yuvc reads (Ctx::yuv_rgb)
 static inline int pix_inner(int pixfmt) { return pix_yuv(pixfmt) ? RIFE_HIP_PIX_A2B10G10R10 : pixfmt; }
 // the workspace serves frames of `pixfmt` from here on: staging buffers of that size, c.pixfmt for every launch site that reads or writes a frame
-static int ensure_ctx(Ctx& c, int w, int h, int pixfmt = RIFE_HIP_PIX_RGB8) {
-    int rc = ensure_ctx_dims(c, w, h, (w + 31) / 32 * 32, (h + 31) / 32 * 32, nullptr, true, false, frame_bytes(w, h, pixfmt));   // pad to 32n, rife.cpp:2499-2500
+static int ensure_ctx(Ctx& c, int w, int h, int pixfmt = RIFE_HIP_PIX_RGB8, int pad = 32) {
+    int rc = ensure_ctx_dims(c, w, h, (w + pad - 1) / pad * pad, (h + pad - 1) / pad * pad, nullptr, true, false, frame_bytes(w, h, pixfmt));   // pad to 32n, rife.cpp:2499-2500 (flow scale 2: 64n)
     if (!rc && pix_yuv(pixfmt) && !c.yuv_rgb && (rc = dalloc(c, c.yuv_rgb, (size_t)c.wp * c.hp))) reset_ctx(c);      // only once a YUV format is served
     if (!rc) c.pixfmt = pixfmt;
     return rc;
@@ -150,7 +150,19 @@ static int run_assemble(const rife_hip& E, Ctx& c, int b, float timestep, const 
     Timed t(E.prof, "assemble", 0, st);
     const int s = E.blk[b].scale;
     dim3 g = grid2d(c.wp / s, c.hp / s);
-    if (pix_deep(c.pixfmt)) {
+    if (E.fscale == 2) {      // block inputs at 1/16, 1/8, 1/4, 1/2
+        if (pix_deep(c.pixfmt)) {
+            if (b == 0) hipLaunchKernelGGL((k_assemble0_s<16, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.X, c.wp, c.hp);
+            else if (s == 8) hipLaunchKernelGGL((k_assemble<8, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+            else if (s == 4) hipLaunchKernelGGL((k_assemble<4, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+            else hipLaunchKernelGGL((k_assemble<2, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+        }
+        else if (b == 0) hipLaunchKernelGGL((k_assemble0_s<16, 8>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.X, c.wp, c.hp);
+        else if (s == 8) hipLaunchKernelGGL(k_assemble<8>, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+        else if (s == 4) hipLaunchKernelGGL(k_assemble<4>, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+        else hipLaunchKernelGGL(k_assemble<2>, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
+    }
+    else if (pix_deep(c.pixfmt)) {
         if (b == 0) hipLaunchKernelGGL(k_assemble0_d10, g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.X, c.wp, c.hp);
         else if (s == 4) hipLaunchKernelGGL((k_assemble<4, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
         else if (s == 2) hipLaunchKernelGGL((k_assemble<2, 10>), g, dim3(256), 0, st, c.img0, c.img1, timestep, tsp, c.F, c.M, c.X, c.wp, c.hp);
@@ -251,7 +263,7 @@ enum { PH_STEMS = 1, PH_TRUNK = 2, PH_HEAD = 4, PH_ALL = 7 };
 // Can the flow update after block b - 1 be left to block b's fused stem (stem_fused.h UPD)?  Blocks 2 and 3 of rife-v4.6 only: their stems
 // visit every full-resolution pixel.
 static bool flow_update_fused_into(const rife_hip& E, const Ctx& c, int b) {
-    return E.fuse_flow && !E.v40 && (b == 2 || b == 3) && c.F2 && E.blk[b].stem0.d_wh && trunk_h2();
+    return E.fuse_flow && !E.v40 && E.fscale == 1 && (b == 2 || b == 3) && c.F2 && E.blk[b].stem0.d_wh && trunk_h2();
 }
 
 // upd_flow != null: the flow of block b - 1, whose update of F, M this block's stem applies itself (flow_update_fused_into); F, M swap with F2, M2
@@ -275,7 +287,17 @@ static int run_block_convs(const rife_hip& E, Ctx& c, int b, float timestep, con
         fa.tiles_x = (fa.Wo + 31) / 32;
         const dim3 grid(fa.tiles_x * ((fa.Ho + 3) / 4));
         const char* const what = "hipGetLastError()";      // the error text this site has always had
-        if (upd_flow) {
+        if (E.fscale == 2) {      // blocks 1..3 at 1/8, 1/4, 1/2: the same kernel, instantiated by (scale, N-subtiles of the block's stem)
+            if (upd_flow || first_flow) return fail(RIFE_HIP_EINVAL, "no fused flow update at flow scale 2");
+            const bool deep = pix_deep(c.pixfmt);
+            if (s == 8 && B.stem0.NS == 2) rc = deep ? launch<stem0_fused_kernel<8, 2, 0, 0, 10>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa)
+                                                     : launch<stem0_fused_kernel<8, 2>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (s == 4 && B.stem0.NS == 2) rc = deep ? launch<stem0_fused_kernel<4, 2, 0, 0, 10>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa)
+                                                          : launch<stem0_fused_kernel<4, 2>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (s == 2 && B.stem0.NS == 1) rc = deep ? launch<stem0_fused_kernel<2, 1, 0, 0, 10>>(what, grid, dim3(512), stemf_lds_bytes<1>(), st, fa)
+                                                          : launch<stem0_fused_kernel<2, 1>>(what, grid, dim3(512), stemf_lds_bytes<1>(), st, fa);
+            else return fail(RIFE_HIP_EINVAL, "no fused stem for this block at flow scale 2");
+        } else if (upd_flow) {
             if (s > 2 || !c.F2) return fail(RIFE_HIP_EINVAL, "no fused flow update for this block");
             fa.pend.flow = upd_flow; fa.pend.Fw = c.F2; fa.pend.Mw = c.M2;
             if (pix_deep(c.pixfmt) && s == 2) rc = launch<stem0_fused_kernel<2, 2, 0, 1, 10>>(what, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
@@ -392,11 +414,26 @@ static int run_flow_update(const rife_hip& E, Ctx& c, int b) {
         HIPCHK(hipGetLastError());
         return 0;
     }
-    if (b == 0) hipLaunchKernelGGL((k_flow_update<8, true>), g, dim3(256), 0, st, c.flow[0], c.F, c.M, c.wp, c.hp);
+    if (E.fscale == 2) {      // Interp(16 / 8 / 4), coefficients 16 / 8 / 4; block 3's update (Interp(2)) is k_final_scaled's
+        if (b == 0) hipLaunchKernelGGL((k_flow_update<16, true>), g, dim3(256), 0, st, c.flow[0], c.F, c.M, c.wp, c.hp);
+        else if (b == 1) hipLaunchKernelGGL((k_flow_update<8, false>), g, dim3(256), 0, st, c.flow[1], c.F, c.M, c.wp, c.hp);
+        else if (b == 2) hipLaunchKernelGGL((k_flow_update<4, false>), g, dim3(256), 0, st, c.flow[2], c.F, c.M, c.wp, c.hp);
+        else return fail(RIFE_HIP_EINVAL, "block 3's flow update at flow scale 2 belongs to the final kernel");
+    }
+    else if (b == 0) hipLaunchKernelGGL((k_flow_update<8, true>), g, dim3(256), 0, st, c.flow[0], c.F, c.M, c.wp, c.hp);
     else if (b == 1) hipLaunchKernelGGL((k_flow_update<4, false>), g, dim3(256), 0, st, c.flow[1], c.F, c.M, c.wp, c.hp);
     else hipLaunchKernelGGL((k_flow_update<2, false>), g, dim3(256), 0, st, c.flow[2], c.F, c.M, c.wp, c.hp);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// flow scale 2: F, M after block 2 + flow3 at half resolution -> the frame in the format `opf` (k_final_scaled, elementwise.h)
+static void launch_final_scaled(hipStream_t st, const Ctx& c, int opf, uint8_t* d_out) {
+    const dim3 g = grid2d(c.w, c.h);
+    if (opf == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_scaled<1>, g, dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+    else if (opf == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_scaled<2>, g, dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+    else if (opf == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_scaled<4>, g, dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+    else hipLaunchKernelGGL(k_final_scaled<0>, g, dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
 }
 
 // RIFE::process_v4, non-TTA branch (rife.cpp:2931-3173) on device-resident frames.
@@ -417,7 +454,7 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         HIPCHK(hipGetLastError());
     }
     if (c.pixfmt && E.v40) return fail(RIFE_HIP_ENOSYS, "10-bit and RGBA frames are served for model family rife-v4.6 only, not rife-v4");
-    const bool fuse_tail = !E.v40 && trunk_h2() && E.blk[3].head.d_wh != nullptr;
+    const bool fuse_tail = !E.v40 && E.fscale == 1 && trunk_h2() && E.blk[3].head.d_wh != nullptr;      // the fused tails are scale-1 kernels
     // 4:2:0: the quantising kernels write the internal A2B10G10R10 frame with the instantiations the packed 10-bit format uses; k_postproc_yuv follows below
     uint8_t* const caller_out = d_out;
     const int opf = pix_inner(c.pixfmt);
@@ -461,6 +498,10 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         Timed t(E.prof, "final", 0, st);
         hipLaunchKernelGGL(k_blend_final, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, d_out, c.w, c.h, c.wp, c.hp);
         HIPCHK(hipGetLastError());
+    } else if (E.fscale == 2) {      // block 3's update and the tail in one pass (k_final_scaled)
+        Timed t(E.prof, "final", 0, st);
+        launch_final_scaled(st, c, opf, d_out);
+        HIPCHK(hipGetLastError());
     } else if (!fuse_tail) {
         Timed t(E.prof, "final", 0, st);
         if (opf == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
@@ -486,6 +527,13 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
 // Same kernels, same arguments per tensor: the frames are bit-identical to G single calls.
 static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t* const* d_in0, const uint8_t* const* d_in1, const float* ts, uint8_t* const* d_out) {
     int rc;
+    if (E.fscale != 1) {      // no lockstep at flow scale 2: the pair schedule once per pair, each on its workspace's stream
+        for (int g = 0; g < G; g++) {
+            tl_cu_budget = cs[g]->cu_budget;
+            if ((rc = run_v4(E, *cs[g], d_in0[g], d_in1[g], ts[g], d_out[g]))) return rc;
+        }
+        return 0;
+    }
     for (int g = 0; g < G; g++) {
         Ctx& c = *cs[g];
         if (!c.ev_group) HIPCHK(hipEventCreateWithFlags(&c.ev_group, hipEventDisableTiming));
@@ -566,7 +614,7 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
 static inline bool use_graph() { return process_switches().use_graph; }
 
 static int run_v4_replay(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t* d_in1, float timestep, uint8_t* d_out) {
-    const bool eligible = use_graph() && !E.prof.on && c.d_ts && c.pixfmt == RIFE_HIP_PIX_RGB8 &&      // the replay's staging copies and captured graph are the 8-bit pass
+    const bool eligible = use_graph() && E.fscale == 1 && !E.prof.on && c.d_ts && c.pixfmt == RIFE_HIP_PIX_RGB8 &&      // the replay's staging copies and captured graph are the 8-bit pass
                           (size_t)c.wp * c.hp <= (size_t)1920 * 1088;
     if (!eligible) return run_v4(E, c, d_in0, d_in1, timestep, d_out);
     hipStream_t st = c.stream;

@@ -39,6 +39,23 @@ int RIFE::load(const std::string& modeldir)
     return ret;
 }
 
+// A weak reference: a host program linked against an engine stand-in that predates the call (tests/test_cli_yuv.py links main.cpp and this file against two stub
+// files) still links; the call then reports -RIFE_HIP_ENOSYS.  librife_hip.so always defines it.
+extern "C" int rife_hip_set_flow_scale(rife_hip_t* r, int divisor) __attribute__((weak));
+
+int RIFE::set_flow_scale(int divisor)
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_set_flow_scale)
+    {
+        fprintf(stderr, "RIFE::set_flow_scale: this engine has no flow scale\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_set_flow_scale(engine, divisor);
+    if (ret) fprintf(stderr, "RIFE::set_flow_scale: %s\n", rife_hip_last_error());
+    return ret;
+}
+
 int RIFE::process(const ncnn::Mat& in0image, const ncnn::Mat& in1image, float timestep, ncnn::Mat& outimage) const
 {
     const int pixfmt = mat_pixfmt(in0image);

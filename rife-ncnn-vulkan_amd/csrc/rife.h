@@ -22,6 +22,11 @@ public:
 
     int process(const ncnn::Mat& in0image, const ncnn::Mat& in1image, float timestep, ncnn::Mat& outimage) const;
 
+    // Extension, not in the reference (include/rife_hip.h "UHD / flow scale"): estimate flow at 1 / divisor of the usual resolution - 1 = the reference's graph,
+    // 2 = every IFBlock at half its resolution (upstream RIFE's scale=0.5, for UHD material; rife-v4.6, plain mode).  After load(), with no call in flight.
+    // Returns the C-ABI's code; the message of a refusal is rife_hip_last_error().
+    int set_flow_scale(int divisor);
+
     // The reference exposes its four back-ends publicly (src/rife.h:25-29).  Here the HIP engine is the only one:
     // process_v4 == process for rife_v4 objects; the *_cpu entry points report an error (no CPU path in this build).
     int process_cpu(const ncnn::Mat& in0image, const ncnn::Mat& in1image, float timestep, ncnn::Mat& outimage) const;

@@ -163,6 +163,14 @@ rm -rf $T/out; mkdir -p $T/out
 run "asan pair" $ASAN -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/o.png -m rife-v4.6 -s 0.3
 $ASAN -0 $T/in_png/000.png -1 $T/nothing.png -o $T/out/o2.png -m rife-v4.6 > $T/log.txt 2>&1; rc=$?; echo "   asan missing input: rc $rc (sanitizer exit codes are 99 / 98)"; [ $rc -ge 98 ] && [ $rc -le 99 ] && FAIL=1
 $ASAN -0 $T/in_png/000.png -1 $T/in_big/000.png -o $T/out/o3.png -m rife-v4.6 > $T/log.txt 2>&1; rc=$?; echo "   asan size mismatch: rc $rc"; [ $rc -ge 98 ] && [ $rc -le 99 ] && FAIL=1
+echo "== 4b. flow scale (-d 2 through RIFE::set_flow_scale of the stub; refusals of -d 3 and of another family end before any engine exists) under both"
+for B in $ASAN $TSAN; do
+    run "$(basename $B) pair -d 2" $B -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/d2.png -m rife-v4.6 -d 2
+    $B -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/d3.png -m rife-v4.6 -d 3 > $T/log.txt 2>&1; rc=$?
+    [ $rc -eq 255 ] && [ ! -e $T/out/d3.png ] || { echo "   $(basename $B) -d 3: rc $rc (a refusal is 255 and writes nothing)"; FAIL=1; tail -20 $T/log.txt; }
+    $B -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/d23.png -m rife-v2.3 -d 2 > $T/log.txt 2>&1; rc=$?
+    [ $rc -eq 255 ] && [ ! -e $T/out/d23.png ] || { echo "   $(basename $B) -d 2 -m rife-v2.3: rc $rc (a refusal is 255 and writes nothing)"; FAIL=1; tail -20 $T/log.txt; }
+done
 echo "== 5. rife_hip_image_check's rules (csrc/image_check.h, host only) over refusing and accepting descriptors, a program of its own under ASan + UBSan"
 $ROOT/rife-ncnn-vulkan_amd/image-check-asan > $T/log.txt 2>&1; rc=$?
 echo "   image-check-asan: rc $rc, $(tail -1 $T/log.txt)"; [ $rc -ne 0 ] && { FAIL=1; tail -30 $T/log.txt; }
