@@ -139,7 +139,7 @@ void rife_hip_frame_release(rife_hip_frame_t* frame);
 #define RIFE_HIP_PIX_P010         18  /* u16 little-endian, the code in the HIGH 10 bits, NV12 plane layout; low bits ignored on input, written as zero */
 #define RIFE_HIP_PIX_I420P10      19  /* u16 little-endian, the code in the LOW 10 bits, I420 plane layout (what Y4M C420p10 holds); a larger value is read as 1023 */
 /* 4:2:2 and 4:4:4 (mezzanine and camera material; screen capture, animation masters, chains that upsampled chroma): 16 * class + 2 * (10 bits) + (planar), class 1 =
- * 4:2:0 above, 2 = 4:2:2, 3 = 4:4:4.  Planar only: 32, 34, 48, 50 (the semi-planar slots NV16 / P210 / NV24 / P410) are unknown formats, as are 20 .. 31 and 52 up.
+ * 4:2:0 above, 2 = 4:2:2, 3 = 4:4:4.  Planar only: 32, 34, 48, 50 (the semi-planar slots NV16 / P210 / NV24 / P410) are unknown formats, as are 20 .. 31 and 52 .. 64 (class 4 is planar RGB, below).
  * Chroma planes have h rows (not ch); YV16 / YV24: swap plane[1] and plane[2] of an image. */
 #define RIFE_HIP_PIX_I422         33  /* u8: planes Y w*h, Cb cw*h, Cr cw*h (what Y4M C422 holds) */
 #define RIFE_HIP_PIX_I422P10      35  /* u16 little-endian, the code in the LOW 10 bits, I422 plane layout; a larger value is read as 1023 */
@@ -172,9 +172,36 @@ void rife_hip_frame_release(rife_hip_frame_t* frame);
  * one colour description; rife_hip_process_frames refuses two frames that differ in either.
  * Scope: that of the 10-bit formats - model family rife-v4.6, plain mode, every frame size; any other family or mode returns -RIFE_HIP_ENOSYS with a message
  * that names it, before anything is written; the opt-in graph replay does not apply.  Out of scope: rife_hip_process_batch (the host batch), semi-planar
- * 4:2:2 / 4:4:4, 12-bit samples, planar RGB, alpha planes, interlaced chroma. */
+ * 4:2:2 / 4:4:4, 12-bit samples, alpha planes, interlaced chroma. */
 
-size_t rife_hip_frame_bytes(int w, int h, int pixfmt);      /* 0 for an unknown format or w, h <= 0; YUV: (w*h + 2*cw*ch) samples (4:2:2: ch = h; 4:4:4: cw = w, ch = h); colour bits are ignored */
+/* ---- planar RGB: three planes R, G, B of w x h samples each (absent in the reference, whose frames are packed 8-bit RGB) ----------------------------------------------
+ * What the RIFE filters of VapourSynth / AviSynth hold (RGB24, RGB30, RGBH, RGBS) and what ffmpeg calls gbrp / gbrp10le / gbrpf32le.  Class 4 of the numbering
+ * 16 * class + 2 * k + (planar), k = 0 u8, 1 u16, 2 half, 3 float; 64, 66, 68, 70 (the packed slots) and 72 up are unknown formats.  A tight frame is the three planes
+ * glued one after the other, R first; an image names them in plane[0..2] with a byte pitch each.  ffmpeg's G, B, R order needs no format of its own: the caller
+ * permutes plane[] (the three planes are treated alike), as for YV12.  A colour description OR-ed onto these formats is -RIFE_HIP_EINVAL, as on every RGB format. */
+#define RIFE_HIP_PIX_RGBP8        65  /* u8 */
+#define RIFE_HIP_PIX_RGBP10       67  /* u16 little-endian, the code in the LOW ten bits; a larger value is read as 1023 (as I444P10) */
+#define RIFE_HIP_PIX_RGBPH        69  /* IEEE binary16, nominal range [0, 1] */
+#define RIFE_HIP_PIX_RGBPF        71  /* IEEE binary32, nominal range [0, 1] */
+/* A planar RGB call is, byte for byte, the A2B10G10R10 call on the converted frames, converted back:
+ *     out = from10(process_px(to10(in0), to10(in1), timestep, A2B10G10R10))
+ * with the conversions fixed to the bit (tests/planar_ref.py states them in numpy, csrc/planar_rgb.h in HIP):
+ *   to10    u8: (v << 2) | (v >> 6) (what `rife-hip -b 10` does to an 8-bit file);  u16: min(v, 1023);
+ *           half and float, on the value x widened to fp32: (int)(fminf(fmaxf(x, 0.f), 1.f) * 1023.f + 0.5f), the product and the sum rounded separately (no fused
+ *           multiply-add).  NaN and negative values read as 0, +inf and values above 1 as 1023.
+ *   from10  u8: c >> 2;  u16: c;  float: (float)c / 1023.f, a correctly rounded division (not a product with a reciprocal: the two differ in 24 of the 1024 codes);
+ *           half: that float rounded to nearest even.
+ * to10(from10(c)) == c for every code in all four formats and u8 -> 10 -> u8 is the identity, so the engine's 1-code contract carries across unchanged (RGBP8: at
+ * most one code at depth 8, since one 10-bit code moves c >> 2 by at most one); an 8-bit value carried as the float v / 255.f comes back as a float that rounds to v.
+ * The padding to 32n (64n at flow scale 2) is zero RGB, as everywhere.  timestep 0 / 1 return the first / second frame's CANONICAL samples from10(to10(v)): a float
+ * frame comes back quantised and NaN comes back as 0.
+ * Depth limit: the resident frame holds ten bits per channel, and that is the precision of the half and float formats - a float frame is quantised to 1024 levels on
+ * the way in and the result is one of 1024 values.  Storing the un-quantised blend for float output is out of scope.
+ * Scope: that of the YUV formats - model family rife-v4.6, plain mode, both flow scales, every frame size, every _px call, rife_hip_process_frames and the image calls;
+ * any other family or mode returns -RIFE_HIP_ENOSYS with a message that names it, before anything is written; the opt-in graph replay does not apply.  Out of scope:
+ * rife_hip_process_batch (the host batch), packed float RGB, planar RGBA / alpha planes, 12- and 16-bit integer planes. */
+
+size_t rife_hip_frame_bytes(int w, int h, int pixfmt);      /* 0 for an unknown format or w, h <= 0; YUV: (w*h + 2*cw*ch) samples (4:2:2: ch = h; 4:4:4: cw = w, ch = h); planar RGB: 3 * w * h samples; colour bits are ignored */
 int rife_hip_process_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt);
 int rife_hip_process_device_px(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt,
                                void* hip_stream);
@@ -190,14 +217,14 @@ int rife_hip_frame_upload_px(const rife_hip_t* r, const void* pixels, int w, int
  * descriptor names each plane and the BYTES from one of its rows to the next, and the image calls read and write those planes in place. */
 typedef struct rife_hip_image {
     int w, h, pixfmt;        /* pixfmt as for the _px calls, colour bits included */
-    void* plane[3];          /* RGB8 / RGB10_U16 / A2B10G10R10 / RGBA8: plane[0];  NV12 / P010: Y, CbCr;  I420 / I422 / I444 and their P10 forms: Y, Cb, Cr */
+    void* plane[3];          /* RGB8 / RGB10_U16 / A2B10G10R10 / RGBA8: plane[0];  NV12 / P010: Y, CbCr;  I420 / I422 / I444 and their P10 forms: Y, Cb, Cr;  RGBP8 / RGBP10 / RGBPH / RGBPF: R, G, B */
     ptrdiff_t pitch[3];      /* BYTES from one row of the plane to the next */
 } rife_hip_image_t;
 /* Entries of plane[] and pitch[] that the format does not use are ignored.  YV12 and its 10-bit form need no format of their own: the caller swaps plane[1] and
  * plane[2] of an I420 / I420P10 image.
  * Rules (the check function below states them, and every image call repeats them before it touches anything; a violation is -RIFE_HIP_EINVAL with a message):
  *   w, h > 0 and pixfmt is one the _px calls accept; every plane the format has is non-NULL; each pitch is positive, at least the plane's row bytes, at most
- *   INT32_MAX and a multiple of the plane's element size (1 for the u8 formats, 2 for the u16 formats, 4 for A2B10G10R10); each plane pointer is aligned to that
+ *   INT32_MAX and a multiple of the plane's element size (1 for the u8 formats, 2 for the u16 and half formats, 4 for A2B10G10R10 and float planes); each plane pointer is aligned to that
  *   element size.  A negative pitch (bottom-up rows) is refused.  The three images of one call agree in w, h and pixfmt.
  *   Output planes must not overlap each other or the inputs (documented, not checked).
  * Contract: an image call is, byte for byte, the _px call on the same samples repacked tight, with the result unpacked into `out`.  It writes only the first

@@ -68,7 +68,8 @@ int rife_hip_op_rgb10_to_yuv(int gpuid, const uint32_t* a2b10g10r10, int w, int 
  * device allocation with the same pitches and the same pointer alignment modulo 16, so the form the host picks is the one it would pick for the caller's planes.
  * force_scalar: 0 = the host's choice, 1 = the scalar form, 2 (image_to_resident only, a TIGHT image) = the tight kernels of the _px path, the reference.
  * image_to_resident: the pre-processing kernel -> the resident form, hp x wp dwords (depth 8: R | G << 8 | B << 16 | A << 24, depth 10: R | G << 10 | B << 20).
- * resident_to_image: tight_frame = what the pass leaves behind - for a YUV format h x w A2B10G10R10 dwords (k_postproc_yuv's input), for an RGB format the tight
+ * resident_to_image: tight_frame = what the pass leaves behind - for a YUV or planar RGB format h x w A2B10G10R10 dwords (k_postproc_yuv's / k_postproc_rgbp's
+ * input; csrc/planar_rgb.h serves tight frames and pitched planes with one kernel set, so these two calls reach every form of it), for a packed RGB format the tight
  * frame of that format (the store kernel's input); the planes come back with every byte the kernel did not write as it went in. */
 int rife_hip_op_image_to_resident(int gpuid, const rife_hip_image_t* host_img, int force_scalar, uint32_t* out_padded);
 int rife_hip_op_resident_to_image(int gpuid, const uint32_t* tight_frame, const rife_hip_image_t* host_img_out, int force_scalar);

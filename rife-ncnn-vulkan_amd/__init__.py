@@ -43,6 +43,9 @@ PIX_NV12, PIX_I420, PIX_P010, PIX_I420P10 = 16, 17, 18, 19      # 5 .. 15 are re
 # 4:2:2 and 4:4:4, planar (16 * class + 2 * (10 bits) + planar; class 2 = 4:2:2, 3 = 4:4:4): Y (h, w), then Cb and Cr of (h, cw) / (h, w) samples
 PIX_I422, PIX_I422P10, PIX_I444, PIX_I444P10 = 33, 35, 49, 51
 _YUV_FORMATS = (PIX_NV12, PIX_I420, PIX_P010, PIX_I420P10, PIX_I422, PIX_I422P10, PIX_I444, PIX_I444P10)
+# planar RGB (class 4; k = 0 u8, 1 u16, 2 half, 3 float): three (h, w) planes R, G, B of uint8 / uint16 (codes 0..1023) / float16 / float32 (nominal range [0, 1])
+PIX_RGBP8, PIX_RGBP10, PIX_RGBPH, PIX_RGBPF = 65, 67, 69, 71
+_RGBP_DTYPE = {PIX_RGBP8: np.uint8, PIX_RGBP10: np.uint16, PIX_RGBPH: np.float16, PIX_RGBPF: np.float32}
 CSP_BT709, CSP_BT601, CSP_BT2020NCL = 0 << 8, 1 << 8, 2 << 8
 CSP_FULL = 1 << 12
 ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
@@ -277,6 +280,13 @@ def _yuv_buf(buf, w, h, pixfmt, what):
     return buf
 
 
+def planar_rgb_dtype(pixfmt):
+    """The sample type of a planar RGB format (PIX_RGBP8 / RGBP10 / RGBPH / RGBPF); ValueError for anything else (a colour description included)."""
+    if pixfmt not in _RGBP_DTYPE:
+        raise ValueError("%r is not a planar RGB pixfmt" % (pixfmt,))
+    return _RGBP_DTYPE[pixfmt]
+
+
 _PIX_LAYOUT = {PIX_RGB8: (np.uint8, 3), PIX_RGB10_U16: (np.uint16, 3), PIX_A2B10G10R10: (np.uint32, 2), PIX_RGBA8: (np.uint8, 3)}      # dtype, ndim
 _PIX_NAME = {PIX_RGB10_U16: "RGB10_U16", PIX_A2B10G10R10: "A2B10G10R10", PIX_RGBA8: "RGBA8"}
 
@@ -309,7 +319,7 @@ def _pix_of(image, pixfmt=None):
 
 
 _ELEM = {PIX_RGB8: 1, PIX_RGB10_U16: 2, PIX_A2B10G10R10: 4, PIX_RGBA8: 1, PIX_NV12: 1, PIX_I420: 1, PIX_P010: 2, PIX_I420P10: 2,
-         PIX_I422: 1, PIX_I422P10: 2, PIX_I444: 1, PIX_I444P10: 2}
+         PIX_I422: 1, PIX_I422P10: 2, PIX_I444: 1, PIX_I444P10: 2, PIX_RGBP8: 1, PIX_RGBP10: 2, PIX_RGBPH: 2, PIX_RGBPF: 4}
 
 
 def image_row_bytes(w, pixfmt, plane):
@@ -370,11 +380,18 @@ def image_of(a, pixfmt=None):
 def planes_image(planes, w, h, pixfmt, what="planes", writable=False):
     """The descriptor of a YUV frame given as a tuple of 2-D arrays, each with its own base and row stride: (h, w) luma and, cw, ch = yuv_chroma_dims(w, h, pixfmt),
     one (ch, 2 * cw) array of interleaved pairs (NV12, P010) or two (ch, cw) arrays Cb, Cr (I420, I422, I444 and their P10 forms; swap them for YV12 / YV16 /
-    YV24).  Raises ValueError."""
-    base = _yuv_base(pixfmt)
-    dt = yuv_dtype(pixfmt)
-    cw, ch = yuv_chroma_dims(w, h, pixfmt)
-    shapes = [(h, w), (ch, 2 * cw)] if base in (PIX_NV12, PIX_P010) else [(h, w), (ch, cw), (ch, cw)]
+    YV24).  Planar RGB (PIX_RGBP8 / RGBP10 / RGBPH / RGBPF): three (h, w) arrays R, G, B of planar_rgb_dtype(pixfmt) (permute them for ffmpeg's G, B, R order), or one
+    (3, h, w) array.  Raises ValueError."""
+    if pixfmt in _RGBP_DTYPE:
+        dt = planar_rgb_dtype(pixfmt)
+        shapes = [(h, w)] * 3
+        if isinstance(planes, np.ndarray) and planes.ndim == 3:
+            planes = tuple(planes)
+    else:
+        base = _yuv_base(pixfmt)
+        dt = yuv_dtype(pixfmt)
+        cw, ch = yuv_chroma_dims(w, h, pixfmt)
+        shapes = [(h, w), (ch, 2 * cw)] if base in (PIX_NV12, PIX_P010) else [(h, w), (ch, cw), (ch, cw)]
     if w <= 0 or h <= 0 or len(planes) != len(shapes):
         raise ValueError("%s: %d arrays of shapes %s" % (what, len(shapes), shapes))
     for a, shp in zip(planes, shapes):
@@ -383,6 +400,11 @@ def planes_image(planes, w, h, pixfmt, what="planes", writable=False):
     im = device_image(w, h, pixfmt, [(a.ctypes.data, _pitch(a)) for a in planes])
     im._keep = tuple(planes)
     return im
+
+
+def _plane_tuple(planes):
+    """A (3, h, w) array stands for its three planes."""
+    return tuple(planes) if isinstance(planes, np.ndarray) and planes.ndim == 3 else planes
 
 
 class Frame:
@@ -491,8 +513,12 @@ class RIFE:
         return call
 
     def process_planes(self, planes0, planes1, timestep, pixfmt, out=None):
-        """YUV frames as tuples of 2-D plane arrays, each with its own base and row stride (what VapourSynth's plane views or an AVFrame's data / linesize
-        are; shapes: planes_image()).  Nothing is repacked on the host.  out: a tuple of writable plane arrays to fill, or None; returns the output planes."""
+        """YUV or planar RGB frames as tuples of 2-D plane arrays, each with its own base and row stride (what VapourSynth's plane views or an AVFrame's data /
+        linesize are; shapes: planes_image()).  Nothing is repacked on the host.  out: a tuple of writable plane arrays to fill, or None; returns the output planes.
+        A planar RGB frame may also be one (3, h, w) array (it is passed as tuple(a))."""
+        planes0, planes1 = _plane_tuple(planes0), _plane_tuple(planes1)
+        if out is not None:
+            out = _plane_tuple(out)
         h, w = planes0[0].shape if len(planes0) and isinstance(planes0[0], np.ndarray) and planes0[0].ndim == 2 else (0, 0)
         a = planes_image(planes0, w, h, pixfmt, "planes0"); b = planes_image(planes1, w, h, pixfmt, "planes1")
         if out is None:
@@ -502,7 +528,9 @@ class RIFE:
         return tuple(out)
 
     def upload_planes(self, planes, pixfmt):
-        """Stream mode for a YUV frame given as plane arrays (process_planes); the resident frame is that of upload_yuv() on the packed frame."""
+        """Stream mode for a YUV or planar RGB frame given as plane arrays (process_planes); the resident frame is that of the _px upload of the packed frame.
+        process_frames() on planar RGB frames returns a (3, h, w) array."""
+        planes = _plane_tuple(planes)
         h, w = planes[0].shape if len(planes) and isinstance(planes[0], np.ndarray) and planes[0].ndim == 2 else (0, 0)
         a = planes_image(planes, w, h, pixfmt, "planes")
         f = ctypes.c_void_p()
@@ -567,7 +595,10 @@ class RIFE:
         if frame0.pixfmt != frame1.pixfmt:
             raise ValueError("the two frames differ in pixel format")
         if frame0.pixfmt != PIX_RGB8:      # the result has the format the frames were uploaded in
-            if (frame0.pixfmt & 0xff) >= PIX_NV12:
+            if frame0.pixfmt in _RGBP_DTYPE:
+                dt = planar_rgb_dtype(frame0.pixfmt)
+                shape = (3, frame0.h, frame0.w)
+            elif (frame0.pixfmt & 0xff) >= PIX_NV12:
                 dt = yuv_dtype(frame0.pixfmt)
                 shape = (yuv_frame_bytes(frame0.w, frame0.h, frame0.pixfmt) // np.dtype(dt).itemsize,)
             else:
@@ -586,7 +617,7 @@ class RIFE:
 
     def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
         """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
-        if pixfmt not in _PIX_LAYOUT:
+        if pixfmt not in _PIX_LAYOUT and pixfmt not in _RGBP_DTYPE:
             _yuv_base(pixfmt)
         if pixfmt != PIX_RGB8:
             _check(self._L.rife_hip_process_device_px(self._h, d_in0, d_in1, w, h, float(timestep), d_out, pixfmt, stream), "process_device_px", self._L)
@@ -604,7 +635,7 @@ class RIFE:
 
     def process_device_batch(self, d_in0, d_in1, w, h, timesteps, d_out, stream=None, pixfmt=PIX_RGB8):
         """n resident pairs in one call (rife_hip_process_device_batch): lists of device pointers; enqueued relative to `stream`."""
-        if pixfmt not in _PIX_LAYOUT:
+        if pixfmt not in _PIX_LAYOUT and pixfmt not in _RGBP_DTYPE:
             _yuv_base(pixfmt)
         n = len(d_in0)
         if len(d_in1) != n or len(d_out) != n or len(timesteps) != n:

@@ -199,7 +199,7 @@ static int pixfmt_supported(const rife_hip* E, int pixfmt) {
     if (pixfmt == RIFE_HIP_PIX_RGB8) return 0;
     const char* what = not_plain_v46(E);
     if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : pix_yuv(pixfmt) ? "YUV" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
+    return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : pix_yuv(pixfmt) ? "YUV" : pix_rgbp(pixfmt) ? "planar RGB" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
 }
 // argument checks of the _px entry points that need no engine; then "no HIP device at all" before anything looks at the engine
 // a pixfmt argument = format | colour description (include/rife_hip.h RIFE_HIP_CSP_*): both must be something the library knows
@@ -217,9 +217,10 @@ static int px_precheck(int pixfmt, bool ptrs_ok, int w, int h) {
     return 0;
 }
 // timestep 0 / 1 at depth 10: the input frame in canonical form (samples clamped to 1023, alpha bits 3) - what a pass over identical frames would write
-// (YUV: the samples' codes - P010 low bits cleared, the planar 10-bit samples clamped to 1023, 8-bit frames unchanged)
+// (YUV: the samples' codes - P010 low bits cleared, the planar 10-bit samples clamped to 1023, 8-bit frames unchanged; planar RGB: from10(to10(v)), planar_rgb.h)
 static void canon10_host(void* out, const void* in, int w, int h, int pixfmt) {
     const size_t npix = (size_t)w * h;
+    if (pix_rgbp(pixfmt)) { canon_row_host(canon_mode(pixfmt), static_cast<const uint8_t*>(in), static_cast<uint8_t*>(out), frame_bytes(w, h, pixfmt)); return; }
     if (pix_yuv(pixfmt)) {
         const size_t nbytes = frame_bytes(w, h, pixfmt);
         if (yuv_depth(pix_base(pixfmt)) == 8) { std::memmove(out, in, nbytes); return; }
@@ -247,7 +248,11 @@ static int copy_frame_device(hipStream_t st, const void* src, void* dst, int w, 
         if (pix_base(pixfmt) == RIFE_HIP_PIX_P010) hipLaunchKernelGGL(k_canon_yuv10<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), n);
         else hipLaunchKernelGGL(k_canon_yuv10<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), n);
     }
-    else { HIPCHK(hipMemcpyAsync(dst, src, frame_bytes(w, h, pixfmt), hipMemcpyDeviceToDevice, st)); return 0; }      // RGB8, RGBA8 and 8-bit YUV: the bytes unchanged
+    else if (pix_rgbp(pixfmt) && canon_mode(pixfmt) != CANON_BYTES) {      // a tight planar frame is 3 h rows of w samples
+        const size_t rb = (size_t)w * rgbp_elem(pix_base(pixfmt));
+        launch_canon_rows(st, canon_mode(pixfmt), static_cast<const uint8_t*>(src), rb, static_cast<uint8_t*>(dst), rb, rb, 3 * h);
+    }
+    else { HIPCHK(hipMemcpyAsync(dst, src, frame_bytes(w, h, pixfmt), hipMemcpyDeviceToDevice, st)); return 0; }      // RGB8, RGBA8, RGBP8 and 8-bit YUV: the bytes unchanged
     HIPCHK(hipGetLastError());
     return 0;
 }

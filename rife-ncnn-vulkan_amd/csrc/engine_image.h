@@ -56,9 +56,7 @@ static void image_canon_host(const rife_hip_image_t& out, const rife_hip_image_t
         for (int y = 0; y < rife_img::plane_rows(in.h, in.pixfmt, p); y++) {
             const uint8_t* s = static_cast<const uint8_t*>(in.plane[p]) + (size_t)y * in.pitch[p];
             uint8_t* d = static_cast<uint8_t*>(out.plane[p]) + (size_t)y * out.pitch[p];
-            if (mode == CANON_BYTES) std::memmove(d, s, rb);
-            else if (mode == CANON_PACKED_ALPHA) { const uint32_t* a = reinterpret_cast<const uint32_t*>(s); uint32_t* b = reinterpret_cast<uint32_t*>(d); for (size_t i = 0; i < rb / 4; i++) b[i] = a[i] | 0xc0000000u; }
-            else { const uint16_t* a = reinterpret_cast<const uint16_t*>(s); uint16_t* b = reinterpret_cast<uint16_t*>(d); for (size_t i = 0; i < rb / 2; i++) b[i] = mode == CANON_P010 ? (uint16_t)(a[i] & 0xffc0u) : std::min<uint16_t>(a[i], 1023); }
+            canon_row_host(mode, s, d, rb);
         }
     }
 }
@@ -71,11 +69,7 @@ static int image_canon_device(hipStream_t st, const rife_hip_image_t& in, const 
         const uint8_t* s = static_cast<const uint8_t*>(in.plane[p]); uint8_t* d = static_cast<uint8_t*>(out.plane[p]);
         const size_t sp = (size_t)in.pitch[p], dp = (size_t)out.pitch[p];
         if (mode == CANON_BYTES) { HIPCHK(hipMemcpy2DAsync(d, dp, s, sp, rb, (size_t)rows, hipMemcpyDeviceToDevice, st)); continue; }
-        const int n = (int)(rb / (mode == CANON_PACKED_ALPHA ? 4 : 2));
-        const dim3 g((n + 255) / 256, rows);
-        if (mode == CANON_U16_CLAMP) hipLaunchKernelGGL(k_canon_rows<CANON_U16_CLAMP>, g, dim3(256), 0, st, s, sp, d, dp, n);
-        else if (mode == CANON_PACKED_ALPHA) hipLaunchKernelGGL(k_canon_rows<CANON_PACKED_ALPHA>, g, dim3(256), 0, st, s, sp, d, dp, n);
-        else hipLaunchKernelGGL(k_canon_rows<CANON_P010>, g, dim3(256), 0, st, s, sp, d, dp, n);
+        launch_canon_rows(st, mode, s, sp, d, dp, rb, rows);
         HIPCHK(hipGetLastError());
     }
     return 0;
@@ -208,9 +202,9 @@ static int rife_hip_process_device_image_impl(const rife_hip_t* E, const rife_hi
     } else {
         if ((rc = ensure_ctx(*c, w, h, pixfmt, E->pad()))) return rc;
         const PlaneIO pio{plane_set(*in0), plane_set(*in1), plane_set(*out)};
-        rc = run_v4(*E, *c, nullptr, nullptr, timestep, c->d_out, nullptr, &pio);      // YUV: the pitched post-processing kernel writes the caller's planes; RGB formats: the tight frame c->d_out
+        rc = run_v4(*E, *c, nullptr, nullptr, timestep, c->d_out, nullptr, &pio);      // YUV and planar RGB: the pitched post-processing kernel writes the caller's planes; packed RGB formats: the tight frame c->d_out
         if (rc) return rc;
-        if (!pix_yuv(pixfmt)) {
+        if (!pix_conv(pixfmt)) {
             Timed t(E->prof, "store_rows", 0, c->stream);
             launch_store_rows(c->stream, c->d_out, rife_img::row_bytes(w, pixfmt, 0), h, static_cast<uint8_t*>(out->plane[0]), (size_t)out->pitch[0], rife_img::elem_size(pixfmt));
             HIPCHK(hipGetLastError());
@@ -318,7 +312,7 @@ int rife_hip_op_resident_to_image(int gpuid, const uint32_t* tight_frame, const 
     if (!tight_frame || force_scalar < 0 || force_scalar > 1) return fail(RIFE_HIP_EINVAL, "op_resident_to_image: a tight frame and force_scalar 0 or 1");
     if ((rc = check_device(gpuid))) return rc;
     const int w = img->w, h = img->h;
-    const bool yuv = pix_yuv(img->pixfmt);
+    const bool yuv = pix_conv(img->pixfmt);      // YUV and planar RGB: converted from an A2B10G10R10 frame
     const size_t nin = yuv ? (size_t)w * h * 4 : frame_bytes(w, h, img->pixfmt);
     ImageMirror m;
     void* d_i = nullptr;

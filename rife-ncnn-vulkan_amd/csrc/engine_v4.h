@@ -84,23 +84,35 @@ static inline int pix_bpp(int pixfmt) {
 // a pixfmt = format (bits 0-7) | colour description (bits 8-12, YUV formats only)
 static inline int pix_base(int pixfmt) { return pixfmt & 0xff; }
 static inline bool pix_yuv(int pixfmt) { return rife_img::is_yuv(pixfmt); }      // NV12 .. I420P10, I422, I422P10, I444, I444P10 (image_check.h)
+static inline bool pix_rgbp(int pixfmt) { return rife_img::is_rgbp(pixfmt); }    // RGBP8, RGBP10, RGBPH, RGBPF: three planes
+// the formats that are CONVERTED at the boundary: a pre-processing kernel makes 10:10:10 dwords of the caller's planes, the pass writes an internal A2B10G10R10
+// frame (Ctx::yuv_rgb) and a post-processing kernel makes the caller's planes of it (yuv.h, planar_rgb.h)
+static inline bool pix_conv(int pixfmt) { return pix_yuv(pixfmt) || pix_rgbp(pixfmt); }
 // size of a tightly packed w x h frame; 0 = unknown format.  YUV: a luma plane and two chroma planes of cw x ch samples - 4:2:0 (w + 1) / 2 x (h + 1) / 2,
-// 4:2:2 (w + 1) / 2 x h, 4:4:4 w x h
+// 4:2:2 (w + 1) / 2 x h, 4:4:4 w x h.  Planar RGB: three planes of w x h samples
 static inline size_t frame_bytes(int w, int h, int pixfmt) {
+    if (pix_rgbp(pixfmt)) return (size_t)3 * w * h * rgbp_elem(pix_base(pixfmt));
     if (!pix_yuv(pixfmt)) return (size_t)w * h * pix_bpp(pixfmt);
     const int cls = yuv_class(pix_base(pixfmt));
     const size_t cw = cls == 3 ? (size_t)w : (size_t)((w + 1) / 2), ch = cls == 1 ? (size_t)((h + 1) / 2) : (size_t)h;
     return ((size_t)w * h + 2 * cw * ch) * (yuv_depth(pix_base(pixfmt)) == 10 ? 2 : 1);
 }
 // the resident frames of this format are 10:10:10 dwords (the D = 10 instantiations of everything that reads a frame); RGB8 and RGBA8 frames are depth 8.
-// YUV frames of either depth are converted to 10-bit RGB on the way in (exactly invertible, include/rife_hip.h) and ride the depth-10 schedule.
-static inline bool pix_deep(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB10_U16 || pixfmt == RIFE_HIP_PIX_A2B10G10R10 || pix_yuv(pixfmt); }
-// the format the quantising kernels of a pass write: the caller's, or for YUV the internal A2B10G10R10 frame k_postproc_yuv / k_postproc_yuvc reads (Ctx::yuv_rgb)
-static inline int pix_inner(int pixfmt) { return pix_yuv(pixfmt) ? RIFE_HIP_PIX_A2B10G10R10 : pixfmt; }
+// YUV frames of either depth are converted to 10-bit RGB on the way in (exactly invertible, include/rife_hip.h) and ride the depth-10 schedule; so do planar RGB frames.
+static inline bool pix_deep(int pixfmt) { return pixfmt == RIFE_HIP_PIX_RGB10_U16 || pixfmt == RIFE_HIP_PIX_A2B10G10R10 || pix_conv(pixfmt); }
+// the format the quantising kernels of a pass write: the caller's, or for a converted format the internal A2B10G10R10 frame k_postproc_yuv / k_postproc_yuvc /
+// k_postproc_rgbp reads (Ctx::yuv_rgb)
+static inline int pix_inner(int pixfmt) { return pix_conv(pixfmt) ? RIFE_HIP_PIX_A2B10G10R10 : pixfmt; }
+// the post-processing kernel of a converted format on a tight frame
+static inline void launch_postproc_conv(hipStream_t st, const uint32_t* rgb, int w, int h, void* frame, int pixfmt) {
+    if (pix_rgbp(pixfmt)) launch_postproc_rgbp(st, rgb, w, h, rgbp_tight_planes(frame, w, h, pix_base(pixfmt)), pixfmt);
+    else launch_postproc_yuv(st, rgb, w, h, frame, pixfmt);
+}
+static inline const char* postproc_class(int pixfmt) { return pix_rgbp(pixfmt) ? "postproc_rgbp" : "postproc_yuv"; }      // the profiler's name of that launch
 // the workspace serves frames of `pixfmt` from here on: staging buffers of that size, c.pixfmt for every launch site that reads or writes a frame
 static int ensure_ctx(Ctx& c, int w, int h, int pixfmt = RIFE_HIP_PIX_RGB8, int pad = 32) {
     int rc = ensure_ctx_dims(c, w, h, (w + pad - 1) / pad * pad, (h + pad - 1) / pad * pad, nullptr, true, false, frame_bytes(w, h, pixfmt));   // pad to 32n, rife.cpp:2499-2500 (flow scale 2: 64n)
-    if (!rc && pix_yuv(pixfmt) && !c.yuv_rgb && (rc = dalloc(c, c.yuv_rgb, (size_t)c.wp * c.hp))) reset_ctx(c);      // only once a YUV format is served
+    if (!rc && pix_conv(pixfmt) && !c.yuv_rgb && (rc = dalloc(c, c.yuv_rgb, (size_t)c.wp * c.hp))) reset_ctx(c);      // only once a converted format (YUV, planar RGB) is served
     if (!rc) c.pixfmt = pixfmt;
     return rc;
 }
@@ -119,6 +131,7 @@ static inline dim3 tta_grid(int w, int h, int elem_bytes) { const dim3 b = tta_b
 // rife_preproc.comp: u8 HWC RGB -> zero-padded RGBX; four pixels per lane when the frame allows 4-byte loads
 static inline void launch_preproc(hipStream_t st, const uint8_t* rgb, int w, int h, uint32_t* out, int wp, int hp, int pixfmt = RIFE_HIP_PIX_RGB8) {
     if (pix_yuv(pixfmt)) { launch_preproc_yuv(st, rgb, w, h, out, wp, hp, pixfmt); return; }      // YUV planes -> 10:10:10 dwords (yuv.h)
+    if (pix_rgbp(pixfmt)) { launch_preproc_rgbp(st, rgbp_tight_planes(rgb, w, h, pix_base(pixfmt)), w, h, out, wp, hp, pixfmt); return; }      // R, G, B planes -> 10:10:10 dwords (planar_rgb.h)
     if (pixfmt == RIFE_HIP_PIX_RGB10_U16) {
         const uint16_t* p = reinterpret_cast<const uint16_t*>(rgb);
         if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 7) == 0) hipLaunchKernelGGL(k_preproc10_u16x4, dim3((wp / 4 + 255) / 256, hp), dim3(256), 0, st, p, w, h, out, wp, hp);
@@ -458,7 +471,7 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
     // 4:2:0: the quantising kernels write the internal A2B10G10R10 frame with the instantiations the packed 10-bit format uses; k_postproc_yuv follows below
     uint8_t* const caller_out = d_out;
     const int opf = pix_inner(c.pixfmt);
-    if (pix_yuv(c.pixfmt)) d_out = reinterpret_cast<uint8_t*>(c.yuv_rgb);
+    if (pix_conv(c.pixfmt)) d_out = reinterpret_cast<uint8_t*>(c.yuv_rgb);
     FinalArgs fin{c.img0, c.img1, c.F, c.M, d_out, c.w, c.h, c.wp, c.hp, opf};
     const float* pending = nullptr;                                      // flow whose update of F, M the next block's stem applies
     // The update after block 0 never reaches HBM on its own (round 5): block 1's scale-4 stem samples it from flow0 (assemble_pixel UPD = 2) and ONE pass after
@@ -510,10 +523,10 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         HIPCHK(hipGetLastError());
     }
-    if (pix_yuv(c.pixfmt)) {
-        Timed t(E.prof, "postproc_yuv", 0, st);
+    if (pix_conv(c.pixfmt)) {
+        Timed t(E.prof, postproc_class(c.pixfmt), 0, st);
         if (pio) launch_postproc_yuv_planes(st, c.yuv_rgb, c.w, c.h, pio->out, c.pixfmt);
-        else launch_postproc_yuv(st, c.yuv_rgb, c.w, c.h, caller_out, c.pixfmt);
+        else launch_postproc_conv(st, c.yuv_rgb, c.w, c.h, caller_out, c.pixfmt);
         HIPCHK(hipGetLastError());
     }
     return 0;
@@ -553,7 +566,7 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
         const bool batched = G >= 2 && block_on_row_kernel(E, *cs[0], b) && block_on_s16(E, *cs[0], b);
         for (int g = 0; g < G; g++) {
             Ctx& c = *cs[g];
-            FinalArgs fin{c.img0, c.img1, c.F, c.M, pix_yuv(c.pixfmt) ? reinterpret_cast<uint8_t*>(c.yuv_rgb) : d_out[g], c.w, c.h, c.wp, c.hp, pix_inner(c.pixfmt)};
+            FinalArgs fin{c.img0, c.img1, c.F, c.M, pix_conv(c.pixfmt) ? reinterpret_cast<uint8_t*>(c.yuv_rgb) : d_out[g], c.w, c.h, c.wp, c.hp, pix_inner(c.pixfmt)};
             if (!batched) {
                 if ((rc = run_block_convs(E, c, b, ts[g], (b == 3 && fuse_tail) ? &fin : nullptr, nullptr, PH_ALL, pend[g]))) return rc;
                 pend[g] = nullptr;
@@ -590,16 +603,16 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
         Ctx& c = *cs[g];
         if (!fuse_tail) {
             const int opf = pix_inner(c.pixfmt);
-            uint8_t* const o = pix_yuv(c.pixfmt) ? reinterpret_cast<uint8_t*>(c.yuv_rgb) : d_out[g];
+            uint8_t* const o = pix_conv(c.pixfmt) ? reinterpret_cast<uint8_t*>(c.yuv_rgb) : d_out[g];
             if (opf == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], o, c.w, c.h, c.wp, c.hp);
             else if (opf == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], o, c.w, c.h, c.wp, c.hp);
             else if (opf == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], o, c.w, c.h, c.wp, c.hp);
             else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, c.stream, c.img0, c.img1, c.F, c.M, c.flow[3], o, c.w, c.h, c.wp, c.hp);
             HIPCHK(hipGetLastError());
         }
-        if (pix_yuv(c.pixfmt)) {      // on the pair's own stream: the caller's join comes after it
-            Timed t(E.prof, "postproc_yuv", 0, c.stream);
-            launch_postproc_yuv(c.stream, c.yuv_rgb, c.w, c.h, d_out[g], c.pixfmt);
+        if (pix_conv(c.pixfmt)) {      // on the pair's own stream: the caller's join comes after it
+            Timed t(E.prof, postproc_class(c.pixfmt), 0, c.stream);
+            launch_postproc_conv(c.stream, c.yuv_rgb, c.w, c.h, d_out[g], c.pixfmt);
             HIPCHK(hipGetLastError());
         }
     }

@@ -18,9 +18,14 @@ static inline bool is_yuv(int pixfmt) {
     const int b = base(pixfmt);
     return (b >= RIFE_HIP_PIX_NV12 && b <= RIFE_HIP_PIX_I420P10) || b == RIFE_HIP_PIX_I422 || b == RIFE_HIP_PIX_I422P10 || b == RIFE_HIP_PIX_I444 || b == RIFE_HIP_PIX_I444P10;
 }
+// planar RGB is class 4 of that numbering: planes R, G, B of w x h samples each; k = 0 u8, 1 u16, 2 half, 3 float (the even, packed slots are unknown formats)
+static inline bool is_rgbp(int pixfmt) {
+    const int b = base(pixfmt);
+    return b == RIFE_HIP_PIX_RGBP8 || b == RIFE_HIP_PIX_RGBP10 || b == RIFE_HIP_PIX_RGBPH || b == RIFE_HIP_PIX_RGBPF;
+}
 static inline bool known(int pixfmt) {
     const int b = base(pixfmt);
-    return pixfmt >= 0 && (b == RIFE_HIP_PIX_RGB8 || b == RIFE_HIP_PIX_RGB10_U16 || b == RIFE_HIP_PIX_A2B10G10R10 || b == RIFE_HIP_PIX_RGBA8 || is_yuv(pixfmt));
+    return pixfmt >= 0 && (b == RIFE_HIP_PIX_RGB8 || b == RIFE_HIP_PIX_RGB10_U16 || b == RIFE_HIP_PIX_A2B10G10R10 || b == RIFE_HIP_PIX_RGBA8 || is_yuv(pixfmt) || is_rgbp(pixfmt));
 }
 // the rules of the _px calls for a pixfmt argument (format | colour description); nullptr = fine
 static inline const char* pixfmt_fault(int pixfmt) {
@@ -32,23 +37,25 @@ static inline const char* pixfmt_fault(int pixfmt) {
         return "full-range YUV is served at 8 bits only (the 10-bit full-range round trip through 10-bit RGB is not exact)";
     return nullptr;
 }
-// bytes of one sample group the kernels address as a unit: 1 for the u8 formats, 2 for the u16 formats, 4 for A2B10G10R10
+// bytes of one sample group the kernels address as a unit: 1 for the u8 formats, 2 for the u16 and half formats, 4 for A2B10G10R10 and float planes
 static inline int elem_size(int pixfmt) {
     const int b = base(pixfmt);
+    if (is_rgbp(pixfmt)) return b == RIFE_HIP_PIX_RGBP8 ? 1 : b == RIFE_HIP_PIX_RGBPF ? 4 : 2;
     return b == RIFE_HIP_PIX_A2B10G10R10 ? 4 : (b == RIFE_HIP_PIX_RGB10_U16 || (is_yuv(pixfmt) && (b & 2))) ? 2 : 1;
 }
 static inline int planes(int pixfmt) {
     const int b = base(pixfmt);
-    return !known(pixfmt) ? 0 : !is_yuv(pixfmt) ? 1 : (b == RIFE_HIP_PIX_NV12 || b == RIFE_HIP_PIX_P010) ? 2 : 3;
+    return !known(pixfmt) ? 0 : is_rgbp(pixfmt) ? 3 : !is_yuv(pixfmt) ? 1 : (b == RIFE_HIP_PIX_NV12 || b == RIFE_HIP_PIX_P010) ? 2 : 3;
 }
 // rows of plane p of a 4:2:0 frame h rows high: h for the first plane, ch = (h + 1) / 2 for chroma
 static inline int plane_rows(int h, int p) { return p == 0 ? h : (h + 1) / 2; }
-// the same for any format: the chroma planes of 4:2:2 and 4:4:4 have h rows
+// the same for any format: the chroma planes of 4:2:2 and 4:4:4 and the planes of planar RGB (class 4) have h rows
 static inline int plane_rows(int h, int pixfmt, int p) { return yuv_class(pixfmt) >= 2 ? h : plane_rows(h, p); }
 // bytes of one row of plane p, 0 for a plane the format does not have (or w <= 0, an unknown format)
 static inline size_t row_bytes(int w, int pixfmt, int p) {
     if (w <= 0 || p < 0 || p >= planes(pixfmt)) return 0;
     const int b = base(pixfmt);
+    if (is_rgbp(pixfmt)) return (size_t)w * (size_t)elem_size(pixfmt);
     if (!is_yuv(pixfmt)) return (size_t)w * (b == RIFE_HIP_PIX_RGB8 ? 3 : b == RIFE_HIP_PIX_RGB10_U16 ? 6 : 4);
     const size_t cw = yuv_class(pixfmt) == 3 ? (size_t)w : ((size_t)w + 1) / 2, es = (size_t)elem_size(pixfmt);
     return p == 0 ? (size_t)w * es : planes(pixfmt) == 2 ? 2 * cw * es : cw * es;

@@ -5,9 +5,10 @@
 //   k_preproc_pitch<PX, WIDE>            RGB8 / RGB10_U16 / A2B10G10R10 / RGBA8 plane -> resident dwords, zero (alpha: edge) padded
 //   k_preproc_yuv_pitch / _x8            Y, Cb, Cr (or Y, CbCr) planes -> resident 10:10:10 dwords
 //   k_postproc_yuv_pitch / _x8           the pass's tight A2B10G10R10 frame -> Y, Cb, Cr (or Y, CbCr) planes
-//   (4:2:2 / 4:4:4: yuv.h k_preproc_yuvc / k_postproc_yuvc take pitched planes to begin with; the launchers below pass the caller's planes to them)
+//   (4:2:2 / 4:4:4: yuv.h k_preproc_yuvc / k_postproc_yuvc take pitched planes to begin with; the launchers below pass the caller's planes to them.  Planar RGB:
+//   planar_rgb.h k_preproc_rgbp / k_postproc_rgbp, likewise)
 //   k_store_rows<T>                      the pass's tight RGB-format frame (Ctx::d_out) -> the caller's strided plane, row_bytes of each row and nothing else
-//   k_canon_rows<MODE>                   timestep 0 / 1 at depth 10: strided plane -> strided plane in canonical form
+//   k_canon_rows<MODE>                   timestep 0 / 1 at depth 10 and for half / float planes: strided plane -> strided plane in canonical form
 // Wide forms (four pixels / a run of eight samples per lane): every plane pointer AND every pitch the kernel touches is aligned to the access width, and
 // w % 4 / w % 8 holds as for the tight kernels; otherwise the scalar form runs.  The host picks (planes_*_wide below), as yuv_x8_ok does for tight frames.
 #pragma once
@@ -15,8 +16,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cstring>
+
 #include "elementwise.h"
 #include "yuv.h"
+#include "planar_rgb.h"
 
 namespace rife {
 
@@ -222,10 +226,15 @@ __global__ void k_store_rows(const uint8_t* __restrict__ src, size_t row_bytes, 
 enum CanonMode { CANON_BYTES = 0,      // the 8-bit formats: bytes unchanged (2-D copies, no kernel)
                  CANON_U16_CLAMP,      // RGB10_U16, I420P10, I422P10, I444P10: u16 clamped to 1023
                  CANON_PACKED_ALPHA,   // A2B10G10R10: dword | alpha bits 3
-                 CANON_P010 };         // P010: low six bits cleared
+                 CANON_P010,           // P010: low six bits cleared
+                 CANON_HALF,           // RGBPH: the half sample of its code, from10(to10(v)) (planar_rgb.h)
+                 CANON_FLOAT };        // RGBPF: the float sample of its code
+static inline size_t canon_elem(CanonMode mode) { return (mode == CANON_PACKED_ALPHA || mode == CANON_FLOAT) ? 4 : 2; }      // bytes of the unit a mode works on (CANON_BYTES: none)
 static inline CanonMode canon_mode(int pixfmt) {
     const int b = pixfmt & 0xff;
-    return (b == RIFE_HIP_PIX_RGB10_U16 || b == RIFE_HIP_PIX_I420P10 || b == RIFE_HIP_PIX_I422P10 || b == RIFE_HIP_PIX_I444P10) ? CANON_U16_CLAMP : b == RIFE_HIP_PIX_A2B10G10R10 ? CANON_PACKED_ALPHA : b == RIFE_HIP_PIX_P010 ? CANON_P010 : CANON_BYTES;
+    if (b == RIFE_HIP_PIX_RGBPH) return CANON_HALF;
+    if (b == RIFE_HIP_PIX_RGBPF) return CANON_FLOAT;
+    return (b == RIFE_HIP_PIX_RGBP10 || b == RIFE_HIP_PIX_RGB10_U16 || b == RIFE_HIP_PIX_I420P10 || b == RIFE_HIP_PIX_I422P10 || b == RIFE_HIP_PIX_I444P10) ? CANON_U16_CLAMP : b == RIFE_HIP_PIX_A2B10G10R10 ? CANON_PACKED_ALPHA : b == RIFE_HIP_PIX_P010 ? CANON_P010 : CANON_BYTES;
 }
 // strided in and out, one element per lane; n = elements per row; grid ((n + 255) / 256, rows).  MODE != CANON_BYTES
 template <CanonMode MODE>
@@ -234,15 +243,39 @@ __global__ void k_canon_rows(const uint8_t* __restrict__ src, size_t spitch, uin
     const size_t y = blockIdx.y;
     if (i >= n) return;
     if (MODE == CANON_PACKED_ALPHA) reinterpret_cast<uint32_t*>(dst + y * dpitch)[i] = reinterpret_cast<const uint32_t*>(src + y * spitch)[i] | 0xc0000000u;
+    else if (MODE == CANON_FLOAT) reinterpret_cast<float*>(dst + y * dpitch)[i] = rgbp_canon<float>(reinterpret_cast<const float*>(src + y * spitch)[i]);
+    else if (MODE == CANON_HALF) reinterpret_cast<_Float16*>(dst + y * dpitch)[i] = rgbp_canon<_Float16>(reinterpret_cast<const _Float16*>(src + y * spitch)[i]);
     else {
         const uint32_t v = reinterpret_cast<const uint16_t*>(src + y * spitch)[i];
         reinterpret_cast<uint16_t*>(dst + y * dpitch)[i] = (uint16_t)(MODE == CANON_P010 ? (v & 0xffc0u) : min(v, 1023u));
     }
 }
+// the same on the host: one row of rb bytes (src == dst is fine: element by element)
+static inline void canon_row_host(CanonMode mode, const uint8_t* s, uint8_t* d, size_t rb) {
+    if (mode == CANON_BYTES) std::memmove(d, s, rb);
+    else if (mode == CANON_PACKED_ALPHA) { const uint32_t* a = reinterpret_cast<const uint32_t*>(s); uint32_t* b = reinterpret_cast<uint32_t*>(d); for (size_t i = 0; i < rb / 4; i++) b[i] = a[i] | 0xc0000000u; }
+    else if (mode == CANON_FLOAT) { const float* a = reinterpret_cast<const float*>(s); float* b = reinterpret_cast<float*>(d); for (size_t i = 0; i < rb / 4; i++) b[i] = rgbp_canon<float>(a[i]); }
+    else if (mode == CANON_HALF) { const _Float16* a = reinterpret_cast<const _Float16*>(s); _Float16* b = reinterpret_cast<_Float16*>(d); for (size_t i = 0; i < rb / 2; i++) b[i] = rgbp_canon<_Float16>(a[i]); }
+    else { const uint16_t* a = reinterpret_cast<const uint16_t*>(s); uint16_t* b = reinterpret_cast<uint16_t*>(d); for (size_t i = 0; i < rb / 2; i++) b[i] = mode == CANON_P010 ? (uint16_t)(a[i] & 0xffc0u) : (uint16_t)(a[i] < 1023 ? a[i] : 1023); }
+}
+template <CanonMode MODE>
+static inline void launch_canon_rows_m(hipStream_t st, const uint8_t* s, size_t sp, uint8_t* d, size_t dp, int n, int rows) {
+    hipLaunchKernelGGL(k_canon_rows<MODE>, dim3((n + 255) / 256, rows), dim3(256), 0, st, s, sp, d, dp, n);
+}
+// rows x rb bytes, strided both ways; mode != CANON_BYTES
+static inline void launch_canon_rows(hipStream_t st, CanonMode mode, const uint8_t* s, size_t sp, uint8_t* d, size_t dp, size_t rb, int rows) {
+    const int n = (int)(rb / canon_elem(mode));
+    if (mode == CANON_U16_CLAMP) launch_canon_rows_m<CANON_U16_CLAMP>(st, s, sp, d, dp, n, rows);
+    else if (mode == CANON_PACKED_ALPHA) launch_canon_rows_m<CANON_PACKED_ALPHA>(st, s, sp, d, dp, n, rows);
+    else if (mode == CANON_P010) launch_canon_rows_m<CANON_P010>(st, s, sp, d, dp, n, rows);
+    else if (mode == CANON_HALF) launch_canon_rows_m<CANON_HALF>(st, s, sp, d, dp, n, rows);
+    else launch_canon_rows_m<CANON_FLOAT>(st, s, sp, d, dp, n, rows);
+}
 
 // ---- host side.  force_scalar: the single-kernel tests run both forms on one frame ----
 static inline void launch_preproc_planes(hipStream_t st, const PlaneSet& s, int w, int h, uint32_t* out, int wp, int hp, int pixfmt, bool force_scalar = false) {
     const int fmt = pixfmt & 0xff;
+    if (rgbp_fmt(fmt)) { launch_preproc_rgbp(st, s, w, h, out, wp, hp, pixfmt, force_scalar); return; }      // planar RGB: planar_rgb.h, one kernel set for tight and pitched planes
     if (fmt >= RIFE_HIP_PIX_I422) { launch_preproc_yuvc(st, s, w, h, out, wp, hp, pixfmt, force_scalar); return; }      // 4:2:2 / 4:4:4: yuv.h, one kernel set for tight and pitched planes
     if (fmt >= RIFE_HIP_PIX_NV12) {
         const YuvCsp k = yuv_csp(pixfmt & ~0xff, yuv_depth(fmt));
@@ -262,8 +295,10 @@ static inline void launch_preproc_planes(hipStream_t st, const PlaneSet& s, int 
     else if (fmt == RIFE_HIP_PIX_RGBA8) RIFE_PL_RGB(RIFE_HIP_PIX_RGBA8); else RIFE_PL_RGB(RIFE_HIP_PIX_RGB8);
 #undef RIFE_PL_RGB
 }
+// (YUV and planar RGB: every format whose output is converted from the pass's A2B10G10R10 frame)
 static inline void launch_postproc_yuv_planes(hipStream_t st, const uint32_t* rgb, int w, int h, const PlaneSet& d, int pixfmt, bool force_scalar = false) {
     const int fmt = pixfmt & 0xff;
+    if (rgbp_fmt(fmt)) { launch_postproc_rgbp(st, rgb, w, h, d, pixfmt, force_scalar); return; }
     if (fmt >= RIFE_HIP_PIX_I422) { launch_postproc_yuvc(st, rgb, w, h, d, pixfmt, force_scalar); return; }
     const YuvCsp k = yuv_csp(pixfmt & ~0xff, yuv_depth(fmt));
     const bool x8 = !force_scalar && planes_yuv_x8(d, w, fmt);

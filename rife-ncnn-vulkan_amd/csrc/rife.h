@@ -42,11 +42,13 @@ public:
     // Extension, not in the reference (include/rife_hip.h "video"): planar Y'CbCr frames (4:2:0, 4:2:2, 4:4:4).  An ncnn::Mat has no natural shape for them, so these take plain pointers
     // to tightly packed frames of `pixfmt` (RIFE_HIP_PIX_NV12 .. I420P10, I422, I422P10, I444, I444P10 | RIFE_HIP_CSP_*), rife_hip_frame_bytes(w, h, pixfmt) bytes each.  rife-v4.6, plain mode.
     // A frame of upload_yuv() goes through process(frame0, frame1, timestep, outimage) above, whose outimage.data then points at a frame of that size.
+    // Both forward `pixfmt` unfiltered, so they serve every planar format of the _px calls: the planar RGB formats too (include/rife_hip.h "planar RGB":
+    // RIFE_HIP_PIX_RGBP8 / RGBP10 / RGBPH / RGBPF, three planes R, G, B glued one after the other, no colour bits).
     int process_yuv(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt) const;
     rife_hip_frame* upload_yuv(const void* frame, int w, int h, int pixfmt) const;
 
     // Extension, not in the reference (include/rife_hip.h "strides and planes"): frames as an AVFrame or a VapourSynth frame holds them - a pointer and a
-    // pitch in BYTES per plane, any of the _px formats.  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
+    // pitch in BYTES per plane, any of the _px formats (planar RGB: R, G, B in plane[0..2]; ffmpeg's gbrp: permute them).  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
     // program that never calls them links against an engine without those two symbols as before; the message of a failure is rife_hip_last_error()).
     int process_image(const rife_hip_image_t& in0, const rife_hip_image_t& in1, float timestep, const rife_hip_image_t& out) const
     {
