@@ -269,6 +269,29 @@ int rife_hip_process_frames_image(const rife_hip_t* r, const rife_hip_frame_t* f
 int rife_hip_set_flow_scale(rife_hip_t* r, int divisor);
 int rife_hip_flow_scale(const rife_hip_t* r);               /* the divisor in force (1 before load and for a null engine) */
 
+/* ---- precision: one f16 product per weight tap in the residual trunks (the reference's Vulkan path runs fp16 storage and arithmetic; this engine's default is
+ * fp32-equivalent) ----
+ * The residual trunk layers x <- leaky(conv3x3(x) + b + x) run on tensors stored as a pair {hi = f16(x), lo = f16(x - hi)}.  RIFE_HIP_PRECISION_FULL (the default)
+ * multiplies every weight with hi and with lo: two matrix instructions per tap, an fp32-equivalent result.  RIFE_HIP_PRECISION_FAST computes
+ *     acc = sum over the 3 x 3 taps of W . hi(x)  +  I . (hi(x) + lo(x))        (fp32 accumulation)
+ * i.e. the convolution sees its input rounded to f16 (round to nearest even), while the skip connection adds the unrounded input, so the residual stream stays
+ * fp32-equivalent from layer to layer; then the unchanged epilogue: bias, LeakyReLU, and the split of the fp32 result into {hi, lo}, both stored as in full
+ * precision.  Tensor layout, zero borders and kernel selection are those of full precision: the same kernel serves a layer in both modes.
+ * Reach: all eight trunk layers of every IFBlock that runs on these tensors at the given frame size - at the usual sizes all four blocks.  A block that leaves that
+ * path runs at full precision, unchanged: block 0 where its row-kernel grid exceeds 5/8 of a workgroup per compute unit (about 160 workgroups on an MI355X: 4K
+ * frames), any trunk tensor of 4 GB and more, and (test build) RIFE_HIP_T64=0.  Stems, heads and everything outside the trunks are full precision always.
+ * Within a mode the bytes are identical across entry points (host, device, stream mode, batch calls and their lockstep groups, CU-masked streams, every _px format
+ * and image call, flow scale 2) and from run to run.  Accuracy of FAST against the reference's network is measured, not bounded by contract: see README
+ * ("Precision"); FULL keeps its bound of one code per channel.
+ * rife_hip_set_precision returns 0 or, leaving the engine unchanged, with a last-error message:
+ *   -RIFE_HIP_EINVAL  before rife_hip_load (the family is not known yet); a value that is neither constant; while a call on the engine is in flight;
+ *   -RIFE_HIP_ENOSYS  FAST on any family other than rife-v4.6 or on an engine created with tta_mode / tta_temporal_mode (the message names the family or mode).
+ * FULL always succeeds after load.  Call it while no call on the engine is in flight: it drops the engine's workspaces and any captured graph.  It composes with
+ * rife_hip_set_flow_scale in either order. */
+enum { RIFE_HIP_PRECISION_FULL = 0, RIFE_HIP_PRECISION_FAST = 1 };
+int rife_hip_set_precision(rife_hip_t* r, int precision);
+int rife_hip_precision(const rife_hip_t* r);                /* FULL before load and for a null engine */
+
 const char* rife_hip_last_error(void);
 
 /* ---- measurement hooks (bench.py / profiles) ---------------------------------------------------------------

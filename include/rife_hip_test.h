@@ -88,6 +88,11 @@ int rife_hip_op_s16_geom(int C, int H, int W, int* pitch, int* rows, unsigned* p
 enum { RIFE_HIP_TRUNK_T64 = 0, RIFE_HIP_TRUNK_RS = 1, RIFE_HIP_TRUNK_RS2 = 2, RIFE_HIP_TRUNK_ROW = 3, RIFE_HIP_TRUNK_KS = 4 };
 int rife_hip_op_trunk(int gpuid, int kernel, int C, int H, int W, int n_layers, const float* weight, const float* bias, const float* slope, int flip, int cus,
                       int nb, const void* const* in_s16, void* const* out_s16);
+/* the same with the launchers' precision (include/rife_hip.h RIFE_HIP_PRECISION_*): FULL is rife_hip_op_trunk byte for byte, FAST launches the fast-precision
+ * instantiation of the same kernel on the same grid - acc = sum over the weight taps of W . hi(x) + I . (hi(x) + lo(x)), the epilogue unchanged.  conv_ks has no
+ * fast form (-RIFE_HIP_ENOSYS); an unknown precision is -RIFE_HIP_EINVAL. */
+int rife_hip_op_trunk_prec(int gpuid, int kernel, int C, int H, int W, int n_layers, const float* weight, const float* bias, const float* slope, int flip, int cus,
+                           int nb, const void* const* in_s16, void* const* out_s16, int precision);
 
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */

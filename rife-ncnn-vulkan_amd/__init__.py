@@ -34,7 +34,11 @@ C_ABI_SYMBOLS = [
     "rife_hip_frame_bytes", "rife_hip_process_px", "rife_hip_process_device_px", "rife_hip_process_device_batch_px", "rife_hip_frame_upload_px",
     "rife_hip_image_check", "rife_hip_image_row_bytes", "rife_hip_process_image", "rife_hip_process_device_image", "rife_hip_frame_upload_image", "rife_hip_process_frames_image",
     "rife_hip_set_flow_scale", "rife_hip_flow_scale",
+    "rife_hip_set_precision", "rife_hip_precision",
 ]
+# include/rife_hip.h RIFE_HIP_PRECISION_*: FULL = two f16 products per weight tap of the residual trunks (fp32-equivalent), FAST = one, the skip at full precision
+PRECISION_FULL, PRECISION_FAST = 0, 1
+_PRECISION_NAMES = {"full": PRECISION_FULL, "fast": PRECISION_FAST}
 # pixel formats at the C boundary (include/rife_hip.h RIFE_HIP_PIX_*)
 PIX_RGB8, PIX_RGB10_U16, PIX_A2B10G10R10 = 0, 1, 2
 PIX_RGBA8 = 4      # 3 is reserved
@@ -52,7 +56,8 @@ ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
-                    "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px"]
+                    "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
+                    "rife_hip_op_trunk_prec"]
 # rife_hip_op_trunk: which S16 trunk kernel (include/rife_hip_test.h RIFE_HIP_TRUNK_*)
 TRUNK_T64, TRUNK_RS, TRUNK_RS2, TRUNK_ROW, TRUNK_KS = 0, 1, 2, 3, 4
 EINVAL = 1      # RIFE_HIP_EINVAL: calls return its negative
@@ -124,6 +129,8 @@ def _load(path, with_test_surface):
     L.rife_hip_process_frames_image.argtypes = [vp, vp, vp, cf, ip]
     L.rife_hip_set_flow_scale.argtypes = [vp, ci]
     L.rife_hip_flow_scale.argtypes = [vp]
+    L.rife_hip_set_precision.argtypes = [vp, ci]
+    L.rife_hip_precision.argtypes = [vp]
     if with_test_surface:
         L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
         L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
@@ -142,6 +149,7 @@ def _load(path, with_test_surface):
         L.rife_hip_op_rgb10_to_yuv.argtypes = [ci, vp, ci, ci, ci, vp]
         L.rife_hip_op_s16_geom.argtypes = [ci, ci, ci, vp, vp, vp, vp]
         L.rife_hip_op_trunk.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp]
+        L.rife_hip_op_trunk_prec.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, ci]
     return L
 
 
@@ -456,6 +464,27 @@ class RIFE:
     def flow_scale(self):
         """The flow scale divisor in force."""
         return int(self._L.rife_hip_flow_scale(self._h))
+
+    def set_precision(self, precision):
+        """"full" / PRECISION_FULL (the default: fp32-equivalent residual trunks) or "fast" / PRECISION_FAST (include/rife_hip.h: one f16 product per weight tap of
+        the trunk convolutions, the skip connection at full precision; rife-v4.6, plain mode).  Call after load() and while no call on the engine is in flight.
+        Anything else is a ValueError; a refusal of the engine raises RifeError with the C code (-1 before load, -6 another family or -x / -z) and leaves the
+        engine unchanged."""
+        if isinstance(precision, str):
+            if precision not in _PRECISION_NAMES:
+                raise ValueError("precision must be 'full' or 'fast' (or PRECISION_FULL / PRECISION_FAST), not %r" % (precision,))
+            value = _PRECISION_NAMES[precision]
+        elif isinstance(precision, (bool, float)) or not isinstance(precision, (int, np.integer)) or int(precision) not in (PRECISION_FULL, PRECISION_FAST):
+            raise ValueError("precision must be 'full' or 'fast' (or PRECISION_FULL / PRECISION_FAST), not %r" % (precision,))
+        else:
+            value = int(precision)
+        _check(self._L.rife_hip_set_precision(self._h, value), "set_precision", self._L)
+        return 0
+
+    @property
+    def precision(self):
+        """The precision in force: PRECISION_FULL or PRECISION_FAST."""
+        return int(self._L.rife_hip_precision(self._h))
 
     def process(self, in0image, in1image, timestep, outimage=None, pixfmt=None):
         """in0image / in1image: (h, w, 3) uint8 RGB arrays (the ncnn::Mat the CLI builds, src/main.cpp:187).
@@ -801,10 +830,12 @@ def op_s16_geom(C, H, W):
     return pitch.value, rows.value, plane.value, nbytes.value
 
 
-def op_trunk(kernel, C, H, W, weight, bias, slope, in_s16, out_s16, flip=0, cus=0, gpuid=0):
+def op_trunk(kernel, C, H, W, weight, bias, slope, in_s16, out_s16, flip=0, cus=0, gpuid=0, fast=False):
     """One (weight (C, C, 3, 3)) or two (weight (2, C, C, 3, 3)) residual trunk layers through ONE S16 kernel's own launcher (kernel = TRUNK_T64 .. TRUNK_KS) on
     raw S16 tensors: uint8 arrays of op_s16_geom(C, H, W)[3] bytes, or lists of up to four of them (the batched form of TRUNK_ROW / TRUNK_KS).  out_s16 goes to the
-    device as given (what the kernel does not write comes back unchanged); returns the final tensor(s) as new arrays.  slope: one value per layer."""
+    device as given (what the kernel does not write comes back unchanged); returns the final tensor(s) as new arrays.  slope: one value per layer.
+    fast: the launch goes through rife_hip_op_trunk_prec with PRECISION_FAST (the fast-precision instantiation of the kernel) or PRECISION_FULL (the bytes of
+    rife_hip_op_trunk, which forwards to it)."""
     weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32)
     n = 1 if weight.ndim == 4 else weight.shape[0]
     if weight.size != n * C * C * 9 or bias.size != n * C:
@@ -822,7 +853,8 @@ def op_trunk(kernel, C, H, W, weight, bias, slope, in_s16, out_s16, flip=0, cus=
         raise ValueError("an S16 tensor of this geometry has %d bytes" % nbytes)
     pi = (ctypes.c_void_p * len(ins))(*[a.ctypes.data for a in ins])
     po = (ctypes.c_void_p * len(outs))(*[a.ctypes.data for a in outs])
-    _check(testlib().rife_hip_op_trunk(gpuid, int(kernel), int(C), int(H), int(W), n, _p(weight), _p(bias), _p(sl), int(flip), int(cus), len(ins), pi, po), "op_trunk", testlib())
+    _check(testlib().rife_hip_op_trunk_prec(gpuid, int(kernel), int(C), int(H), int(W), n, _p(weight), _p(bias), _p(sl), int(flip), int(cus), len(ins), pi, po,
+                                            PRECISION_FAST if fast else PRECISION_FULL), "op_trunk", testlib())
     return outs[0] if single else outs
 
 

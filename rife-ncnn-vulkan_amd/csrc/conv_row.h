@@ -65,6 +65,7 @@ __global__ __launch_bounds__(2 * C) __attribute__((amdgpu_waves_per_eu(convrow_w
     constexpr int PSLOTS = PH * 4 * NPX, NLD = (PSLOTS + NTHR - 1) / NTHR;      // 16-byte slots per phase, loads per thread and phase
     constexpr int WSTRIDE = t64_img_nt(1, NCH);                          // bytes per output block of the weight image
     static_assert(NCH % PH == 0, "whole load phases");
+    constexpr bool FAST = (TAG & S16_FAST) != 0;                         // conv_t64.h: hi products only in the weight taps, hi and lo in the skip's identity tap
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     unsigned char* const lds = ldsb;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -129,7 +130,8 @@ __global__ __launch_bounds__(2 * C) __attribute__((amdgpu_waves_per_eu(convrow_w
 
     // weight fragments: a ring of RING (chunk, tap) slots, every slot refilled right after its use, i.e. always RING taps (two K chunks)
     // ahead of the matrix pipe: an L2 round trip is longer than the 18 MFMAs of one chunk
-    constexpr int RING = (C == 128 && !(TAG & 16)) || C < 128 ? 10 : 18, NJ = NCH * 9;       // block 1: 10 slots keep the kernel inside 168 VGPRs
+    // (fast precision, 192 channels: 16 slots - with 18 the register allocator spills five VGPRs of the 168)
+    constexpr int RING = (C == 128 && !(TAG & 16)) || C < 128 ? 10 : FAST ? 16 : 18, NJ = NCH * 9;       // block 1: 10 slots keep the kernel inside 168 VGPRs
     f16x8 wr[RING];
 #define ROW_WSLOT(J) wr[(J) % RING] = *reinterpret_cast<const f16x8*>(wsrc + (J) * 1024);
 #define ROW_TAP(J)                                                                                           \
@@ -138,9 +140,10 @@ __global__ __launch_bounds__(2 * C) __attribute__((amdgpu_waves_per_eu(convrow_w
         const unsigned char* const cb_ = lds + (((c_ / PH) & 1) * PH + c_ % PH) * CHB;                       \
         _Pragma("unroll") for (int rr = 0; rr < ROWS; rr++) {                                                \
             const f16x8 ah = *reinterpret_cast<const f16x8*>(cb_ + ao[rr][t_]);                              \
-            const f16x8 al = *reinterpret_cast<const f16x8*>(cb_ + ao[rr][t_] + PLANE);                      \
+            f16x8 al = ah;                                                   /* fast precision: no lo fragment is read for a weight tap */ \
+            if constexpr (!FAST) al = *reinterpret_cast<const f16x8*>(cb_ + ao[rr][t_] + PLANE);             \
             acc[rr] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[(J) % RING], ah, acc[rr], 0, 0, 0);          \
-            acc[rr] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[(J) % RING], al, acc[rr], 0, 0, 0);          \
+            if constexpr (!FAST) acc[rr] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[(J) % RING], al, acc[rr], 0, 0, 0); \
         }                                                                                                    \
         if ((J) + RING < NJ) ROW_WSLOT((J) + RING)                                                           \
         if (t_ == 8 && (c_ >> 1) == w) {      /* K chunk c_ carries the input channels of output block c_ >> 1: the skip connection */ \

@@ -112,6 +112,7 @@ constexpr int RS_NPAIR = 38, RS_PF = 3;      // pairs per row; fragment prefetch
 template <int N, int TAG>
 __device__ __forceinline__ void rs_consumer(const RsArgs& a, unsigned char* const ldsb, const int ro, const int lane, const int S, const int ufirst) {
     const int h = lane >> 5, li = lane & 31;
+    constexpr bool FAST = (TAG & S16_FAST) != 0;                         // conv_t64.h: the lo chain carries the skip's identity products only; no lo fragment is read for a weight tap
     // weights of output block N: [chunk][tap] A fragments, lane (li, h) = row li, k half h (conv_t64's image: [chunk][tap][k half][64 rows][8 f16])
     f16x8 W[4][9];
     {
@@ -168,7 +169,7 @@ __device__ __forceinline__ void rs_consumer(const RsArgs& a, unsigned char* cons
             constexpr RsPairDesc d = rs_pair(N, m % RS_NPAIR);
             constexpr int st = (m + 2 * PAR) % NF;
             fh[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG));
-            fl[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
+            if constexpr (!FAST || d.idn) fl[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
         };
         f32x16 accH, accL;
         if (!RIFE_ABL(TAG & RS_NOMATH)) {
@@ -179,6 +180,20 @@ __device__ __forceinline__ void rs_consumer(const RsArgs& a, unsigned char* cons
                 if constexpr (m == RS_NPAIR - RS_PF) step_addresses(cur.advance(a.npairs, a.descend));     // ad[] is dead: every read of this step is issued
                 frag_read(std::integral_constant<int, m + RS_PF>{});     // m + RS_PF >= 38: pair m + RS_PF - 38 of the next step (sets continue to rotate)
                 const f16x8 A = d.idn ? idf[d.c & 1] : W[d.c][d.t];
+                if constexpr (FAST) {                                    // the identity taps are those of chunks 2 N (the first: it opens the lo chain) and 2 N + 1
+                    if constexpr (m == 0) {
+                        f32x16 z;
+#pragma unroll
+                        for (int q = 0; q < 16; q++) z[q] = 0.f;
+                        accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], z, 0, 0, 0);
+                    } else accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], accH, 0, 0, 0);
+                    if constexpr (d.idn && (d.c & 1) == 0) {
+                        f32x16 z;
+#pragma unroll
+                        for (int q = 0; q < 16; q++) z[q] = 0.f;
+                        accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], z, 0, 0, 0);
+                    } else if constexpr (d.idn) accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], accL, 0, 0, 0);
+                } else
                 if constexpr (m == 0) {
                     f32x16 z;
 #pragma unroll
@@ -215,7 +230,7 @@ __device__ __forceinline__ void rs_consumer(const RsArgs& a, unsigned char* cons
         constexpr int m = decltype(mc)::value;
         constexpr RsPairDesc d = rs_pair(N, m);
         fh[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG));
-        fl[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
+        if constexpr (!FAST || d.idn) fl[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
     });
     while (it + 1 < S) { step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); }
     if (it < S) step(std::integral_constant<int, 0>{});

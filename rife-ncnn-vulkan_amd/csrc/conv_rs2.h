@@ -100,6 +100,7 @@ template <int N, int NR, int TAG>
 __device__ __forceinline__ void rs2_consumer(const Rs2Args& a, const unsigned char* const img, unsigned char* const ldsb, const unsigned ring, const unsigned stgbase,
                                              const int lead, const int extra, const int lag, const int lane) {
     const int h = lane >> 5, li = lane & 31;
+    constexpr bool FAST = (TAG & S16_FAST) != 0;                         // conv_t64.h; both layers of the launch, the code of rs_consumer's fast form
     f16x8 W[4][9];                                                       // rs_consumer's register-resident weights
     {
         const unsigned char* wsrc = img + h * 1024 + (N * 32 + li) * 16;
@@ -147,6 +148,7 @@ __device__ __forceinline__ void rs2_consumer(const Rs2Args& a, const unsigned ch
             constexpr int st = (m + 2 * PAR) % NF;
             if RIFE_ABL(TAG & RS2_NOFRAG) { asm volatile("" : "+v"(fh[st]), "+v"(fl[st])); return; }
             fh[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG));
+            if constexpr (FAST && !d.idn) return;
             if (!RIFE_ABL(TAG & RS2_NOLO)) fl[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
         };
         f32x16 accH, accL;
@@ -158,6 +160,20 @@ __device__ __forceinline__ void rs2_consumer(const Rs2Args& a, const unsigned ch
                 if constexpr (m == RS_NPAIR - RS_PF) { RS2_NEXT(sq, NR) step_addresses(); }      // ad[] is dead: every read of this step is issued
                 frag_read(std::integral_constant<int, m + RS_PF>{});
                 const f16x8 A = d.idn ? idf[d.c & 1] : W[d.c][d.t];
+                if constexpr (FAST) {                                    // conv_rs.h: the lo chain starts at the identity tap of chunk 2 N
+                    if constexpr (m == 0) {
+                        f32x16 z;
+#pragma unroll
+                        for (int q = 0; q < 16; q++) z[q] = 0.f;
+                        accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], z, 0, 0, 0);
+                    } else accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], accH, 0, 0, 0);
+                    if constexpr (d.idn && (d.c & 1) == 0) {
+                        f32x16 z;
+#pragma unroll
+                        for (int q = 0; q < 16; q++) z[q] = 0.f;
+                        accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], z, 0, 0, 0);
+                    } else if constexpr (d.idn) accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], accL, 0, 0, 0);
+                } else
                 if constexpr (m == 0) {
                     f32x16 z;
 #pragma unroll
@@ -196,7 +212,7 @@ __device__ __forceinline__ void rs2_consumer(const Rs2Args& a, const unsigned ch
             constexpr int m = decltype(mc)::value;
             constexpr RsPairDesc d = rs_pair(N, m);
             fh[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG));
-            fl[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
+            if constexpr (!FAST || d.idn) fl[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
         });
         int k = 0;
         for (; k + 1 < S; k += 2) { step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); }

@@ -89,6 +89,13 @@ struct T64Args {
 // bench-only ablation bits of TAG (timing experiments; the results of all but T64_STAMPS are garbage).  The product instantiates TAG = 3.
 enum { T64_NOSTORE = 0x100, T64_NODMA = 0x200, T64_NOMATH = 0x400, T64_NOVMWAIT = 0x800, T64_STAMPS = 0x1000, T64_CLK = 0x40000 };
 
+// PRODUCT bit of TAG, shared by the four S16 trunk families (conv_t64 / conv_rs / conv_rs2 / conv_row): fast precision (include/rife_hip.h
+// rife_hip_set_precision).  acc = sum over the weight taps of W . hi(x)  +  I . (hi(x) + lo(x)): the lo fragment of the {hi, lo} pair is left out of the
+// WEIGHT taps - one matrix instruction per tap instead of two - and kept in the identity tap of the skip connection, so the residual stream stays
+// fp32-equivalent from layer to layer.  Loads, LDS images, walking order and the epilogue (bias, LeakyReLU, {hi, lo} split) are the plain kernel's.
+// Unlike the ablation bits it is not wrapped in RIFE_ABL: it is part of the product.
+enum { S16_FAST = 0x100000 };
+
 typedef __attribute__((address_space(3))) unsigned char t64_lds_u8;
 typedef __attribute__((address_space(1))) const unsigned char t64_glb_u8;
 // 64 lanes x 16 bytes, global -> LDS without passing through registers; LDS destination = wave-uniform base + lane * 16
@@ -103,6 +110,7 @@ __device__ __forceinline__ void t64_glds16(const unsigned char* g, unsigned char
 template <int TAG, int NS = 2, int LW = 0>
 __global__ __launch_bounds__(T64_NTHR + 64 * LW) __attribute__((amdgpu_waves_per_eu(2 * t64_wg_per_cu(NS), 2 * t64_wg_per_cu(NS) + (LW ? 1 : 0)))) void conv_t64_kernel(T64Args a) {
     constexpr int T64_WCH = t64_wch(NS), T64_BSB = t64_bsb(NS), T64_LDS_BS = t64_lds_bs(NS), T64_LDS = t64_lds(NS), CH = 32 * NS;
+    constexpr bool FAST = (TAG & S16_FAST) != 0;                         // one product per weight tap (hi only); the skip's identity tap keeps hi and lo
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     unsigned char* const lds = ldsb;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -244,11 +252,12 @@ __global__ __launch_bounds__(T64_NTHR + 64 * LW) __attribute__((amdgpu_waves_per
     if (!RIFE_ABL(TAG & T64_NOMATH)) {                                                                               \
         _Pragma("unroll") for (int t = 0; t < 9; t++) {                                                      \
             const f16x8 ah = *reinterpret_cast<const f16x8*>(ap[t] + (PAR) * T64_INB);                       \
-            const f16x8 al = *reinterpret_cast<const f16x8*>(ap[t] + (PAR) * T64_INB + T64_PLANE);           \
+            f16x8 al = ah;                                                   /* fast precision: no lo fragment is read for a weight tap */ \
+            if constexpr (!FAST) al = *reinterpret_cast<const f16x8*>(ap[t] + (PAR) * T64_INB + T64_PLANE);  \
             f16x8 bw_[NS];                                                                                   \
             _Pragma("unroll") for (int n = 0; n < NS; n++) bw_[n] = *reinterpret_cast<const f16x8*>(wb + (PAR) * T64_WCH + t * (2 * CH * 16) + n * 512); \
             _Pragma("unroll") for (int n = 0; n < NS; n++) acc[n] = T64_MFMA(bw_[n], ah, acc[n]);            \
-            _Pragma("unroll") for (int n = 0; n < NS; n++) acc[n] = T64_MFMA(bw_[n], al, acc[n]);            \
+            if constexpr (!FAST) { _Pragma("unroll") for (int n = 0; n < NS; n++) acc[n] = T64_MFMA(bw_[n], al, acc[n]); } \
         }                                                                                                    \
         if ((IDN) >= 0) {   /* skip connection: identity on the centre pixel; K chunk C only feeds output block C >> 1 */ \
             const f16x8 ah = *reinterpret_cast<const f16x8*>(ap[4] + (PAR) * T64_INB);                       \

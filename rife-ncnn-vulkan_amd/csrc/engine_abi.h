@@ -174,6 +174,34 @@ int rife_hip_set_flow_scale(rife_hip_t* E, int divisor) {
     });
 }
 
+// ---- precision (include/rife_hip.h): one f16 product per weight tap of the S16 trunk kernels, the skip connection at full precision ----
+int rife_hip_precision(const rife_hip_t* E) { return E ? E->precision : RIFE_HIP_PRECISION_FULL; }
+int rife_hip_set_precision(rife_hip_t* E, int precision) {
+    if (!E) return fail(RIFE_HIP_EINVAL, "null engine");
+    if (!E->loaded) return fail(RIFE_HIP_EINVAL, "set_precision() before load(): the model family is not known yet");
+    if (precision != RIFE_HIP_PRECISION_FULL && precision != RIFE_HIP_PRECISION_FAST)
+        return fail(RIFE_HIP_EINVAL, "the precision must be RIFE_HIP_PRECISION_FULL (0) or RIFE_HIP_PRECISION_FAST (1)");
+    if (precision == RIFE_HIP_PRECISION_FAST) {
+        const char* what = E->v1 ? "model family rife (v1: rife, rife-HD, rife-UHD, rife-anime)" : (!E->v4 && E->v3) ? "model family rife-v3.x" : !E->v4 ? "model family rife-v2.x"
+                           : E->v40 ? "model family rife-v4 (4.0)" : E->tta ? "TTA mode (-x)" : E->tta_temporal ? "temporal TTA mode (-z)" : nullptr;
+        if (what) return fail(RIFE_HIP_ENOSYS, std::string("fast precision is served for model family rife-v4.6 in plain mode only, not for ") + what);
+    }
+    if (precision == E->precision) return 0;
+    return guarded("rife_hip_set_precision", [&] {
+        std::vector<std::unique_ptr<Ctx>> dead;                          // a workspace may hold a captured graph of the other mode's kernels; destroyed outside the lock
+        {
+            std::lock_guard<std::mutex> g(E->mu);
+            if (E->leased > 0) return fail(RIFE_HIP_EINVAL, "set_precision() while a call on the engine is in flight");
+            dead.swap(E->free_ctx);
+            for (auto& kv : E->stream_ctx) dead.push_back(std::move(kv.second));
+            E->stream_ctx.clear();
+            E->precision = precision;
+        }
+        if (!dead.empty()) (void)hipSetDevice(E->gpuid);
+        return 0;
+    });
+}
+
 static int process_common(const rife_hip* E, int w, int h, float timestep) {
     tl_cu_budget = 0;                                                    // every entry point starts on the whole chip; rife_hip_process_device sets its stream's part
     if (!E) return fail(RIFE_HIP_EINVAL, "null engine");
@@ -1351,7 +1379,14 @@ int rife_hip_op_s16_geom(int C, int H, int W, int* pitch, int* rows, unsigned* p
 
 int rife_hip_op_trunk(int gpuid, int kernel, int C, int H, int W, int n_layers, const float* weight, const float* bias, const float* slope, int flip, int cus,
                       int nb, const void* const* in_s16, void* const* out_s16) {
+    return rife_hip_op_trunk_prec(gpuid, kernel, C, H, W, n_layers, weight, bias, slope, flip, cus, nb, in_s16, out_s16, RIFE_HIP_PRECISION_FULL);
+}
+int rife_hip_op_trunk_prec(int gpuid, int kernel, int C, int H, int W, int n_layers, const float* weight, const float* bias, const float* slope, int flip, int cus,
+                           int nb, const void* const* in_s16, void* const* out_s16, int precision) {
     int rc;
+    if (precision != RIFE_HIP_PRECISION_FULL && precision != RIFE_HIP_PRECISION_FAST) return fail(RIFE_HIP_EINVAL, "op_trunk: unknown precision");
+    const bool fast = precision == RIFE_HIP_PRECISION_FAST;
+    if (fast && kernel == RIFE_HIP_TRUNK_KS) return fail(RIFE_HIP_ENOSYS, "op_trunk: conv_ks has no fast-precision form");
     size_t bytes = 0;
     if ((rc = rife_hip_op_s16_geom(C, H, W, nullptr, nullptr, nullptr, &bytes))) return rc;
     if (!weight || !bias || !slope || !in_s16 || !out_s16) return fail(RIFE_HIP_EINVAL, "op_trunk: null argument");
@@ -1411,10 +1446,10 @@ int rife_hip_op_trunk(int gpuid, int kernel, int C, int H, int W, int n_layers, 
         const unsigned char* const* pin = d[cur];
         unsigned char* const* pout = d[cur ^ 1];
         switch (kernel) {
-            case RIFE_HIP_TRUNK_T64: rc = launch_t64(L[i], pin[0], pout[0], H, W, 0, dir); break;
-            case RIFE_HIP_TRUNK_RS: rc = launch_rs(L[i], pin[0], pout[0], H, W, 0, dir); break;
-            case RIFE_HIP_TRUNK_RS2: rc = launch_rs2(L[0], L[1], pin[0], pout[0], H, W, 0, dir); break;
-            case RIFE_HIP_TRUNK_ROW: rc = nb > 1 ? launch_row(L[i], nullptr, nullptr, H, W, 0, nb, pin, pout) : launch_row(L[i], pin[0], pout[0], H, W, 0); break;
+            case RIFE_HIP_TRUNK_T64: rc = launch_t64(L[i], pin[0], pout[0], H, W, 0, dir, fast); break;
+            case RIFE_HIP_TRUNK_RS: rc = launch_rs(L[i], pin[0], pout[0], H, W, 0, dir, fast); break;
+            case RIFE_HIP_TRUNK_RS2: rc = launch_rs2(L[0], L[1], pin[0], pout[0], H, W, 0, dir, fast); break;
+            case RIFE_HIP_TRUNK_ROW: rc = nb > 1 ? launch_row(L[i], nullptr, nullptr, H, W, 0, nb, pin, pout, fast) : launch_row(L[i], pin[0], pout[0], H, W, 0, 0, nullptr, nullptr, fast); break;
             default: rc = nb > 1 ? launch_ks(L[i], nullptr, nullptr, H, W, 0, nb, pin, pout) : launch_ks(L[i], pin[0], pout[0], H, W, 0); break;
         }
     }

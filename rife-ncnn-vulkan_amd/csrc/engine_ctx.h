@@ -193,6 +193,9 @@ struct rife_hip {
     // to 64n and block 3's update happens in k_final_scaled (run_v4)
     int fscale = 1;
     int pad() const { return 32 * fscale; }
+    // rife_hip_set_precision (rife-v4.6, plain mode): RIFE_HIP_PRECISION_FAST = the S16_FAST instantiations of the trunk kernels (conv_t64.h) in every block
+    // that runs on S16 tensors (run_block_convs); a block that leaves that path runs at full precision
+    int precision = RIFE_HIP_PRECISION_FULL;
     // rife-v2.x schedule (IFNet + ContextNet + FusionNet)
     struct V2Block { ConvLayer stem0, stem1, conv[6], head; int c = 0, scale = 1; } fblk[4];
     // rife-v3.x: same ContextNet / FusionNet, IFNet of 3 blocks (scales 4, 2, 1; 160 channels; trunk = 3 x [conv, conv, + skip])

@@ -293,7 +293,9 @@ static int resident_cus() { return std::min(device_cus(true), device_cus()); }
 // RIFE_HIP_T64_LW=1: the 96-channel trunk with two loader waves (conv_t64.h, template parameter LW).  Off by default: measured equal or 2 % slower
 // (4K, same call: trunk_b2 0.401 vs 0.392 - 0.396 ms per pair) - unlike in conv_rs_kernel, whose consumers also lose the weight stream and the stores
 static inline bool t64_loader_waves() { return process_switches().t64_loader_waves; }
-static int launch_t64(const ConvLayer& L, const unsigned char* in, unsigned char* out, int H, int W, hipStream_t st, bool reverse = false) {
+// fast (here and in launch_rs / launch_rs2 / launch_row): the S16_FAST instantiation of the SAME kernel on the same grid (conv_t64.h; include/rife_hip.h
+// rife_hip_set_precision) - which launcher serves a layer never depends on it.
+static int launch_t64(const ConvLayer& L, const unsigned char* in, unsigned char* out, int H, int W, hipStream_t st, bool reverse = false, bool fast = false) {
     if (!L.d_t64) return fail(RIFE_HIP_EINVAL, "layer has no conv_t64 image");
     const int NS = t64_ns(L.cout);
     const int cus = std::max(8, resident_cus() / 8 * 8);
@@ -303,6 +305,12 @@ static int launch_t64(const ConvLayer& L, const unsigned char* in, unsigned char
     a.nchunks = L.cout / 16; a.nnt = L.cout / (32 * NS);
     const int nwg = std::min(t64_wg_per_cu(NS) * cus, (a.ntiles * a.nnt + 7) / 8 * 8);      // all workgroups resident at once
     const char* const what = "conv_t64 launch";
+    if (fast) {
+        if (L.cout == 64) return launch<conv_t64_kernel<3 | S16_FAST, 2>>(what, dim3(nwg), dim3(T64_NTHR), t64_lds(2), st, a);
+        if (L.cout == 96 && t64_loader_waves()) return launch<conv_t64_kernel<2 | S16_FAST, 3, 2>>(what, dim3(nwg), dim3(T64_NTHR + 128), t64_lds(3), st, a);
+        if (L.cout == 96) return launch<conv_t64_kernel<2 | S16_FAST, 3>>(what, dim3(nwg), dim3(T64_NTHR), t64_lds(3), st, a);
+        return fail(RIFE_HIP_EINVAL, "conv_t64 serves 64 and 96 channels");
+    }
     if (L.cout == 64) return launch<conv_t64_kernel<3, 2>>(what, dim3(nwg), dim3(T64_NTHR), t64_lds(2), st, a);       // TAG: the profile class (trunk_b3 .. trunk_b0)
     if (L.cout == 96 && t64_loader_waves()) return launch<conv_t64_kernel<2, 3, 2>>(what, dim3(nwg), dim3(T64_NTHR + 128), t64_lds(3), st, a);      // two loader waves
     if (L.cout == 96) return launch<conv_t64_kernel<2, 3>>(what, dim3(nwg), dim3(T64_NTHR), t64_lds(3), st, a);
@@ -312,7 +320,7 @@ static int launch_t64(const ConvLayer& L, const unsigned char* in, unsigned char
 // the same 64 -> 64 layer on the row-streaming kernel (conv_rs.h): one workgroup per CU, specialised waves.  descend: walk every
 // workgroup's range bottom-up; consecutive layers alternate so that a layer starts on the rows its predecessor wrote last.
 static inline bool rs_split() { return process_switches().rs_split; }      // A/B: epilogue shared by all four io waves (conv_rs.h, SPLIT)
-static int launch_rs(const ConvLayer& L, const unsigned char* in, unsigned char* out, int H, int W, hipStream_t st, bool descend = false) {
+static int launch_rs(const ConvLayer& L, const unsigned char* in, unsigned char* out, int H, int W, hipStream_t st, bool descend = false, bool fast = false) {
     if (!L.d_t64 || L.cout != 64) return fail(RIFE_HIP_EINVAL, "layer has no 64-channel conv_t64 image");
     if ((H + 1) / 2 < RS_MIN_PAIRS) return fail(RIFE_HIP_EINVAL, "conv_rs needs at least " + std::to_string(2 * RS_MIN_PAIRS - 1) + " rows");
     const S16Geom G(H, W);
@@ -320,6 +328,8 @@ static int launch_rs(const ConvLayer& L, const unsigned char* in, unsigned char*
     a.in = in; a.out = out; a.img = L.d_t64; a.H = H; a.W = W; a.pitch = G.pitch; a.plane = G.plane();
     a.npairs = (H + 1) / 2; a.nunits = G.tiles_x * a.npairs; a.descend = descend ? 1 : 0;
     const int nwg = std::min(std::max(1, resident_cus()), a.nunits);      // one workgroup per CU (154 KB of LDS), all resident
+    if (fast && rs_split()) return launch<conv_rs_kernel<S16_FAST, 1>>("conv_rs launch", dim3(nwg), dim3(RS_NTHR), RS_LDS, st, a);
+    if (fast) return launch<conv_rs_kernel<S16_FAST>>("conv_rs launch", dim3(nwg), dim3(RS_NTHR), RS_LDS, st, a);
     if (rs_split()) return launch<conv_rs_kernel<0, 1>>("conv_rs launch", dim3(nwg), dim3(RS_NTHR), RS_LDS, st, a);
     return launch<conv_rs_kernel<0>>("conv_rs launch", dim3(nwg), dim3(RS_NTHR), RS_LDS, st, a);
 }
@@ -340,7 +350,7 @@ static bool rs2_applies(int H, int W) {
     const int cus = rs2_cus();
     return S16Geom(H, W).bytes(64) < (1ull << 31) && rs2_plan(H, W, cus, kparts, nstrips) >= RS2_MIN_ROWS;
 }
-static int launch_rs2(const ConvLayer& LA, const ConvLayer& LB, const unsigned char* in, unsigned char* out, int H, int W, hipStream_t st, bool descend = false) {
+static int launch_rs2(const ConvLayer& LA, const ConvLayer& LB, const unsigned char* in, unsigned char* out, int H, int W, hipStream_t st, bool descend = false, bool fast = false) {
     if (!LA.d_t64 || LA.cout != 64 || !LB.d_t64 || LB.cout != 64) return fail(RIFE_HIP_EINVAL, "layer has no 64-channel conv_t64 image");
     const S16Geom G(H, W);
     const int cus = rs2_cus();
@@ -350,13 +360,14 @@ static int launch_rs2(const ConvLayer& LA, const ConvLayer& LB, const unsigned c
     a.in = in; a.out = out; a.imgA = LA.d_t64; a.imgB = LB.d_t64; a.H = H; a.W = W; a.pitch = G.pitch; a.plane = G.plane(); a.rowmax = G.pitch - 2;
     a.kparts = kparts; a.nseg = nstrips * kparts; a.descend = descend ? 1 : 0; a.limit = (int)(G.bytes(64) - 16);
     const int nwg = std::min(cus, a.nseg);                               // one workgroup per CU (all of its LDS), all resident
+    if (fast) return launch<conv_rs2_kernel<S16_FAST>>("conv_rs2 launch", dim3(nwg), dim3(RS2_NTHR), RS2_LDS, st, a);
     return launch<conv_rs2_kernel<0>>("conv_rs2 launch", dim3(nwg), dim3(RS2_NTHR), RS2_LDS, st, a);
 }
 
 // one C -> C (C = 128, 192) residual trunk convolution of a coarse block, S16 in / S16 out: one workgroup per ROWS x 32 pixels (conv_row.h)
 // nb > 0: one launch for the tensors inb[k] -> outb[k] of nb pairs in flight (gridDim.y = nb)
 static int launch_row(const ConvLayer& L, const unsigned char* in, unsigned char* out, int H, int W, hipStream_t st, int nb = 0,
-                      const unsigned char* const* inb = nullptr, unsigned char* const* outb = nullptr) {
+                      const unsigned char* const* inb = nullptr, unsigned char* const* outb = nullptr, bool fast = false) {
     const unsigned char* const rimg = L.cout == 96 ? L.d_row : L.d_t64;
     if (!rimg) return fail(RIFE_HIP_EINVAL, "layer has no conv_row image");
     const S16Geom G(H, W);
@@ -369,9 +380,12 @@ static int launch_row(const ConvLayer& L, const unsigned char* in, unsigned char
     const char* const what = "conv_row launch";
     if (L.cout == 192) {
         a.ntiles = a.tiles_x * H;
+        if (fast) return launch<conv_row_kernel<192, 1, 0 | S16_FAST>>(what, dim3(a.ntiles, gy), dim3(384), convrow_lds_bytes<192, 1>(), st, a);
         return launch<conv_row_kernel<192, 1, 0>>(what, dim3(a.ntiles, gy), dim3(384), convrow_lds_bytes<192, 1>(), st, a);
     }
     a.ntiles = a.tiles_x * ((H + 1) / 2);
+    if (fast && L.cout == 128) return launch<conv_row_kernel<128, 2, 1 | S16_FAST>>(what, dim3(a.ntiles, gy), dim3(256), convrow_lds_bytes<128, 2>(), st, a);
+    if (fast && L.cout == 96) return launch<conv_row_kernel<96, 2, 2 | S16_FAST>>(what, dim3(a.ntiles, gy), dim3(192), convrow_lds_bytes<96, 2, 2>(), st, a);
     if (L.cout == 128) return launch<conv_row_kernel<128, 2, 1>>(what, dim3(a.ntiles, gy), dim3(256), convrow_lds_bytes<128, 2>(), st, a);
     if (L.cout == 96) return launch<conv_row_kernel<96, 2, 2>>(what, dim3(a.ntiles, gy), dim3(192), convrow_lds_bytes<96, 2, 2>(), st, a);
     return fail(RIFE_HIP_EINVAL, "conv_row serves 96, 128 and 192 channels");

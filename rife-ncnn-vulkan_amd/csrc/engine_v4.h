@@ -365,18 +365,19 @@ after_stem0:
             if ((rc = launch_conv(B.stem1, {c.S1, B.c / 2, 0}, Hb / 2, Wb / 2, {reinterpret_cast<float*>(PA), B.c, 0}, nullptr, st, nullptr, G.pitch, G.plane()))) return rc;
         }
         unsigned char *pc = PA, *pn = PB;
+        const bool fast = E.precision == RIFE_HIP_PRECISION_FAST;       // the S16_FAST instantiations of the same launchers (conv_t64.h); conv_ks has none: the row kernel instead
         if (phases & PH_TRUNK) for (int i = 0; i < 8; i++) {
             if (!rowk && E.rs && E.rs2 && B.c == 64 && !(i & 1) && rs2_applies(Ht, Wt)) {      // layers i, i + 1 in one launch (conv_rs2.h)
                 Timed t(E.prof, B.res[i].cls, (B.res[i].flops_per_pixel + B.res[i + 1].flops_per_pixel) * Ht * Wt, st);
-                if ((rc = launch_rs2(B.res[i], B.res[i + 1], pc, pn, Ht, Wt, st, (i & 2) != 0))) return rc;
+                if ((rc = launch_rs2(B.res[i], B.res[i + 1], pc, pn, Ht, Wt, st, (i & 2) != 0, fast))) return rc;
                 std::swap(pc, pn); i++;
                 continue;
             }
             Timed t(E.prof, B.res[i].cls, B.res[i].flops_per_pixel * Ht * Wt, st);
-            if (rowk && ks_serves(E.ks_mask, B.c)) rc = launch_ks(B.res[i], pc, pn, Ht, Wt, st);
-            else if (rowk) rc = launch_row(B.res[i], pc, pn, Ht, Wt, st);
-            else if (E.rs && B.c == 64 && (Ht + 1) / 2 >= RS_MIN_PAIRS) rc = launch_rs(B.res[i], pc, pn, Ht, Wt, st, (i & 1) != 0);      // tiny tensors: conv_t64
-            else rc = launch_t64(B.res[i], pc, pn, Ht, Wt, st, (i & 1) == 0);
+            if (rowk && ks_serves(E.ks_mask, B.c) && !fast) rc = launch_ks(B.res[i], pc, pn, Ht, Wt, st);
+            else if (rowk) rc = launch_row(B.res[i], pc, pn, Ht, Wt, st, 0, nullptr, nullptr, fast);
+            else if (E.rs && B.c == 64 && (Ht + 1) / 2 >= RS_MIN_PAIRS) rc = launch_rs(B.res[i], pc, pn, Ht, Wt, st, (i & 1) != 0, fast);      // tiny tensors: conv_t64
+            else rc = launch_t64(B.res[i], pc, pn, Ht, Wt, st, (i & 1) == 0, fast);
             if (rc) return rc;
             std::swap(pc, pn);
         }
@@ -586,8 +587,9 @@ static int run_v4_group(const rife_hip& E, Ctx* const* cs, int G, const uint8_t*
             for (int i = 0; i < 8; i++) {
                 for (int g = 0; g < G; g++) { pin[g] = cs[g]->P[b][i & 1]; pout[g] = cs[g]->P[b][(i & 1) ^ 1]; }
                 Timed t(E.prof, B.res[i].cls, B.res[i].flops_per_pixel * Ht * Wt * G, lead);
-                if (ks_serves(E.ks_mask, B.c)) rc = launch_ks(B.res[i], nullptr, nullptr, Ht, Wt, lead, G, pin, pout);
-                else rc = launch_row(B.res[i], nullptr, nullptr, Ht, Wt, lead, G, pin, pout);
+                const bool fast = E.precision == RIFE_HIP_PRECISION_FAST;
+                if (ks_serves(E.ks_mask, B.c) && !fast) rc = launch_ks(B.res[i], nullptr, nullptr, Ht, Wt, lead, G, pin, pout);
+                else rc = launch_row(B.res[i], nullptr, nullptr, Ht, Wt, lead, G, pin, pout, fast);
                 if (rc) return rc;
             }
         }

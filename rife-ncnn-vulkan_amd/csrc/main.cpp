@@ -798,6 +798,7 @@ static void print_usage() {
     fprintf(stderr, "  -z                   enable temporal tta mode\n");
     fprintf(stderr, "  -u                   enable UHD mode\n");
     fprintf(stderr, "  -d divisor           estimate flow at 1/divisor resolution (1 or 2; rife-v4.6; for UHD material)\n");
+    fprintf(stderr, "  -p precision         full (default) or fast: one f16 product per weight tap of the residual trunks (rife-v4.6; not with -x/-z)\n");
     fprintf(stderr, "  -f pattern-format    output image filename pattern format (%%08d.jpg/png/webp/ppm, default=ext/%%08d.png)\n");
     fprintf(stderr, "  -b bit-depth         bits per sample, 8 or 10 (default=8); 10: rife-v4.6 only, 16-bit png / maxval-1023 ppm output\n");
     fprintf(stderr, "  -c matrix[:range]    video mode (-i in.y4m): colour description, 709 / 601 / 2020 and limited / full (default=709:limited, or the file's XCOLORRANGE);\n");
@@ -867,7 +868,7 @@ int main(int argc, char** argv) {
         if (!encode_image10(argv[3], w, h, codes.data())) { fprintf(stderr, "encode image %s failed\n", argv[3]); return 1; }
         return 0;
     }
-    std::string input0, input1, inputpath, outputpath, model = "rife-v2.3", pattern_format = "%08d.png", colour;
+    std::string input0, input1, inputpath, outputpath, model = "rife-v2.3", pattern_format = "%08d.png", colour, precision_arg = "full";
     int numframe = 0;
     float timestep = 0.5f;
     std::vector<int> gpuid, jobs_proc;
@@ -875,7 +876,7 @@ int main(int argc, char** argv) {
     bool verbose = false, tta = false, tta_temporal = false, uhd = false, keep_alpha = false;
 
     int opt;
-    while ((opt = getopt(argc, argv, "0:1:i:o:n:s:m:g:j:f:b:c:d:avxzuh")) != -1) {
+    while ((opt = getopt(argc, argv, "0:1:i:o:n:s:m:g:j:f:b:c:d:p:avxzuh")) != -1) {
         switch (opt) {
             case '0': input0 = optarg; break;
             case '1': input1 = optarg; break;
@@ -898,6 +899,7 @@ int main(int argc, char** argv) {
             case 'b': bits = atoi(optarg); break;
             case 'c': colour = optarg; break;
             case 'd': flow_divisor = atoi(optarg); break;
+            case 'p': precision_arg = optarg; break;
             case 'a': keep_alpha = true; break;
             case 'v': verbose = true; break;
             case 'x': tta = true; break;
@@ -920,6 +922,12 @@ int main(int argc, char** argv) {
     if (flow_divisor != 1 && flow_divisor != 2) { fprintf(stderr, "invalid flow scale divisor argument (-d), must be 1 or 2\n"); return -1; }
     if (flow_divisor == 2 && (tta || tta_temporal)) {
         fprintf(stderr, "flow scale 2 (-d 2) is served in plain mode only, not with %s\n", tta ? "-x (TTA mode)" : "-z (temporal TTA mode)");
+        return -1;
+    }
+    if (precision_arg != "full" && precision_arg != "fast") { fprintf(stderr, "invalid precision argument (-p), must be full or fast\n"); return -1; }
+    const int precision = precision_arg == "fast" ? RIFE_HIP_PRECISION_FAST : RIFE_HIP_PRECISION_FULL;
+    if (precision == RIFE_HIP_PRECISION_FAST && (tta || tta_temporal)) {
+        fprintf(stderr, "fast precision (-p fast) is served in plain mode only, not with %s\n", tta ? "-x (TTA mode)" : "-z (temporal TTA mode)");
         return -1;
     }
     if (keep_alpha && deep) { fprintf(stderr, "alpha (-a) is served at depth 8 only, not with -b 10 (A2B10G10R10 has two alpha bits)\n"); return -1; }
@@ -984,6 +992,7 @@ int main(int argc, char** argv) {
     if (keep_alpha && !rife_v4) { fprintf(stderr, "alpha (-a) is served for model family rife-v4.6 only, not for %s\n", model.c_str()); return -1; }
     if (video && !rife_v4) { fprintf(stderr, "4:2:0 YUV frames are served for model family rife-v4.6 in plain mode only, not for %s\n", model.c_str()); return 1; }
     if (flow_divisor == 2 && !rife_v4) { fprintf(stderr, "flow scale 2 (-d 2) is served for model family rife-v4.6 only, not for %s\n", model.c_str()); return -1; }
+    if (precision == RIFE_HIP_PRECISION_FAST && !rife_v4) { fprintf(stderr, "fast precision (-p fast) is served for model family rife-v4.6 only, not for %s\n", model.c_str()); return -1; }
     if (!rife_v4 && (numframe != 0 || timestep != 0.5f)) { fprintf(stderr, "only rife-v4 model support custom numframe and timestep\n"); return -1; }
 
     // ---- task list (src/main.cpp:692-766) ----
@@ -1044,6 +1053,7 @@ int main(int argc, char** argv) {
         if (r->load(model) != 0) { fprintf(stderr, "loading %s failed: %s\n", model.c_str(), rife_hip_last_error()); return video ? 1 : -1; }
         // rife-v4 (4.0) shares the directory prefix: the engine knows the family, and refuses before the first pair
         if (flow_divisor != 1 && r->set_flow_scale(flow_divisor) != 0) { fprintf(stderr, "flow scale %d (-d) is not available: %s\n", flow_divisor, rife_hip_last_error()); return video ? 1 : -1; }
+        if (precision != RIFE_HIP_PRECISION_FULL && r->set_precision(precision) != 0) { fprintf(stderr, "fast precision (-p fast) is not available: %s\n", rife_hip_last_error()); return video ? 1 : -1; }
         if (video) {      // rife-v4 (4.0) shares the directory prefix, and the engine knows which colour descriptions it serves: ask it now, with one pixel
             const uint16_t one[3] = {0, 0, 0};
             rife_hip_frame* f = r->upload_yuv(one, 1, 1, yuv_pixfmt);

@@ -56,6 +56,28 @@ int RIFE::set_flow_scale(int divisor)
     return ret;
 }
 
+// weak for the same reason: an engine stand-in without the two precision calls still links
+extern "C" int rife_hip_set_precision(rife_hip_t* r, int precision) __attribute__((weak));
+extern "C" int rife_hip_precision(const rife_hip_t* r) __attribute__((weak));
+
+int RIFE::set_precision(int precision)
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_set_precision)
+    {
+        fprintf(stderr, "RIFE::set_precision: this engine has one precision\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_set_precision(engine, precision);
+    if (ret) fprintf(stderr, "RIFE::set_precision: %s\n", rife_hip_last_error());
+    return ret;
+}
+
+int RIFE::precision() const
+{
+    return engine && rife_hip_precision ? rife_hip_precision(engine) : RIFE_HIP_PRECISION_FULL;
+}
+
 int RIFE::process(const ncnn::Mat& in0image, const ncnn::Mat& in1image, float timestep, ncnn::Mat& outimage) const
 {
     const int pixfmt = mat_pixfmt(in0image);

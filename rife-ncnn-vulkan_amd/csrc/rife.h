@@ -27,6 +27,12 @@ public:
     // Returns the C-ABI's code; the message of a refusal is rife_hip_last_error().
     int set_flow_scale(int divisor);
 
+    // Extension, not in the reference (include/rife_hip.h "precision"): RIFE_HIP_PRECISION_FULL (the default) or RIFE_HIP_PRECISION_FAST - one f16 product per
+    // weight tap of the residual trunk convolutions, the skip connection at full precision (rife-v4.6, plain mode).  After load(), with no call in flight.
+    // Returns the C-ABI's code; the message of a refusal is rife_hip_last_error().
+    int set_precision(int precision);
+    int precision() const;
+
     // The reference exposes its four back-ends publicly (src/rife.h:25-29).  Here the HIP engine is the only one:
     // process_v4 == process for rife_v4 objects; the *_cpu entry points report an error (no CPU path in this build).
     int process_cpu(const ncnn::Mat& in0image, const ncnn::Mat& in1image, float timestep, ncnn::Mat& outimage) const;

@@ -171,6 +171,14 @@ for B in $ASAN $TSAN; do
     $B -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/d23.png -m rife-v2.3 -d 2 > $T/log.txt 2>&1; rc=$?
     [ $rc -eq 255 ] && [ ! -e $T/out/d23.png ] || { echo "   $(basename $B) -d 2 -m rife-v2.3: rc $rc (a refusal is 255 and writes nothing)"; FAIL=1; tail -20 $T/log.txt; }
 done
+echo "== 4c. precision (-p fast through RIFE::set_precision of the stub; refusals of an unknown word and of another family end before any engine exists) under both"
+for B in $ASAN $TSAN; do
+    run "$(basename $B) pair -p fast" $B -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/pf.png -m rife-v4.6 -p fast
+    $B -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/pb.png -m rife-v4.6 -p bogus > $T/log.txt 2>&1; rc=$?
+    [ $rc -eq 255 ] && [ ! -e $T/out/pb.png ] || { echo "   $(basename $B) -p bogus: rc $rc (a refusal is 255 and writes nothing)"; FAIL=1; tail -20 $T/log.txt; }
+    $B -0 $T/in_png/000.png -1 $T/in_png/001.png -o $T/out/p23.png -m rife-v2.3 -p fast > $T/log.txt 2>&1; rc=$?
+    [ $rc -eq 255 ] && [ ! -e $T/out/p23.png ] || { echo "   $(basename $B) -p fast -m rife-v2.3: rc $rc (a refusal is 255 and writes nothing)"; FAIL=1; tail -20 $T/log.txt; }
+done
 echo "== 5. rife_hip_image_check's rules (csrc/image_check.h, host only) over refusing and accepting descriptors, a program of its own under ASan + UBSan"
 $ROOT/rife-ncnn-vulkan_amd/image-check-asan > $T/log.txt 2>&1; rc=$?
 echo "   image-check-asan: rc $rc, $(tail -1 $T/log.txt)"; [ $rc -ne 0 ] && { FAIL=1; tail -30 $T/log.txt; }
