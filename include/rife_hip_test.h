@@ -26,7 +26,11 @@ int rife_hip_v4_flow_dims(const rife_hip_t* r, int w, int h, int fi, int* channe
  * written by the stem kernel that applies the last update itself (blocks 2 and 3; flownet.param:99-105, 152-158).
  * what = 5 (b = 3): the 12-channel input of IFBlock 3 read back through the product's row-streaming stem kernel (both of its convolutions with
  * one-hot weights, eight launches; values to 2^-21 relative), 12 x hp x wp.
- * what = 6 (b = 2, 3): F and M, 5 x hp x wp, written by the flow cascade kernel from the b injected flows alone; what = 4 is its reference. */
+ * what = 6 (b = 2, 3): F and M, 5 x hp x wp, written by the flow cascade kernel from the b injected flows alone; what = 4 is its reference.
+ * what = 7 (b = 0..3, n_inject = b, RGB8): the FIRST S16 trunk tensor of IFBlock b, raw and whole, after the block's stems as a plain pass runs them (assembly +
+ * stem-0 + stem-1 for block 0, the fused stem-0 kernel + the S16 stride-2 kernel for blocks 1 - 3, the row-streaming stem kernel where the product uses it;
+ * RIFE_HIP_STEM_RS=0 at create time: the two-kernel sequence for block 3).  out_chw then takes rife_hip_op_s16_geom(C, hp / 4 s, wp / 4 s) bytes, C = 192, 128, 96, 64
+ * and s = 8, 4, 2, 1 for b = 0..3.  A block that is not on the S16 path at that frame size: -RIFE_HIP_EINVAL. */
 int rife_hip_v4_tap(const rife_hip_t* r, const uint8_t* in0_rgb, const uint8_t* in1_rgb, int w, int h, float timestep, int what, int b,
                     const float* const* inject, int n_inject, float* out_chw);
 /* The plain pass with blobs flow0 .. flow{n_inject - 1} injected (n_inject = 0..3): the remaining blocks and the fused tail run as in
@@ -93,6 +97,19 @@ int rife_hip_op_trunk(int gpuid, int kernel, int C, int H, int W, int n_layers, 
  * fast form (-RIFE_HIP_ENOSYS); an unknown precision is -RIFE_HIP_EINVAL. */
 int rife_hip_op_trunk_prec(int gpuid, int kernel, int C, int H, int W, int n_layers, const float* weight, const float* bias, const float* slope, int flip, int cus,
                            int nb, const void* const* in_s16, void* const* out_s16, int precision);
+
+/* ---- the two ENDS of the S16 trunk alone: the kernel that writes the first S16 tensor of a block and the kernel that reads the last one, one launch each, through
+ * the product's layer upload with the flags rife_hip_load sets and the product's launcher (launch_conv).  C = 64, 96, 128, 192; anything else, and weights that are
+ * not exactly fp16, return -RIFE_HIP_EINVAL before anything is uploaded or launched.
+ * op_stem1_s16: stem-1, the 3x3 stride-2 convolution C/2 -> C + bias + LeakyReLU(slope) with the S16 epilogue (conv_h2s2_kernel<NS, true>, weights packed with the
+ * row permutation of the S16 kernels).  x_chw: C/2 x 2 Ht x 2 Wt fp32 (the kernel reads it as NHWC, ld = C/2); weight [C][C/2][3][3], bias [C]; out_s16: a raw S16
+ * tensor of op_s16_geom(C, Ht, Wt), uploaded as given, and the whole tensor comes back after the launch. */
+int rife_hip_op_stem1_s16(int gpuid, int C, int Ht, int Wt, const float* x_chw, const float* weight, const float* bias, float slope, void* out_s16);
+/* op_head_ps: the head, 4x4 stride-2 pad-1 transposed convolution C -> 24 + bias + PixelShuffle(2) into the flow tensor [4 Ht][4 Wt][8] (head_h2_kernel<EPI_DECONV_PS,
+ * S16IN>).  s16 = 1: input is a raw S16 tensor of op_s16_geom(C, Ht, Wt); s16 = 0: input is C x Ht x Wt fp32 (read as NHWC, ld = C).  weight [24][C][4][4],
+ * bias [24].  out8hw: 8 x 4 Ht x 4 Wt planar; it is uploaded into the device flow tensor before the launch and all 8 planes come back - the kernel writes
+ * planes 0 - 5 and must leave 6 and 7 alone. */
+int rife_hip_op_head_ps(int gpuid, int C, int Ht, int Wt, int s16, const void* input, const float* weight, const float* bias, float* out8hw);
 
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */

@@ -57,7 +57,7 @@ ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
-                    "rife_hip_op_trunk_prec"]
+                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps"]
 # rife_hip_op_trunk: which S16 trunk kernel (include/rife_hip_test.h RIFE_HIP_TRUNK_*)
 TRUNK_T64, TRUNK_RS, TRUNK_RS2, TRUNK_ROW, TRUNK_KS = 0, 1, 2, 3, 4
 EINVAL = 1      # RIFE_HIP_EINVAL: calls return its negative
@@ -150,6 +150,8 @@ def _load(path, with_test_surface):
         L.rife_hip_op_s16_geom.argtypes = [ci, ci, ci, vp, vp, vp, vp]
         L.rife_hip_op_trunk.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp]
         L.rife_hip_op_trunk_prec.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, ci]
+        L.rife_hip_op_stem1_s16.argtypes = [ci, ci, ci, ci, vp, vp, vp, cf, vp]
+        L.rife_hip_op_head_ps.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp]
     return L
 
 
@@ -747,7 +749,8 @@ class RIFE:
         """what 0 / 1: 12-channel input of IFBlock b (unfused kernel / through the fused stem kernel); 2: blob out0 before the postproc;
         4 / 3: F (4 channels) and M as block b's stem finds them, after k_flow_update / as written by the stem that applies the last update itself;
         5 (b = 3): the block input through the row-streaming stem kernel of the product;
-        6 (b = 2, 3): F and M, (5, hp, wp), as k_flow_cascade<b> writes them from the b injected flows alone (4 is its sequential reference)."""
+        6 (b = 2, 3): F and M, (5, hp, wp), as k_flow_cascade<b> writes them from the b injected flows alone (4 is its sequential reference);
+        7 (b = 0..3, RGB8): the first S16 trunk tensor of block b after the block's stems, raw: a uint8 array of op_s16_geom(C, hp / 4 s, wp / 4 s)[3] bytes."""
         self._need_taps()
         px = _pix_of(in0image, pixfmt)
         if px is not None and _pix_of(in1image, px) != px:
@@ -759,7 +762,11 @@ class RIFE:
         h, w = a.shape[:2]
         wp, hp = (w + 31) // 32 * 32, (h + 31) // 32 * 32
         s = {1: 4, 2: 2, 3: 1}.get(b, 1)
-        out = np.empty((4 if px == PIX_RGBA8 else 3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4, 6) else (12, hp // s, wp // s), np.float32)
+        if what == 7:
+            s, C = {0: (8, 192), 1: (4, 128), 2: (2, 96), 3: (1, 64)}[b]
+            out = np.empty(op_s16_geom(C, hp // (4 * s), wp // (4 * s))[3], np.uint8)
+        else:
+            out = np.empty((4 if px == PIX_RGBA8 else 3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4, 6) else (12, hp // s, wp // s), np.float32)
         inj = [np.ascontiguousarray(f, dtype=np.float32) for f in inject]
         arr = (ctypes.c_void_p * max(1, len(inj)))(*[f.ctypes.data for f in inj])
         if px is not None:
@@ -856,6 +863,36 @@ def op_trunk(kernel, C, H, W, weight, bias, slope, in_s16, out_s16, flip=0, cus=
     _check(testlib().rife_hip_op_trunk_prec(gpuid, int(kernel), int(C), int(H), int(W), n, _p(weight), _p(bias), _p(sl), int(flip), int(cus), len(ins), pi, po,
                                             PRECISION_FAST if fast else PRECISION_FULL), "op_trunk", testlib())
     return outs[0] if single else outs
+
+
+def op_stem1_s16(C, Ht, Wt, x, weight, bias, slope, out_s16, gpuid=0):
+    """conv_h2s2_kernel<NS, true> alone: x (C / 2, 2 Ht, 2 Wt) fp32 -> the raw S16 tensor of a C x Ht x Wt trunk.  out_s16 (uint8, op_s16_geom(C, Ht, Wt)[3] bytes)
+    goes to the device as given; returns the whole tensor after the launch as a new array."""
+    x = np.ascontiguousarray(x, np.float32); weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32)
+    if x.shape != (C // 2, 2 * Ht, 2 * Wt) or weight.size != C * (C // 2) * 9 or bias.size != C:
+        raise ValueError("x must be (C / 2, 2 Ht, 2 Wt), weight (C, C / 2, 3, 3) and bias (C)")
+    out = np.array(out_s16, np.uint8).reshape(-1)      # a copy: the call writes into it
+    if C % 16 == 0 and out.size != op_s16_geom(C, Ht, Wt)[3]:
+        raise ValueError("an S16 tensor of this geometry has %d bytes" % op_s16_geom(C, Ht, Wt)[3])
+    _check(testlib().rife_hip_op_stem1_s16(gpuid, int(C), int(Ht), int(Wt), _p(x), _p(weight), _p(bias), float(slope), _p(out)), "op_stem1_s16", testlib())
+    return out
+
+
+def op_head_ps(C, Ht, Wt, x, weight, bias, out8, gpuid=0):
+    """head_h2_kernel<EPI_DECONV_PS, S16IN> alone.  x: a raw S16 tensor (uint8: S16IN = true) or (C, Ht, Wt) fp32 (S16IN = false).  out8 (8, 4 Ht, 4 Wt) fp32 is the
+    flow tensor before the launch; returns all 8 planes after it as a new array."""
+    s16 = isinstance(x, np.ndarray) and x.dtype == np.uint8
+    x = np.ascontiguousarray(x) if s16 else np.ascontiguousarray(x, np.float32)
+    weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32)
+    if weight.size != 24 * C * 16 or bias.size != 24 or (not s16 and x.shape != (C, Ht, Wt)):
+        raise ValueError("x must be (C, Ht, Wt) or a raw S16 tensor, weight (24, C, 4, 4) and bias (24)")
+    if s16 and C % 16 == 0 and x.size != op_s16_geom(C, Ht, Wt)[3]:
+        raise ValueError("an S16 tensor of this geometry has %d bytes" % op_s16_geom(C, Ht, Wt)[3])
+    out = np.array(out8, np.float32)                   # a copy: the call writes into it
+    if out.shape != (8, 4 * Ht, 4 * Wt):
+        raise ValueError("out8 must be (8, 4 Ht, 4 Wt)")
+    _check(testlib().rife_hip_op_head_ps(gpuid, int(C), int(Ht), int(Wt), int(s16), _p(x), _p(weight), _p(bias), _p(out)), "op_head_ps", testlib())
+    return out
 
 
 def op_yuv_to_rgb10(buf, w, h, pixfmt, gpuid=0):

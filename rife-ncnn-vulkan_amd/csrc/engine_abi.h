@@ -998,6 +998,7 @@ static int tap_prologue(const rife_hip_t* E, Ctx& c, const uint8_t* in0, const u
 // what = 4 / 3: F, M as block b's stem reads them: after k_flow_update / written by the stem that applies the update of flow{b-1} itself.
 // what = 5: block 3's input through stem_rs_kernel, the product's kernel for that block (see below).
 // what = 6: F, M as k_flow_cascade<b> (flow_cascade.h) writes them from the b injected flows alone, b = 2 / 3; what = 4 is its sequential reference.
+// what = 7: the first S16 trunk tensor of block b (0..3), raw, after the block's stems as run_block_convs runs them (n_inject = b).
 // out: planar CHW fp32, 12 x hp/S x wp/S (what 0, 1) or 3 x hp x wp (what 2).  n_inject must be b (what 0, 1) or 4 (what 2).
 static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, int what, int b,
                                 const float* const* inject, int n_inject, float* out, int pixfmt = RIFE_HIP_PIX_RGB8) {
@@ -1008,15 +1009,28 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
     if (pix_bpp(pixfmt) == 0) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
     if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if (pixfmt && what == 3) return fail(RIFE_HIP_EINVAL, "tap 3 (an A/B form the product does not run) is served for RGB8 frames only");
-    if (what < 0 || what > 6) return fail(RIFE_HIP_EINVAL, "bad tap");
+    if (what < 0 || what > 7) return fail(RIFE_HIP_EINVAL, "bad tap");
+    if (what == 7 && pixfmt) return fail(RIFE_HIP_EINVAL, "tap 7 (the block stems) is served for RGB8 frames only");
     if (what == 6 && b != 2 && b != 3) return fail(RIFE_HIP_EINVAL, "the flow cascade runs after block 1 (b = 2) or block 2 (b = 3)");
     if (what == 5 && b != 3) return fail(RIFE_HIP_EINVAL, "the row-streaming stem kernel serves block 3");
-    if (what == 2 ? n_inject != 4 : (b < 1 || b > 3 || n_inject != b)) return fail(RIFE_HIP_EINVAL, "bad block / injection count");
+    if (what == 2 ? n_inject != 4 : (b < (what == 7 ? 0 : 1) || b > 3 || n_inject != b)) return fail(RIFE_HIP_EINVAL, "bad block / injection count");
     if ((rc = check_device(E->gpuid))) return rc;
     Ctx c; float* tmp = nullptr;
     const float* pending = nullptr;
-    if ((rc = tap_prologue(E, c, in0, in1, w, h, inject, n_inject, tmp, (what == 1 || what == 3) ? &pending : nullptr, pixfmt, what != 6))) return rc;
+    if ((rc = tap_prologue(E, c, in0, in1, w, h, inject, n_inject, tmp, (what == 1 || what == 3 || what == 7) ? &pending : nullptr, pixfmt, what != 6))) return rc;
     hipStream_t st = c.stream;
+    if (what == 7) {
+        // Block b's stems as a plain pass runs them (run_block_convs with PH_STEMS: run_assemble + stem-0 + stem-1 for block 0, stem0_fused_kernel +
+        // conv_h2s2_kernel<NS, true> for blocks 1 - 3, stem_rs_kernel where block_on_stem_rs says so), then the first S16 trunk tensor c.P[b][0], whole and raw:
+        // rife_hip_op_s16_geom(C of the block, hp / 4 scale, wp / 4 scale) bytes.
+        if (!block_on_s16(*E, c, b)) return fail(RIFE_HIP_EINVAL, "tap 7: this block does not run on S16 trunk tensors at this frame size");
+        if ((rc = run_block_convs(*E, c, b, timestep, nullptr, nullptr, PH_STEMS, pending))) return rc;
+        const rife_hip::Block& B7 = E->blk[b];
+        const size_t nb = S16Geom(c.hp / B7.scale / 4, c.wp / B7.scale / 4).bytes(B7.c);
+        HIPCHK(hipMemcpyAsync(out, c.P[b][0], nb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }
     // what = 3 / 4: F (4 channels) and M as block b's stem finds them, [5][hp][wp]: 4 = after k_flow_update, 3 = as written by the stem that applies
     // the last update itself (only where the product fuses it: EINVAL otherwise)
     auto copy_fm = [&](const float4* F, const float* M) -> int {
@@ -1459,6 +1473,89 @@ int rife_hip_op_trunk_prec(int gpuid, int kernel, int C, int H, int W, int n_lay
         e = hipMemcpy(out_s16[k], d[cur][k], bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("op_trunk: ") + hipGetErrorString(e));
     }
+    cleanup();
+    return rc;
+}
+
+// ---- the two ends of the S16 trunk alone (tests/test_gpu_s16_ends.py): the stride-2 stem that writes the first S16 tensor of a block and the PixelShuffle head
+// that reads the last one, each through the product's layer upload (the flags rife_hip_load sets) and launch_conv ----
+static bool s16_ends_channels(int C) { return C == 64 || C == 96 || C == 128 || C == 192; }
+static bool all_fp16(const float* w, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!((float)(_Float16)w[i] == w[i])) return false;
+    return true;
+}
+
+int rife_hip_op_stem1_s16(int gpuid, int C, int Ht, int Wt, const float* x_chw, const float* weight, const float* bias, float slope, void* out_s16) {
+    int rc;
+    if (!s16_ends_channels(C)) return fail(RIFE_HIP_EINVAL, "op_stem1_s16: the S16 variant of the stride-2 stem serves 64, 96, 128 and 192 output channels");
+    size_t bytes = 0;
+    if ((rc = rife_hip_op_s16_geom(C, Ht, Wt, nullptr, nullptr, nullptr, &bytes))) return rc;
+    if (!x_chw || !weight || !bias || !out_s16) return fail(RIFE_HIP_EINVAL, "op_stem1_s16: null argument");
+    const int cin = C / 2, H = 2 * Ht, W = 2 * Wt;
+    if (!all_fp16(weight, (size_t)C * cin * 9)) return fail(RIFE_HIP_EINVAL, "op_stem1_s16: the S16 kernels need weights that are exactly fp16");
+    if ((rc = check_device(gpuid))) return rc;
+    ConvLayer L;
+    float *d_chw = nullptr, *d_x = nullptr; unsigned char* d_o = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_chw); (void)hipFree(d_x); (void)hipFree(d_o); free_layer(L); };
+    L.cin = cin; L.cout = C; L.stride = 2; L.deconv = false; L.epi = EPI_STORE; L.cls = "stem1"; L.tag = 0; L.skip = false;      // setup() of rife_hip_load for stem1_b*
+    L.want_t64 = false; L.want_s16out = true;
+    if ((rc = upload_layer(L, weight, bias, nullptr, slope))) { cleanup(); return rc; }
+    if (!L.d_whp) { cleanup(); return fail(RIFE_HIP_EINVAL, "op_stem1_s16: the layer upload made no row-permuted weight image"); }
+    const S16Geom G(Ht, Wt);
+    const size_t nin = (size_t)cin * H * W;
+    hipError_t e = hipMalloc(&d_chw, nin * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_x, nin * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_o, bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_chw, x_chw, nin * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_o, out_s16, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cleanup(); return fail(RIFE_HIP_EHIP, std::string("op_stem1_s16: ") + hipGetErrorString(e)); }
+    hipLaunchKernelGGL(k_chw_to_nhwc, grid2d(W, H), dim3(256), 0, 0, d_chw, d_x, cin, H, W, cin);
+    rc = launch_conv(L, {d_x, cin, 0}, H, W, {reinterpret_cast<float*>(d_o), C, 0}, nullptr, 0, nullptr, G.pitch, G.plane());      // run_block_convs: stem-1 on the S16 path
+    e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = hipMemcpy(out_s16, d_o, bytes, hipMemcpyDeviceToHost);
+    if (!rc && e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("op_stem1_s16: ") + hipGetErrorString(e));
+    cleanup();
+    return rc;
+}
+
+int rife_hip_op_head_ps(int gpuid, int C, int Ht, int Wt, int s16, const void* input, const float* weight, const float* bias, float* out8hw) {
+    int rc;
+    if (!s16_ends_channels(C)) return fail(RIFE_HIP_EINVAL, "op_head_ps: the heads of rife-v4.6 read 64, 96, 128 or 192 channels");
+    size_t bytes = 0;
+    if ((rc = rife_hip_op_s16_geom(C, Ht, Wt, nullptr, nullptr, nullptr, &bytes))) return rc;
+    if (!input || !weight || !bias || !out8hw) return fail(RIFE_HIP_EINVAL, "op_head_ps: null argument");
+    if (!all_fp16(weight, (size_t)24 * C * 16)) return fail(RIFE_HIP_EINVAL, "op_head_ps: the split-f16 head needs weights that are exactly fp16");
+    if ((rc = check_device(gpuid))) return rc;
+    ConvLayer L;
+    float *d_chw = nullptr, *d_flow = nullptr; unsigned char* d_in = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_chw); (void)hipFree(d_flow); (void)hipFree(d_in); free_layer(L); };
+    L.cin = C; L.cout = 24; L.stride = 1; L.deconv = true; L.epi = EPI_DECONV_PS; L.cls = "head"; L.tag = 0; L.skip = false;      // setup() of rife_hip_load for head_b*
+    L.want_t64 = false; L.want_s16out = false;
+    if ((rc = upload_layer(L, weight, bias, nullptr, 1.0f))) { cleanup(); return rc; }
+    if (!L.d_wh) { cleanup(); return fail(RIFE_HIP_EINVAL, "op_head_ps: the layer upload made no split-f16 weight image"); }
+    const S16Geom G(Ht, Wt);
+    const int Hf = 4 * Ht, Wf = 4 * Wt;
+    const size_t nflow = (size_t)8 * Hf * Wf, nin = (size_t)C * Ht * Wt, nx = s16 ? bytes : nin * 4;
+    hipError_t e = hipMalloc(&d_chw, std::max(nflow, nin) * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_flow, nflow * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_in, nx);
+    if (e == hipSuccess) e = hipMemcpy(d_chw, out8hw, nflow * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cleanup(); return fail(RIFE_HIP_EHIP, std::string("op_head_ps: ") + hipGetErrorString(e)); }
+    hipLaunchKernelGGL(k_chw_to_nhwc, grid2d(Wf, Hf), dim3(256), 0, 0, d_chw, d_flow, 8, Hf, Wf, 8);
+    if (s16) {
+        e = hipMemcpy(d_in, input, bytes, hipMemcpyHostToDevice);
+    } else {
+        e = hipMemcpy(d_chw, input, nin * 4, hipMemcpyHostToDevice);      // the null stream: after the kernel above has read d_chw
+        if (e == hipSuccess) hipLaunchKernelGGL(k_chw_to_nhwc, grid2d(Wt, Ht), dim3(256), 0, 0, d_chw, reinterpret_cast<float*>(d_in), C, Ht, Wt, C);
+    }
+    if (e != hipSuccess) { cleanup(); return fail(RIFE_HIP_EHIP, std::string("op_head_ps: ") + hipGetErrorString(e)); }
+    rc = launch_conv(L, {reinterpret_cast<float*>(d_in), C, 0}, Ht, Wt, {d_flow, 8, 0}, nullptr, 0, nullptr, s16 ? G.pitch : 0, s16 ? G.plane() : 0u);
+    if (!rc) {
+        hipLaunchKernelGGL(k_nhwc_to_chw, grid2d(Wf, Hf), dim3(256), 0, 0, d_flow, d_chw, 8, Hf, Wf, 8);
+        e = hipMemcpy(out8hw, d_chw, nflow * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("op_head_ps: ") + hipGetErrorString(e));
+    } else (void)hipDeviceSynchronize();
     cleanup();
     return rc;
 }

@@ -1,7 +1,9 @@
 """rife-v4.6 on the HIP engine vs the CPU oracle, through the C-ABI (GPU box only).
 
-Bar (BASELINE.json north_star): <= 1 LSB per RGB channel against the reference CPU path.  Stage taps are checked
-at 1e-3 absolute (flows are O(1) px; fp32 reassociation noise through up to 40 stacked convs is ~1e-5)."""
+Bar (BASELINE.json north_star): <= 1 LSB per RGB channel against the reference CPU path.  Stage taps: flows are O(1) px and the fp32
+reassociation noise through up to 40 stacked convs measures 1e-6 .. 8e-6 on the MI355X (profiles/s16_ends/README.md).  The bar of a stage-flow test is
+8 x its largest measured error where that stays under 4.8e-5 - half of the smallest change a lost lo plane at either end of a block's trunk makes
+to that block's own flow (9.6e-5, flow0 at 64x64) - and the old 1e-3 where it does not (160x96: 8 x 7.9e-6 = 6.3e-5)."""
 import importlib
 
 import numpy as np
@@ -45,6 +47,11 @@ def lsb_report(a, b):
     return int(d.max()), float((d == 0).mean()), float((d == 1).mean()), psnr
 
 
+# (w, h): bar.  Measured (largest over flow0..3): 64x64 4.05e-6, 160x96 7.87e-6
+STAGE_FLOW_BAR = {(64, 64): 3.3e-5, (160, 96): 1e-3}
+FLOW_INJECTION_BAR = 3.9e-5      # measured 4.77e-6 (flow3)
+
+
 @pytest.mark.parametrize("w,h", [(64, 64), (160, 96)])
 def test_stage_flows_match_oracle(tap_engines, w, h):
     g, o = tap_engines
@@ -53,7 +60,8 @@ def test_stage_flows_match_oracle(tap_engines, w, h):
         got = g.v4_extract_flow(a, b, 0.5, fi)
         want = o.v4_extract(a, b, 0.5, "flow%d" % fi)
         assert got.shape == want.shape
-        assert np.abs(got - want).max() < 1e-3, fi
+        print("stage flows %dx%d flow%d: max |got - oracle| = %.3e" % (w, h, fi, np.abs(got - want).max()))
+        assert np.abs(got - want).max() < STAGE_FLOW_BAR[(w, h)], fi
 
 
 def test_flow_injection_matches_oracle(tap_engines):
@@ -65,7 +73,8 @@ def test_flow_injection_matches_oracle(tap_engines):
     for fi in (1, 2, 3):
         got = g.v4_extract_flow(a, b, 0.4, fi, inject=inj[:fi])
         want = o.v4_extract(a, b, 0.4, "flow%d" % fi, flows=inj[:fi])
-        assert np.abs(got - want).max() < 1e-3, fi
+        print("flow injection flow%d: max |got - oracle| = %.3e" % (fi, np.abs(got - want).max()))
+        assert np.abs(got - want).max() < FLOW_INJECTION_BAR, fi
 
 
 @pytest.mark.parametrize("w,h,t,seed", [(640, 360, 0.5, 1000), (256, 192, 0.125, 1001), (100, 60, 0.7, 1002), (33, 47, 0.9, 1003)])

@@ -14,7 +14,9 @@ from oracle import pyoracle
 from tools import gen_frames
 from torch_graph import TorchNet
 
-torch.set_num_threads(max(1, os.cpu_count() or 1))
+# No torch.set_num_threads(os.cpu_count()) here: the setting is process-wide and this module is imported by every session that collects tests/, os.cpu_count()
+# counts the whole machine also where the job may use 16 CPUs of it, and an oversubscribed pool made every later torch call of the session 20 x and more slower
+# (the CPU models in tests/test_gpu_fastprec.py and tests/test_gpu_s16_ends.py).  torch's default honours OMP_NUM_THREADS and the cores it may use.
 
 
 def chw(img_u8, wp, hp):
