@@ -309,6 +309,22 @@ __device__ __forceinline__ void flow_upsampled_cells(const float* p00, const flo
     um = RIFE_UP(m00, m01, m10, m11);
 }
 #undef RIFE_UP
+// RIFE_UP in its two stages, for a caller whose pixels share a column and so the horizontal stage (k_flow_cascade): flow_cell_row is (c0 * a0 + c1 * a1) of
+// the five channels of the records p, p + 8; flow_cell_rows_blend is hA * b0 + hB * b1 of the cell rows (sy, sy + 1).  The sub-expressions of RIFE_UP in its
+// order: the bits of flow_upsampled_cells.
+struct FlowCellRow { float4 q; float m; };
+__device__ __forceinline__ FlowCellRow flow_cell_row(const float* p, float a0, float a1) {
+    const float4 q0 = *reinterpret_cast<const float4*>(p), q1 = *reinterpret_cast<const float4*>(p + 8);
+    const float m0 = p[4], m1 = p[12];
+    FlowCellRow h;
+    h.q = make_float4(q0.x * a0 + q1.x * a1, q0.y * a0 + q1.y * a1, q0.z * a0 + q1.z * a1, q0.w * a0 + q1.w * a1);
+    h.m = m0 * a0 + m1 * a1;
+    return h;
+}
+__device__ __forceinline__ void flow_cell_rows_blend(const FlowCellRow& hA, const FlowCellRow& hB, float b0, float b1, float4& u, float& um) {
+    u = make_float4(hA.q.x * b0 + hB.q.x * b1, hA.q.y * b0 + hB.q.y * b1, hA.q.z * b0 + hB.q.z * b1, hA.q.w * b0 + hB.q.w * b1);
+    um = hA.m * b0 + hB.m * b1;
+}
 // the FIRST update (after block 0): F = u[0:4] * S, M = u[4] (k_flow_update<S, true>)
 template <int S>
 __device__ __forceinline__ void flow_first_of(const float4 u, const float um, float4& f, float& m) {

@@ -13,8 +13,9 @@
 //   stem 0   waves 4-7: the two new half-resolution rows x two 32-pixel tiles, 18 MFMAs each (weights in registers) -> bias, LeakyReLU, {hi, lo}
 //            -> LDS ring B (3 row slots).
 //   stem 1   waves 0-3: output block n = wave & 1 (32 of the 64 channels) x K chunk wave >> 1 (16 of the 32 input channels), 18 MFMAs each on
-//            9 register-resident weight fragments; the two K partial sums meet through 8 KB of LDS, waves 0-1 finish (bias, LeakyReLU) and store
-//            S16 entries (conv_t64.h) - 992 contiguous bytes per plane and instruction.
+//            9 register-resident weight fragments; the two K partial sums meet through 8 KB of LDS: every wave hands over the half of its sums
+//            the partner finishes and finishes the other half (bias, LeakyReLU) - waves 0-1 the first 16 bytes of their lanes' S16 entries
+//            (conv_t64.h), waves 2-3 the second 16 - and stores them, one 16-byte piece per lane and plane.
 // Three barriers per step; every wave runs the same loop (wave-uniform role tests), so the barrier counts cannot diverge.  The first step of a
 // strip (and of a workgroup's range) needs three more input rows and one more half-resolution row: a blocking "pre-step".
 // Arithmetic: the block input is assemble_pixel<1>'s bit for bit; stem 0 accumulates in stem0_fused_kernel's order (bit-identical values before
@@ -77,12 +78,20 @@ struct SrsTaps { WarpLoads a, b; };
 #define SRS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // 8-byte global store the compiler does not see (tail_rs.h, trs_store_dword: a store the compiler knows to be in flight turns its next wait for
-// a loaded value into vmcnt(0), which drains the prefetched F, M and taps of waves 0-1 every step)
+// a loaded value into vmcnt(0), which drains the prefetched F, M and taps of the storing waves every step)
 __device__ __forceinline__ void srs_store_b64(unsigned char* base, unsigned off, f16x4 v) {
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     u32x2 d;
     __builtin_memcpy(&d, &v, 8);
     asm volatile("global_store_dwordx2 %0, %1, %2" :: "v"(off), "v"(d), "s"(base) : "memory");
+}
+// the same with 16 bytes.  The string ends with `s_nop 1`: the hardware wants two wait states between a store of more than 8 bytes and the next VALU write
+// of its data registers (what the compiler emits after a global_store_dwordx4 it sees); it does not look into the string, so the pad stands inside it.
+__device__ __forceinline__ void srs_store_b128(unsigned char* base, unsigned off, f16x8 v) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 d;
+    __builtin_memcpy(&d, &v, 16);
+    asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" :: "v"(off), "v"(d), "s"(base) : "memory");
 }
 
 // D = 10: the frames are 10:10:10 dwords (elementwise.h unpack_rgb<10>); nothing else differs.
@@ -262,31 +271,32 @@ __global__ __launch_bounds__(SRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
     if (has_next) { fresh_next = nxt.advance(a.Hq); fm_next = load_fm(nxt.strip, 4 * nxt.q); }
     SRS_SYNC();
 
-    // waves 0-1: output row q of the strip: own K partial sum + the partner's (LDS), bias, LeakyReLU, {hi, lo}, S16 entries.  A lane holds
-    // channels 32 n + 16 half .. + 15 of pixel ox = the pixel's entry of chunk 2 n + half: four 8-byte pieces per plane.
+    // waves 0-3: output row q of the strip.  A lane holds channels 32 n + 16 half .. + 15 of pixel ox = the pixel's entry of chunk 2 n + half, as four quads of
+    // 8 bytes per plane; the wave of K chunk ck finishes the quads 2 ck, 2 ck + 1 (`own`: its partial sums of them; the partner's come from LDS): (K chunk 0 +
+    // K chunk 1) + bias - on waves 2-3 with the own sum as the right-hand operand, the same bits - LeakyReLU, {hi, lo}, one 16-byte piece per plane.
     // (Measured and dropped: deferring this to the top of the next iteration, where these waves idle behind the stem-0 phase - 234 vs 227-231 us.)
-    auto finish_row = [&](const f32x16& acc, int strip, int q, const int half, const int li, const int lane) {
-        const int n = wv;
-        const f32x4* const sd = reinterpret_cast<const f32x4*>(ldsb + SRS_LDS_STG + n * 4096 + lane * 16);
+    auto finish_row = [&](const f32x4 (&own)[2], int strip, int q, const int half, const int li, const int lane) {
+        const int n = wv & 1, ck = wv >> 1;
+        const f32x4* const sd = reinterpret_cast<const f32x4*>(ldsb + SRS_LDS_STG + n * 4096 + 2 * ck * 1024 + lane * 16);
         const int ox = SRS_SW * strip + li;
         bool pok = li < SRS_SW && ox < a.Wq;
-        const unsigned o = (unsigned)(2 * half + 4 * n) * a.plane + (unsigned)((q + 1) * a.pitch + ox + 1) * 32u;      // S16 tensors stay below 4 GB (block_on_s16)
+        const unsigned o = (unsigned)(2 * half + 4 * n) * a.plane + (unsigned)((q + 1) * a.pitch + ox + 1) * 32u + 16u * ck;      // S16 tensors stay below 4 GB (block_on_s16)
+        f16x8 hi8, lo8;
 #pragma unroll
-        for (int qd = 0; qd < 4; qd++) {
-            const f32x4 p = sd[qd * 64];
-            const f32x4 b4 = *reinterpret_cast<const f32x4*>(lbs + 64 + n * 32 + 16 * half + 4 * qd);
-            const f32x4 s4 = *reinterpret_cast<const f32x4*>(lbs + 128 + n * 32 + 16 * half + 4 * qd);
-            f16x4 hi4, lo4;
+        for (int j = 0; j < 2; j++) {
+            const f32x4 p = sd[j * 64];
+            const f32x4 b4 = *reinterpret_cast<const f32x4*>(lbs + 64 + n * 32 + 16 * half + 8 * ck + 4 * j);
+            const f32x4 s4 = *reinterpret_cast<const f32x4*>(lbs + 128 + n * 32 + 16 * half + 8 * ck + 4 * j);
 #pragma unroll
             for (int kk = 0; kk < 4; kk++) {
-                const float y = (acc[4 * qd + kk] + p[kk]) + b4[kk];
+                const float y = (own[j][kk] + p[kk]) + b4[kk];
                 const float v = y < 0.f ? y * s4[kk] : y;
                 const _Float16 hh = (_Float16)v;
-                hi4[kk] = hh; lo4[kk] = (_Float16)(v - (float)hh);
+                hi8[4 * j + kk] = hh; lo8[4 * j + kk] = (_Float16)(v - (float)hh);
             }
             if (RIFE_ABL(TAG & SRS_NOSTORE)) pok = pok && p[0] == 123.456f;
-            if (pok) { srs_store_b64(a.out, o + 8u * qd, hi4); srs_store_b64(a.out, o + a.plane + 8u * qd, lo4); }
         }
+        if (pok) { srs_store_b128(a.out, o, hi8); srs_store_b128(a.out, o + a.plane, lo8); }
     };
 
     long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
@@ -310,8 +320,9 @@ __global__ __launch_bounds__(SRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
         SRS_SYNC();
         SRS_STAMP(2)                                                     // barrier
 
-        f32x16 acc;
+        f32x4 own[2];                                                    // stem-1 waves: the partial sums of the two quads this wave finishes
         if (wv < 4) {
+            f32x16 acc;
             const int ck = wv >> 1, n = wv & 1;
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[r] = 0.f;
@@ -339,10 +350,14 @@ __global__ __launch_bounds__(SRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
                 } else acc[t] += (float)ah[t % 3][0] + (float)al[t % 3][1] + (float)Wf[t][2];
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (ck == 1) {
-                f32x4* const sd = reinterpret_cast<f32x4*>(ldsb + SRS_LDS_STG + n * 4096 + ln * 16);
+            // K chunk 0 keeps the quads 0, 1 and hands over 2, 3; K chunk 1 the other way round: the same 8 KB, written by four waves
+            f32x4* const sd = reinterpret_cast<f32x4*>(ldsb + SRS_LDS_STG + n * 4096 + ln * 16);
 #pragma unroll
-                for (int q = 0; q < 4; q++) sd[q * 64] = f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
+            for (int j = 0; j < 2; j++) {
+                const f32x4 lo = f32x4{acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]};
+                const f32x4 hi = f32x4{acc[8 + 4 * j], acc[8 + 4 * j + 1], acc[8 + 4 * j + 2], acc[8 + 4 * j + 3]};
+                own[j] = ck == 0 ? lo : hi;
+                sd[(ck == 0 ? 2 + j : j) * 64] = ck == 0 ? hi : lo;
             }
         }
         // waves 4-7 are done with their matrix work: they finish their pixel of the next step while waves 0-3 run stem 1 (ring A's rows of step
@@ -353,12 +368,12 @@ __global__ __launch_bounds__(SRS_NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))
         SRS_STAMP(4)                                                     // early gather finish (waves 4-7)
         SRS_SYNC();
         SRS_STAMP(5)                                                     // barrier
-        if (wv < 2) finish_row(acc, cur.strip, cur.q, hf, l32, ln);
+        if (wv < 4) finish_row(own, cur.strip, cur.q, hf, l32, ln);
         if (has_next) {
             if (fresh_next) prestep(nxt);
             if (wv < 4 || fresh_next) finish(nxt.strip, 4 * nxt.q, fm_next, tp_next, 4 * SRS_AW);
         }
-        SRS_STAMP(6)                                                     // combine, gather finish (waves 0-3), stores
+        SRS_STAMP(6)                                                     // combine and stores, gather finish (waves 0-3)
         SRS_SYNC();
         SRS_STAMP(7)                                                     // barrier
         cur = nxt; nxt = nn; fm_next = fm_nn; has_next = has_nn; fresh_next = fresh_nn;
