@@ -110,6 +110,21 @@ int rife_hip_op_stem1_s16(int gpuid, int C, int Ht, int Wt, const float* x_chw, 
  * bias [24].  out8hw: 8 x 4 Ht x 4 Wt planar; it is uploaded into the device flow tensor before the launch and all 8 planes come back - the kernel writes
  * planes 0 - 5 and must leave 6 and 7 alone. */
 int rife_hip_op_head_ps(int gpuid, int C, int Ht, int Wt, int s16, const void* input, const float* weight, const float* bias, float* out8hw);
+/* op_tail: the kernels that read the LAST trunk tensor of block 3 and write the quantised frame, one launch of the kernel under test per call.  kernel =
+ * RIFE_HIP_TAIL_RS: launch_tail_rs (tail_rs_kernel<0, PX>); RIFE_HIP_TAIL_HEAD_S16: launch_conv with the fused tail and the S16 geometry (head_h2_kernel<EPI_FINAL,
+ * true, PX>); RIFE_HIP_TAIL_HEAD_F32: the same on an fp32 tensor (head_h2_kernel<EPI_FINAL, false, PX>); RIFE_HIP_TAIL_UNFUSED: launch_conv with EPI_DECONV_PS into a
+ * flow tensor, then k_final / k_final_px<PX>, as a pass launches them when the tail is not fused.  pixfmt: RIFE_HIP_PIX_RGB8, RGB10_U16, A2B10G10R10 or RGBA8.
+ * Frame w x h, padded to wp x hp (32n); C = 64 and the trunk is hp / 4 x wp / 4.  trunk: the raw S16 tensor of op_s16_geom(64, hp / 4, wp / 4), for
+ * RIFE_HIP_TAIL_HEAD_F32 64 x hp / 4 x wp / 4 fp32 (read as NHWC).  weight [24][64][4][4] (exactly fp16), bias [24]; F [hp][wp][4] and M [hp][wp]: the running flow
+ * and mask logit before block 3's update; img0, img1: the resident frames, hp x wp dwords (depth 8: R | G << 8 | B << 16 | A << 24, depth 10: R | G << 10 | B << 20).
+ * cus > 0: persistent grids sized for that many compute units during the call (0 = the chip), as in rife_hip_op_trunk.  out: RIFE_HIP_TAIL_GUARD bytes, the frame
+ * (w x h pixels of 3, 6, 4 or 4 bytes), RIFE_HIP_TAIL_GUARD bytes; uploaded as given, the launch writes at the frame's offset, the whole buffer comes back.
+ * A null argument, a frame of 2^27 padded pixels or more, an unknown kernel or pixfmt, weights that are not fp16, and RIFE_HIP_TAIL_RS where the product would
+ * not run that kernel on this head (RIFE_HIP_TAIL_RS=0, RIFE_HIP_T64=0, RIFE_HIP_TRUNK=f32) return -RIFE_HIP_EINVAL before anything is uploaded. */
+enum { RIFE_HIP_TAIL_RS = 0, RIFE_HIP_TAIL_HEAD_S16 = 1, RIFE_HIP_TAIL_HEAD_F32 = 2, RIFE_HIP_TAIL_UNFUSED = 3 };
+enum { RIFE_HIP_TAIL_GUARD = 256 };
+int rife_hip_op_tail(int gpuid, int kernel, int pixfmt, int w, int h, const void* trunk, const float* weight, const float* bias, const float* F, const float* M,
+                     const uint32_t* img0, const uint32_t* img1, int cus, void* out);
 
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */

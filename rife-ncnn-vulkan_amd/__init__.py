@@ -57,7 +57,10 @@ ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
-                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps"]
+                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail"]
+# rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
+TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
+TAIL_GUARD = 256
 # rife_hip_op_trunk: which S16 trunk kernel (include/rife_hip_test.h RIFE_HIP_TRUNK_*)
 TRUNK_T64, TRUNK_RS, TRUNK_RS2, TRUNK_ROW, TRUNK_KS = 0, 1, 2, 3, 4
 EINVAL = 1      # RIFE_HIP_EINVAL: calls return its negative
@@ -152,6 +155,7 @@ def _load(path, with_test_surface):
         L.rife_hip_op_trunk_prec.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, ci]
         L.rife_hip_op_stem1_s16.argtypes = [ci, ci, ci, ci, vp, vp, vp, cf, vp]
         L.rife_hip_op_head_ps.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp]
+        L.rife_hip_op_tail.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
     return L
 
 
@@ -893,6 +897,30 @@ def op_head_ps(C, Ht, Wt, x, weight, bias, out8, gpuid=0):
         raise ValueError("out8 must be (8, 4 Ht, 4 Wt)")
     _check(testlib().rife_hip_op_head_ps(gpuid, int(C), int(Ht), int(Wt), int(s16), _p(x), _p(weight), _p(bias), _p(out)), "op_head_ps", testlib())
     return out
+
+
+def op_tail(kernel, pixfmt, w, h, trunk, weight, bias, F, M, img0, img1, out, cus=0, gpuid=0):
+    """One of the kernels that write the quantised frame from block 3's last trunk tensor (kernel = TAIL_RS .. TAIL_UNFUSED), alone.  trunk: the raw S16 tensor
+    (uint8) of a 64 x hp / 4 x wp / 4 trunk, for TAIL_HEAD_F32 (64, hp / 4, wp / 4) fp32; weight (24, 64, 4, 4), bias (24); F (hp, wp, 4), M (hp, wp) fp32; img0, img1
+    (hp, wp) uint32 resident frames; out: uint8, TAIL_GUARD + frame bytes + TAIL_GUARD, goes to the device as given.  Returns the whole buffer after the launch as a
+    new array."""
+    wp, hp = (w + 31) // 32 * 32, (h + 31) // 32 * 32
+    f32 = kernel == TAIL_HEAD_F32
+    trunk = np.ascontiguousarray(trunk, np.float32) if f32 else np.ascontiguousarray(trunk, np.uint8).reshape(-1)
+    weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32)
+    F = np.ascontiguousarray(F, np.float32); M = np.ascontiguousarray(M, np.float32)
+    img0 = np.ascontiguousarray(img0, np.uint32); img1 = np.ascontiguousarray(img1, np.uint32)
+    if weight.size != 24 * 64 * 16 or bias.size != 24 or F.shape != (hp, wp, 4) or M.shape != (hp, wp) or img0.shape != (hp, wp) or img1.shape != (hp, wp):
+        raise ValueError("weight (24, 64, 4, 4), bias (24), F (hp, wp, 4), M (hp, wp) and two (hp, wp) uint32 frames")
+    if trunk.size != (64 * (hp // 4) * (wp // 4) if f32 else op_s16_geom(64, hp // 4, wp // 4)[3]):
+        raise ValueError("the trunk of this frame is 64 x %d x %d" % (hp // 4, wp // 4))
+    bpp = {PIX_RGB8: 3, PIX_RGB10_U16: 6, PIX_A2B10G10R10: 4, PIX_RGBA8: 4}.get(pixfmt)
+    buf = np.array(out, np.uint8).reshape(-1)          # a copy: the call writes into it
+    if bpp is not None and buf.size != 2 * TAIL_GUARD + w * h * bpp:
+        raise ValueError("out must hold %d bytes" % (2 * TAIL_GUARD + w * h * bpp))
+    _check(testlib().rife_hip_op_tail(gpuid, int(kernel), int(pixfmt), int(w), int(h), _p(trunk), _p(weight), _p(bias), _p(F), _p(M), _p(img0), _p(img1), int(cus),
+                                      _p(buf)), "op_tail", testlib())
+    return buf
 
 
 def op_yuv_to_rgb10(buf, w, h, pixfmt, gpuid=0):

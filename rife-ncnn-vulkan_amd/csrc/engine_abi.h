@@ -1560,6 +1560,87 @@ int rife_hip_op_head_ps(int gpuid, int C, int Ht, int Wt, int s16, const void* i
     return rc;
 }
 
+// ---- the fused tails alone (tests/test_gpu_tail_parity.py): the kernels that read the last S16 trunk tensor of block 3 and write the quantised frame, one launch
+// each through the product's layer upload (the flags rife_hip_load sets for head_b3) and the product's launchers; the unfused pair is the two launches of run_v4 ----
+int rife_hip_op_tail(int gpuid, int kernel, int pixfmt, int w, int h, const void* trunk, const float* weight, const float* bias, const float* F, const float* M,
+                     const uint32_t* img0, const uint32_t* img1, int cus, void* out) {
+    int rc;
+    constexpr int C = 64;
+    if (!trunk || !weight || !bias || !F || !M || !img0 || !img1 || !out) return fail(RIFE_HIP_EINVAL, "op_tail: null argument");
+    if (kernel < RIFE_HIP_TAIL_RS || kernel > RIFE_HIP_TAIL_UNFUSED) return fail(RIFE_HIP_EINVAL, "op_tail: unknown kernel");
+    if (pixfmt != RIFE_HIP_PIX_RGB8 && pixfmt != RIFE_HIP_PIX_RGB10_U16 && pixfmt != RIFE_HIP_PIX_A2B10G10R10 && pixfmt != RIFE_HIP_PIX_RGBA8)
+        return fail(RIFE_HIP_EINVAL, "op_tail: one of the four packed RGB formats");
+    if (w <= 0 || h <= 0 || cus < 0) return fail(RIFE_HIP_EINVAL, "op_tail: a frame size and a CU budget >= 0");
+    const long long wpl = ((long long)w + 31) / 32 * 32, hpl = ((long long)h + 31) / 32 * 32;
+    if (wpl * hpl >= (1ll << 27)) return fail(RIFE_HIP_EINVAL, "op_tail: frames stay below 2^27 pixels (the kernels address F and the frame with 32-bit byte offsets)");
+    const int wp = (int)wpl, hp = (int)hpl, Hq = hp / 4, Wq = wp / 4;
+    size_t bytes = 0;
+    if ((rc = rife_hip_op_s16_geom(C, Hq, Wq, nullptr, nullptr, nullptr, &bytes))) return rc;
+    if (!all_fp16(weight, (size_t)24 * C * 16)) return fail(RIFE_HIP_EINVAL, "op_tail: the split-f16 head needs weights that are exactly fp16");
+    // run_block_convs gives block 3's head to tail_rs_kernel only on the S16 path of the split-f16 trunk and with the kernel switched on
+    const Switches sw = read_switches();                                 // engine scope in the product (rife_hip_create): per call here, which has no engine
+    if (kernel == RIFE_HIP_TAIL_RS && !(sw.tail_rs && sw.t64 && trunk_h2()))
+        return fail(RIFE_HIP_EINVAL, "op_tail: the product would not run tail_rs_kernel on this head (RIFE_HIP_TAIL_RS=0, RIFE_HIP_T64=0 or RIFE_HIP_TRUNK=f32)");
+    if ((rc = check_device(gpuid))) return rc;
+    struct BudgetGuard { int keep; ~BudgetGuard() { tl_cu_budget = keep; } } budget_guard{tl_cu_budget};
+    tl_cu_budget = cus;
+
+    rife_hip::Block B;
+    ConvLayer& L = B.head;
+    float *d_chw = nullptr, *d_flow = nullptr, *d_F = nullptr, *d_M = nullptr; uint32_t *d_i0 = nullptr, *d_i1 = nullptr; unsigned char *d_in = nullptr, *d_out = nullptr;
+    auto cleanup = [&]() {
+        (void)hipFree(d_chw); (void)hipFree(d_flow); (void)hipFree(d_F); (void)hipFree(d_M); (void)hipFree(d_i0); (void)hipFree(d_i1); (void)hipFree(d_in); (void)hipFree(d_out);
+        free_layer(L);
+    };
+    B.c = C; B.scale = 1;
+    L.cin = C; L.cout = 24; L.stride = 1; L.deconv = true; L.epi = EPI_DECONV_PS; L.cls = "head"; L.tag = 0; L.skip = false;      // setup() of rife_hip_load for head_b3
+    L.want_t64 = false; L.want_s16out = false;
+    if ((rc = upload_layer(L, weight, bias, nullptr, 1.0f))) { cleanup(); return rc; }
+    if (!L.d_wh) { cleanup(); return fail(RIFE_HIP_EINVAL, "op_tail: the layer upload made no split-f16 weight image"); }
+    const S16Geom G(Hq, Wq);
+    const bool s16 = kernel != RIFE_HIP_TAIL_HEAD_F32;
+    const size_t npix = (size_t)wp * hp, nin = (size_t)C * Hq * Wq, nx = s16 ? bytes : nin * 4;
+    const size_t nframe = frame_bytes(w, h, pixfmt), nout = nframe + 2 * (size_t)RIFE_HIP_TAIL_GUARD;
+    hipError_t e = hipMalloc(&d_in, nx);
+    if (e == hipSuccess) e = hipMalloc(&d_F, npix * 16);
+    if (e == hipSuccess) e = hipMalloc(&d_M, npix * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_i0, npix * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_i1, npix * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_out, nout);
+    if (e == hipSuccess && !s16) e = hipMalloc(&d_chw, nin * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_flow, npix * 8 * 4);      // the fused kernels get the flow tensor the product hands them and leave it alone
+    if (e == hipSuccess) e = hipMemcpy(d_F, F, npix * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_M, M, npix * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_i0, img0, npix * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_i1, img1, npix * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_out, out, nout, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_flow, 0xff, npix * 8 * 4);      // NaN: k_final reads what the head wrote, nothing else
+    if (e == hipSuccess) e = hipMemcpy(s16 ? reinterpret_cast<void*>(d_in) : reinterpret_cast<void*>(d_chw), trunk, nx, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cleanup(); return fail(RIFE_HIP_EHIP, std::string("op_tail: ") + hipGetErrorString(e)); }
+    if (!s16) hipLaunchKernelGGL(k_chw_to_nhwc, grid2d(Wq, Hq), dim3(256), 0, 0, d_chw, reinterpret_cast<float*>(d_in), C, Hq, Wq, C);
+    uint8_t* const frame = d_out + RIFE_HIP_TAIL_GUARD;
+    const FinalArgs fin{d_i0, d_i1, reinterpret_cast<const float4*>(d_F), d_M, frame, w, h, wp, hp, pixfmt};
+    const TensorView x{reinterpret_cast<float*>(d_in), C, 0};
+    switch (kernel) {
+        case RIFE_HIP_TAIL_RS: rc = launch_tail_rs(B, d_in, Hq, Wq, fin, 0); break;
+        case RIFE_HIP_TAIL_HEAD_S16: rc = launch_conv(L, x, Hq, Wq, {d_flow, 8, 0}, nullptr, 0, &fin, G.pitch, G.plane()); break;
+        case RIFE_HIP_TAIL_HEAD_F32: rc = launch_conv(L, x, Hq, Wq, {d_flow, 8, 0}, nullptr, 0, &fin); break;
+        default:
+            rc = launch_conv(L, x, Hq, Wq, {d_flow, 8, 0}, nullptr, 0, nullptr, G.pitch, G.plane());
+            if (rc) break;
+            if (pixfmt == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(w, h), dim3(256), 0, 0, d_i0, d_i1, fin.F, d_M, d_flow, frame, w, h, wp, hp);
+            else if (pixfmt == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(w, h), dim3(256), 0, 0, d_i0, d_i1, fin.F, d_M, d_flow, frame, w, h, wp, hp);
+            else if (pixfmt == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(w, h), dim3(256), 0, 0, d_i0, d_i1, fin.F, d_M, d_flow, frame, w, h, wp, hp);
+            else hipLaunchKernelGGL(k_final, grid2d(w, h), dim3(256), 0, 0, d_i0, d_i1, fin.F, d_M, d_flow, frame, w, h, wp, hp);
+            break;
+    }
+    e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost);
+    if (!rc && e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("op_tail: ") + hipGetErrorString(e));
+    cleanup();
+    return rc;
+}
+
 #endif  // RIFE_HIP_TEST_BUILD
 
 #ifdef RIFE_HIP_BENCH_BUILD
