@@ -292,6 +292,46 @@ enum { RIFE_HIP_PRECISION_FULL = 0, RIFE_HIP_PRECISION_FAST = 1 };
 int rife_hip_set_precision(rife_hip_t* r, int precision);
 int rife_hip_precision(const rife_hip_t* r);                /* FULL before load and for a null engine */
 
+/* ---- motion export: the final flows and the blend mask, with the frame (absent in the reference, whose flow and mask blobs never leave the Extractor) ----------------
+ * Every synthesised pixel has a displacement into frame 0, one into frame 1 and a blend weight; the kernels that finish the frame hold them in registers and a motion
+ * call stores them next to the frame: an occlusion / confidence map, motion vectors for an encoder, a motion-blur pass or a temporal denoiser, cut detection without
+ * a second optical-flow pass.  What to do with them is the caller's policy.
+ *   flow   the graph's final flow tensor, the blob that feeds the last two rife.Warp layers (`327` of the stock models/rife-v4.6/flownet.param: F + flow3[0:4]): the
+ *          output pixel (x, y) was sampled from frame 0 at (x + dx0, y + dy0) and from frame 1 at (x + dx1, y + dy1), in pixels of the full-resolution frame, as
+ *          rife.Warp reads them (src/warp.cpp:96-168).  h rows of w pixels of 4 samples dx0, dy0, dx1, dy1.
+ *   mask   the Sigmoid output (blob `332`): the weight of frame 0's warp; frame 1's is 1 - mask.  h rows of w samples.
+ * Both are cropped to w x h and are THE values the frame of the same call was finished from, not a recomputation; at flow scale 2 they are the flow and sigmoid(mask
+ * logit) after block 3's update at full resolution.  RIFE_HIP_MOTION_F16 is the F32 sample rounded to nearest even.  The frame of a motion call is byte for byte the
+ * frame of the call without it (the same kernel code on the same grids, plus the stores), in every _px format: the motion does not depend on the frame format.
+ * flow or mask may be NULL ("not wanted"); both NULL is -RIFE_HIP_EINVAL.  At timestep 0 / 1 the engine returns a copy of a frame without running the network; the
+ * motion of such a call is defined as flow 0 and mask 1 - timestep.
+ * Rules (rife_hip_motion_check states them, every motion call repeats them before it touches anything; a violation is -RIFE_HIP_EINVAL with the fault named in the
+ * message): a known format; each pitch at least the row bytes; flow and its pitch aligned to the pixel (16 bytes for F32, 8 for F16), mask and its pitch to its element
+ * (4 / 2); h * pitch < 2^32.  Rows may be padded: the bytes between the rows and around the buffers are not written.
+ * Scope: model family rife-v4.6, plain mode, flow scale 1 and 2, precision full and fast, every _px format and frame size.  Any other family (rife-v4 4.0 included) or
+ * mode (-x, -z, -u) returns -RIFE_HIP_ENOSYS with a message that names it and the words "motion export", and leaves every output untouched.  The opt-in graph replay
+ * does not apply to motion calls.  Out of scope: the batch calls, image (strided-frame) calls with motion, lower-resolution or block motion, the command line (no file
+ * format it writes holds this data). */
+#define RIFE_HIP_MOTION_F32 0   /* IEEE binary32 samples */
+#define RIFE_HIP_MOTION_F16 1   /* IEEE binary16: the F32 sample rounded to nearest-even */
+typedef struct rife_hip_motion {
+    void*  flow;  size_t flow_pitch;   /* h rows of w pixels x 4 samples: dx0, dy0, dx1, dy1; pitch in BYTES */
+    void*  mask;  size_t mask_pitch;   /* h rows of w samples */
+    int    format;
+} rife_hip_motion_t;
+int rife_hip_motion_check(const rife_hip_motion_t* m, int w, int h);          /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
+/* host frames and host motion buffers: the motion is downloaded into the caller's pitched buffers from a tight device buffer the workspace allocates at its first
+ * motion call (a process that never asks pays no memory) */
+int rife_hip_process_motion(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt,
+                            const rife_hip_motion_t* host_motion);
+/* device frames and device motion buffers, written in place by the kernel that finishes the frame; stream semantics as for the device _px call (NULL = the engine's
+ * own stream, synchronised before returning) */
+int rife_hip_process_device_motion(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt,
+                                   const rife_hip_motion_t* device_motion, void* hip_stream);
+/* stream mode: resident frames, the result and its motion into host memory */
+int rife_hip_process_frames_motion(const rife_hip_t* r, const rife_hip_frame_t* frame0, const rife_hip_frame_t* frame1, float timestep, void* out,
+                                   const rife_hip_motion_t* host_motion);
+
 const char* rife_hip_last_error(void);
 
 /* ---- measurement hooks (bench.py / profiles) ---------------------------------------------------------------

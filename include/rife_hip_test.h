@@ -126,6 +126,14 @@ enum { RIFE_HIP_TAIL_GUARD = 256 };
 int rife_hip_op_tail(int gpuid, int kernel, int pixfmt, int w, int h, const void* trunk, const float* weight, const float* bias, const float* F, const float* M,
                      const uint32_t* img0, const uint32_t* img1, int cus, void* out);
 
+/* op_tail_motion: rife_hip_op_tail with the motion export (include/rife_hip.h rife_hip_motion_t) - ONE launch of the motion form of the kernel under test
+ * (tail_rs_motion_kernel, head_h2_motion_kernel; the unfused pair: the head as before, then k_final_motion<PX>), which writes the frame AND each pixel's final flow and blend weight.  motion_format:
+ * RIFE_HIP_MOTION_F32 / _F16.  flow, mask: HOST buffers of RIFE_HIP_TAIL_GUARD bytes, h rows of flow_pitch / mask_pitch bytes, RIFE_HIP_TAIL_GUARD bytes; uploaded as
+ * given, the launch writes at the guard's offset, the whole buffers come back (guards and the gaps of padded rows with them).  Either may be null (not wanted); both null,
+ * an unknown format and a pitch the product's motion calls refuse are -RIFE_HIP_EINVAL before anything is uploaded.  Everything else as in rife_hip_op_tail. */
+int rife_hip_op_tail_motion(int gpuid, int kernel, int pixfmt, int w, int h, const void* trunk, const float* weight, const float* bias, const float* F, const float* M,
+                            const uint32_t* img0, const uint32_t* img1, int cus, void* out, int motion_format, void* flow, size_t flow_pitch, void* mask, size_t mask_pitch);
+
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */
 int rife_hip_pool_state(const rife_hip_t* r, int* pooled, int* leased, int* high_water);

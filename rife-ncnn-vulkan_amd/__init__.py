@@ -35,6 +35,7 @@ C_ABI_SYMBOLS = [
     "rife_hip_image_check", "rife_hip_image_row_bytes", "rife_hip_process_image", "rife_hip_process_device_image", "rife_hip_frame_upload_image", "rife_hip_process_frames_image",
     "rife_hip_set_flow_scale", "rife_hip_flow_scale",
     "rife_hip_set_precision", "rife_hip_precision",
+    "rife_hip_motion_check", "rife_hip_process_motion", "rife_hip_process_device_motion", "rife_hip_process_frames_motion",
 ]
 # include/rife_hip.h RIFE_HIP_PRECISION_*: FULL = two f16 products per weight tap of the residual trunks (fp32-equivalent), FAST = one, the skip at full precision
 PRECISION_FULL, PRECISION_FAST = 0, 1
@@ -53,11 +54,14 @@ _RGBP_DTYPE = {PIX_RGBP8: np.uint8, PIX_RGBP10: np.uint16, PIX_RGBPH: np.float16
 CSP_BT709, CSP_BT601, CSP_BT2020NCL = 0 << 8, 1 << 8, 2 << 8
 CSP_FULL = 1 << 12
 ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
+# motion export (include/rife_hip.h RIFE_HIP_MOTION_*): the sample type of the flow and mask buffers
+MOTION_F32, MOTION_F16 = 0, 1
+_MOTION_DTYPE = {MOTION_F32: np.float32, MOTION_F16: np.float16}
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
-                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail"]
+                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion"]
 # rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
 TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
 TAIL_GUARD = 256
@@ -69,6 +73,12 @@ EINVAL = 1      # RIFE_HIP_EINVAL: calls return its negative
 class rife_hip_image(ctypes.Structure):
     """rife_hip_image_t of include/rife_hip.h: a frame as a pointer and a pitch in BYTES per plane."""
     _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("pixfmt", ctypes.c_int), ("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_ssize_t * 3)]
+
+
+class rife_hip_motion(ctypes.Structure):
+    """rife_hip_motion_t of include/rife_hip.h: where a motion call puts the final flows (h rows of w pixels of dx0, dy0, dx1, dy1) and the blend mask (h rows of
+    w samples); pitches in BYTES, either pointer may be null (not wanted)."""
+    _fields_ = [("flow", ctypes.c_void_p), ("flow_pitch", ctypes.c_size_t), ("mask", ctypes.c_void_p), ("mask_pitch", ctypes.c_size_t), ("format", ctypes.c_int)]
 
 
 def build(force=False):
@@ -134,6 +144,11 @@ def _load(path, with_test_surface):
     L.rife_hip_flow_scale.argtypes = [vp]
     L.rife_hip_set_precision.argtypes = [vp, ci]
     L.rife_hip_precision.argtypes = [vp]
+    mp = ctypes.POINTER(rife_hip_motion)
+    L.rife_hip_motion_check.argtypes = [mp, ci, ci]
+    L.rife_hip_process_motion.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, mp]
+    L.rife_hip_process_device_motion.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, mp, vp]
+    L.rife_hip_process_frames_motion.argtypes = [vp, vp, vp, cf, vp, mp]
     if with_test_surface:
         L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
         L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
@@ -156,6 +171,7 @@ def _load(path, with_test_surface):
         L.rife_hip_op_stem1_s16.argtypes = [ci, ci, ci, ci, vp, vp, vp, cf, vp]
         L.rife_hip_op_head_ps.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp]
         L.rife_hip_op_tail.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+        L.rife_hip_op_tail_motion.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t]
     return L
 
 
@@ -421,6 +437,41 @@ def _plane_tuple(planes):
     return tuple(planes) if isinstance(planes, np.ndarray) and planes.ndim == 3 else planes
 
 
+def motion_desc(flow=None, mask=None, fmt=MOTION_F32, flow_pitch=0, mask_pitch=0):
+    """A rife_hip_motion from raw addresses (ints; None or 0 = not wanted) and pitches in bytes - device buffers for process_device_motion(), or any of the C calls."""
+    return rife_hip_motion(int(flow) if flow else None, int(flow_pitch), int(mask) if mask else None, int(mask_pitch), int(fmt))
+
+
+def motion_check(m, w, h):
+    """rife_hip_motion_check (host only): raises RifeError with the fault."""
+    _check(lib().rife_hip_motion_check(ctypes.byref(m), int(w), int(h)), "motion_check")
+
+
+def _motion_host(w, h, dtype, flow, mask):
+    """The descriptor of a host motion call and the arrays it fills.  flow / mask: None = a new (h, w, 4) / (h, w) array of `dtype`; False = not wanted; an array
+    or view of that shape and dtype whose rows are strided but whose pixels are contiguous (row-padded arrays, crops) is written in place, without a copy."""
+    dt = np.dtype(dtype)
+    fmt = {np.dtype(np.float32): MOTION_F32, np.dtype(np.float16): MOTION_F16}.get(dt)
+    if fmt is None:
+        raise ValueError("the motion dtype is np.float32 or np.float16")
+    out = []
+    for a, shape, what in ((flow, (h, w, 4), "flow"), (mask, (h, w), "mask")):
+        if a is None:
+            a = np.empty(shape, dt)
+        elif a is False:
+            out.append(None)
+            continue
+        if not isinstance(a, np.ndarray) or a.shape != shape or a.dtype != dt or not a.flags.writeable or not _rows_strided(a):
+            raise ValueError("%s must be a writable %s array of shape %s whose rows are contiguous" % (what, dt.name, shape))
+        out.append(a)
+    f, m = out
+    if f is None and m is None:
+        raise ValueError("flow and mask are both unwanted")
+    d = motion_desc(f.ctypes.data if f is not None else None, m.ctypes.data if m is not None else None, fmt, _pitch(f) if f is not None else 0, _pitch(m) if m is not None else 0)
+    d._keep = (f, m)
+    return d, f, m
+
+
 class Frame:
     """A frame resident in device memory (rife_hip_frame_t): upload once, use as either side of any number of pairs."""
 
@@ -649,6 +700,50 @@ class RIFE:
             raise ValueError("outimage must be a contiguous (h, w, 3) uint8 array of the frames' size")
         _check(self._L.rife_hip_process_frames(self._h, frame0._f, frame1._f, float(timestep), _p(out)), "process_frames", self._L)
         return out
+
+    def process_motion(self, in0image, in1image, timestep, dtype=np.float32, outimage=None, pixfmt=None, flow=None, mask=None):
+        """process() that also returns the motion the frame was made from (rife-v4.6, plain mode; include/rife_hip.h "motion export"): (frame, flow, mask) with
+        flow (h, w, 4) = dx0, dy0, dx1, dy1 - output pixel (x, y) was sampled from frame 0 at (x + dx0, y + dy0) and from frame 1 at (x + dx1, y + dy1) - and
+        mask (h, w) the weight of frame 0's warp.  dtype: np.float32 or np.float16 (the float32 value rounded to nearest even).  flow= / mask=: arrays to fill (row-padded
+        arrays and views are written in place), or False for "not wanted" (None comes back in its place).  The frame is byte for byte process()'s."""
+        px = _pix_of(in0image, pixfmt)
+        if px is None:
+            a = np.ascontiguousarray(in0image, dtype=np.uint8); b = np.ascontiguousarray(in1image, dtype=np.uint8)
+            if a.ndim != 3 or a.shape[2] != 3 or a.shape != b.shape:
+                raise ValueError("frames must be (h, w, 3) uint8 arrays of equal size")
+            px = PIX_RGB8
+        else:
+            if _pix_of(in1image, px) != px or in1image.shape != in0image.shape:
+                raise ValueError("both frames must have the same pixel format and size")
+            a = np.ascontiguousarray(in0image); b = np.ascontiguousarray(in1image)
+        h, w = a.shape[:2]
+        out = outimage if outimage is not None else np.empty_like(a)
+        if not isinstance(out, np.ndarray) or out.shape != a.shape or out.dtype != a.dtype or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("outimage must be a writable contiguous array of the frames' dtype and shape")
+        d, f, m = _motion_host(w, h, dtype, flow, mask)
+        _check(self._L.rife_hip_process_motion(self._h, _p(a), _p(b), w, h, float(timestep), _p(out), px, ctypes.byref(d)), "process_motion", self._L)
+        return out, f, m
+
+    def process_frames_motion(self, frame0, frame1, timestep, dtype=np.float32, outimage=None, flow=None, mask=None):
+        """process_frames() with the motion: (frame, flow, mask) as process_motion() returns them, between two resident frames of a packed RGB format."""
+        if frame0._f is None or frame1._f is None:
+            raise ValueError("frame was released")
+        if frame0.pixfmt != frame1.pixfmt or frame0.pixfmt not in _PIX_LAYOUT:
+            raise ValueError("two frames of one packed RGB format")
+        dt, _ = _PIX_LAYOUT[frame0.pixfmt]
+        shape = _pix_shape(frame0.pixfmt, frame0.h, frame0.w)
+        out = outimage if outimage is not None else np.empty(shape, dt)
+        if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dt or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("outimage must be a writable contiguous array of the frames' format and size")
+        d, f, m = _motion_host(frame0.w, frame0.h, dtype, flow, mask)
+        _check(self._L.rife_hip_process_frames_motion(self._h, frame0._f, frame1._f, float(timestep), _p(out), ctypes.byref(d)), "process_frames_motion", self._L)
+        return out, f, m
+
+    def process_device_motion(self, d_in0, d_in1, w, h, timestep, d_out, motion, stream=None, pixfmt=PIX_RGB8):
+        """rife_hip_process_device_motion: device pointers (ints) to tight frames of `pixfmt` and a motion_desc() of DEVICE buffers with their pitches, written in
+        place by the kernel that finishes the frame; enqueues on `stream` (hipStream_t as int; None = the engine's own stream, synchronised before returning)."""
+        _check(self._L.rife_hip_process_device_motion(self._h, d_in0, d_in1, int(w), int(h), float(timestep), d_out, int(pixfmt), ctypes.byref(motion), stream),
+               "process_device_motion", self._L)
 
     def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
         """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
@@ -921,6 +1016,32 @@ def op_tail(kernel, pixfmt, w, h, trunk, weight, bias, F, M, img0, img1, out, cu
     _check(testlib().rife_hip_op_tail(gpuid, int(kernel), int(pixfmt), int(w), int(h), _p(trunk), _p(weight), _p(bias), _p(F), _p(M), _p(img0), _p(img1), int(cus),
                                       _p(buf)), "op_tail", testlib())
     return buf
+
+
+def op_tail_motion(kernel, pixfmt, w, h, trunk, weight, bias, F, M, img0, img1, out, fmt=MOTION_F32, flow=None, flow_pitch=0, mask=None, mask_pitch=0, cus=0, gpuid=0):
+    """op_tail() through the motion form of the kernel under test (rife_hip_op_tail_motion).  flow / mask: uint8 buffers of TAIL_GUARD bytes, h rows
+    of flow_pitch / mask_pitch bytes and TAIL_GUARD bytes, uploaded as given (None = not wanted).  Returns (frame buffer, flow buffer, mask buffer), whole, as new arrays."""
+    wp, hp = (w + 31) // 32 * 32, (h + 31) // 32 * 32
+    f32 = kernel == TAIL_HEAD_F32
+    trunk = np.ascontiguousarray(trunk, np.float32) if f32 else np.ascontiguousarray(trunk, np.uint8).reshape(-1)
+    weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32)
+    F = np.ascontiguousarray(F, np.float32); M = np.ascontiguousarray(M, np.float32)
+    img0 = np.ascontiguousarray(img0, np.uint32); img1 = np.ascontiguousarray(img1, np.uint32)
+    if weight.size != 24 * 64 * 16 or bias.size != 24 or F.shape != (hp, wp, 4) or M.shape != (hp, wp) or img0.shape != (hp, wp) or img1.shape != (hp, wp):
+        raise ValueError("weight (24, 64, 4, 4), bias (24), F (hp, wp, 4), M (hp, wp) and two (hp, wp) uint32 frames")
+    if trunk.size != (64 * (hp // 4) * (wp // 4) if f32 else op_s16_geom(64, hp // 4, wp // 4)[3]):
+        raise ValueError("the trunk of this frame is 64 x %d x %d" % (hp // 4, wp // 4))
+    bpp = {PIX_RGB8: 3, PIX_RGB10_U16: 6, PIX_A2B10G10R10: 4, PIX_RGBA8: 4}.get(pixfmt)
+    buf = np.array(out, np.uint8).reshape(-1)          # copies: the call writes into them
+    if bpp is not None and buf.size != 2 * TAIL_GUARD + w * h * bpp:
+        raise ValueError("out must hold %d bytes" % (2 * TAIL_GUARD + w * h * bpp))
+    fb = None if flow is None else np.array(flow, np.uint8).reshape(-1)
+    mb = None if mask is None else np.array(mask, np.uint8).reshape(-1)
+    if (fb is not None and fb.size != 2 * TAIL_GUARD + h * flow_pitch) or (mb is not None and mb.size != 2 * TAIL_GUARD + h * mask_pitch):
+        raise ValueError("a motion buffer holds TAIL_GUARD + h * pitch + TAIL_GUARD bytes")
+    _check(testlib().rife_hip_op_tail_motion(gpuid, int(kernel), int(pixfmt), int(w), int(h), _p(trunk), _p(weight), _p(bias), _p(F), _p(M), _p(img0), _p(img1), int(cus),
+                                             _p(buf), int(fmt), _p(fb), int(flow_pitch), _p(mb), int(mask_pitch)), "op_tail_motion", testlib())
+    return buf, fb, mb
 
 
 def op_yuv_to_rgb10(buf, w, h, pixfmt, gpuid=0):

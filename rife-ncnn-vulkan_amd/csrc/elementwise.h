@@ -554,6 +554,76 @@ __global__ void k_final_scaled(const uint32_t* __restrict__ img0, const uint32_t
     final_tail<PX>(img0, img1, f, mm, out, x, y, w, wp, hp);
 }
 
+// ---- motion export (include/rife_hip.h rife_hip_motion_t): the final flow f (the blob the last two rife.Warp layers read) and the blend weight m (the Sigmoid output)
+// of a pixel, stored by the lane that finishes it.  Pointers null = not wanted; pitches in bytes; offsets are 32-bit (h * pitch < 2^32, motion_check.h).  format is
+// wave-uniform: one branch, no instantiation per format.  Half = round to nearest even (the _Float16 conversion, as planar_rgb.h's).
+// The kernels of a plain call are untouched: a motion call launches a kernel of its own on the same grid (k_final_motion, k_final_scaled_motion here; head_h2.h and
+// tail_rs.h have theirs), which evaluates the plain kernel's expressions in their order and stores f and m on the way.
+struct MotionArgs {
+    uint8_t* flow = nullptr; uint8_t* mask = nullptr;
+    unsigned flow_pitch = 0, mask_pitch = 0;
+    int format = 0;              // RIFE_HIP_MOTION_F32 / _F16
+};
+__device__ __forceinline__ uint2 motion_half4(const float4 f) {
+    const uint32_t a = __builtin_bit_cast(uint16_t, (_Float16)f.x), b = __builtin_bit_cast(uint16_t, (_Float16)f.y);
+    const uint32_t c = __builtin_bit_cast(uint16_t, (_Float16)f.z), d = __builtin_bit_cast(uint16_t, (_Float16)f.w);
+    return make_uint2(a | (b << 16), c | (d << 16));
+}
+__device__ __forceinline__ uint32_t motion_half(const float m) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)m); }
+__device__ __forceinline__ void motion_put_flow(const MotionArgs& mo, int x, int y, const float4 f) {
+    if (!mo.flow) return;
+    if (mo.format == RIFE_HIP_MOTION_F16) *reinterpret_cast<uint2*>(mo.flow + ((unsigned)y * mo.flow_pitch + (unsigned)x * 8u)) = motion_half4(f);
+    else *reinterpret_cast<float4*>(mo.flow + ((unsigned)y * mo.flow_pitch + (unsigned)x * 16u)) = f;
+}
+__device__ __forceinline__ void motion_put_mask(const MotionArgs& mo, int x, int y, const float m) {
+    if (!mo.mask) return;
+    if (mo.format == RIFE_HIP_MOTION_F16) *reinterpret_cast<uint16_t*>(mo.mask + ((unsigned)y * mo.mask_pitch + (unsigned)x * 2u)) = (uint16_t)motion_half(m);
+    else *reinterpret_cast<float*>(mo.mask + ((unsigned)y * mo.mask_pitch + (unsigned)x * 4u)) = m;
+}
+// the pixel's motion, then final_tail: m is final_tail's own expression on the same mm, i.e. the weight the frame is blended with
+template <int PX>
+__device__ __forceinline__ void final_tail_motion(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4 f, const float mm,
+                                                  uint8_t* __restrict__ out, int x, int y, int w, int wp, int hp, const MotionArgs& mo) {
+    motion_put_flow(mo, x, y, f);
+    motion_put_mask(mo, x, y, 1.f / (1.f + expf(-mm)));
+    final_tail<PX>(img0, img1, f, mm, out, x, y, w, wp, hp);
+}
+// k_final / k_final_px<PX> with the motion stores (final_body's expressions)
+template <int PX>
+__global__ void k_final_motion(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F, const float* __restrict__ M,
+                               const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp, MotionArgs mo) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * wp + x;
+    const float* fl = flow3 + i * 8;
+    const float4 d = *reinterpret_cast<const float4*>(fl);
+    float4 f = F[i];
+    f.x = f.x + d.x; f.y = f.y + d.y; f.z = f.z + d.z; f.w = f.w + d.w;
+    const float mm = M[i] + fl[4];
+    final_tail_motion<PX>(img0, img1, f, mm, out, x, y, w, wp, hp, mo);
+}
+// k_final_scaled<PX> with the motion stores: f and mm after flow_accumulate<2>
+template <int PX>
+__global__ void k_final_scaled_motion(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F, const float* __restrict__ M,
+                                      const float* __restrict__ flow3, uint8_t* __restrict__ out, int w, int h, int wp, int hp, MotionArgs mo) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * wp + x;
+    float4 u; float um;
+    flow_upsampled<2>(flow3, wp, hp, x, y, u, um);
+    float4 f = F[i];
+    float mm = M[i];
+    flow_accumulate<2>(u, um, f, mm);
+    final_tail_motion<PX>(img0, img1, f, mm, out, x, y, w, wp, hp, mo);
+}
+// timestep 0 / 1 (the engine returns a copy of a frame, no network pass): flow 0, mask 1 - timestep
+__global__ void k_motion_fill(MotionArgs mo, int w, int h, float m) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w || y >= h) return;
+    motion_put_flow(mo, x, y, make_float4(0.f, 0.f, 0.f, 0.f));
+    motion_put_mask(mo, x, y, m);
+}
+
 // rife-v4 (4.0) tail (models/rife-v4/flownet.param:154-168): F and M are final after the block-3 flow update;
 //   m = sigmoid(M); out = warp(in0,F.xy)*m + warp(in1,F.zw)*(1-m); then the same postproc as k_final.
 __global__ void k_blend_final(const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1, const float4* __restrict__ F,

@@ -42,6 +42,7 @@
 #include "yuv.h"
 #include "planes.h"
 #include "image_check.h"
+#include "motion_check.h"
 #include "elementwise_v2.h"
 #include "stem_fused.h"
 #include "stem_fused_v2.h"

@@ -75,6 +75,7 @@ struct Ctx {
     float4* F2 = nullptr; float* M2 = nullptr;                       // the other pair of buffers for a flow update fused into the next stem (stem_fused.h UPD); F, M are swapped with them
     float4* outf = nullptr;                                          // TTA only: out0 as float, padded
     uint32_t* yuv_rgb = nullptr;                                     // YUV calls only (allocated by the first): the pass's A2B10G10R10 frame, tight w x h in wp x hp dwords; k_postproc_yuv reads it
+    uint8_t *mo_flow = nullptr, *mo_mask = nullptr;                  // host motion calls only (each allocated by the first that wants it): tight w x h x 16 B / w x h x 4 B, the D2H source
     // hipGraph replay of the plain v4 schedule for launch-bound frame sizes: fixed staging buffers (d_in0 / d_in1 / d_out), the
     // timestep in device memory, one warm-up pass (lazy allocations, kernel attributes), then capture once and replay
     float* d_ts = nullptr;

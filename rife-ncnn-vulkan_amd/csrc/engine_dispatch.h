@@ -97,7 +97,8 @@ static int launch_conv_h2s2(const ConvLayer& L, ConvArgs a, unsigned gy, int x_w
 }
 
 // fin: the fused tail (EPI_FINAL: the PixelShuffle head goes on to the output frame, in the format fin->pixfmt names)
-static int launch_head_h2(const ConvLayer& L, ConvArgs a, unsigned gy, TensorView y, const FinalArgs* fin, int s16_pitch, hipStream_t st) {
+// mo (with fin): a motion call - head_h2_motion_kernel, the same body on the same grid, which also stores each pixel's final flow and blend weight
+static int launch_head_h2(const ConvLayer& L, ConvArgs a, unsigned gy, TensorView y, const FinalArgs* fin, int s16_pitch, hipStream_t st, const MotionArgs* mo = nullptr) {
     a.ntiles_xy = a.tiles_x * ((a.Ho + 7) / 8);
     a.nchunks = L.nchunksh;
     a.nz = (L.cout + 31) / 32;
@@ -108,6 +109,13 @@ static int launch_head_h2(const ConvLayer& L, ConvArgs a, unsigned gy, TensorVie
     if (L.epi == EPI_DECONV_PS && (L.cout != 24 || y.ld != 8 || y.coff != 0))
         return fail(RIFE_HIP_EINVAL, "the PixelShuffle head kernel writes the 6-channel flow tensor [4H][4W][8] only");
     if (s16_pitch > 0 && L.epi != EPI_DECONV_PS) return fail(RIFE_HIP_EINVAL, "no S16 variant of this head");
+    if (mo && !(fin && L.epi == EPI_DECONV_PS)) return fail(RIFE_HIP_EINVAL, "motion export needs the fused tail");
+    if (fin && mo)
+        return with_outfmt(fin->pixfmt, [&](auto of) {
+            constexpr int OF = decltype(of)::value;
+            if (s16_pitch > 0) return launch<head_h2_motion_kernel<true, OF>>(what, grid, block, lds, st, a, *fin, *mo);
+            return launch<head_h2_motion_kernel<false, OF>>(what, grid, block, lds, st, a, *fin, *mo);
+        });
     if (fin && L.epi == EPI_DECONV_PS)
         return with_outfmt(fin->pixfmt, [&](auto of) {
             constexpr int OF = decltype(of)::value;
@@ -226,7 +234,8 @@ static int launch_conv_generic(const ConvLayer& L, ConvArgs a, hipStream_t st) {
 // x: NHWC input (H x W), y: output; for deconv layers y has 2H x 2W pixels (or the 4H x 4W flow tensor with EPI_DECONV_PS).
 // s16_pitch > 0: the stride-2 stem writes / the head reads an S16 tensor (conv_t64.h) of that row pitch instead of NHWC fp32
 static int launch_conv(const ConvLayer& L, TensorView x, int H, int W, TensorView y, const TensorView* res, hipStream_t st, const FinalArgs* fin = nullptr,
-                       int s16_pitch = 0, unsigned s16_plane = 0, const float* in1 = nullptr, float* out1 = nullptr, const TensorView* y2 = nullptr) {
+                       int s16_pitch = 0, unsigned s16_plane = 0, const float* in1 = nullptr, float* out1 = nullptr, const TensorView* y2 = nullptr,
+                       const MotionArgs* mo = nullptr) {
     // in1 / out1: a second tensor pair of the same geometry through the same launch (gridDim.y = 2; the stride-2 and stride-1 split-f16 kernels)
     ConvArgs a;
     a.in1 = in1; a.out1 = out1;
@@ -248,9 +257,10 @@ static int launch_conv(const ConvLayer& L, TensorView x, int H, int W, TensorVie
     a.tiles_x = (a.Wo + 31) / 32;
     if (conv_is_h2s2(L, res)) return launch_conv_h2s2(L, a, gy, x.ld - x.coff, s16_pitch, st);
     if (fin && !conv_is_head_h2(L)) return fail(RIFE_HIP_EINVAL, "fused tail needs the split-f16 head kernel");
+    if (mo && !fin) return fail(RIFE_HIP_EINVAL, "motion export rides on the fused tail or on the final kernels");
     if (conv_is_head_h2(L)) {
         if (in1) return fail(RIFE_HIP_EINVAL, "no two-tensor form of the head kernel");
-        return launch_head_h2(L, a, gy, y, fin, s16_pitch, st);
+        return launch_head_h2(L, a, gy, y, fin, s16_pitch, st, mo);
     }
     if (conv_is_h2(L, res)) return launch_conv_h2(L, a, gy, y, in1 || y2, st);
     if (in1) return fail(RIFE_HIP_EINVAL, "no two-tensor form of this convolution kernel");

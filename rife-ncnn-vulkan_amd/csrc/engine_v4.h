@@ -22,7 +22,7 @@ static int ensure_ctx_dims_impl(Ctx& c, int w, int h, int wp, int hp, const Ctx*
     c.g_warm = false; c.d_ts = nullptr;
     for (void* p : c.allocs) (void)hipFree(p);
     c.allocs.clear();
-    c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr;
+    c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr; c.mo_flow = c.mo_mask = nullptr;
     for (auto& pb : c.P) pb[0] = pb[1] = nullptr;                       // S16 trunk tensors: allocated by the first block that runs on them (ensure_s16)
     c.w = w; c.h = h; c.wp = wp; c.hp = hp;
     const size_t P = (size_t)wp * hp;
@@ -69,7 +69,7 @@ static void reset_ctx(Ctx& c) {
     if (c.gexec) { (void)hipGraphExecDestroy(c.gexec); c.gexec = nullptr; }
     for (void* p : c.allocs) (void)hipFree(p);
     c.allocs.clear();
-    c.w = c.h = c.wp = c.hp = 0; c.stage_bytes = 0; c.v2 = false; c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr; c.d_ts = nullptr; c.g_warm = false; for (auto& pb : c.P) pb[0] = pb[1] = nullptr;
+    c.w = c.h = c.wp = c.hp = 0; c.stage_bytes = 0; c.v2 = false; c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr; c.mo_flow = c.mo_mask = nullptr; c.d_ts = nullptr; c.g_warm = false; for (auto& pb : c.P) pb[0] = pb[1] = nullptr;
 }
 static int ensure_ctx_dims(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch = nullptr, bool own_images = true, bool want_outf = false, size_t stage_bytes = 0) {
     const int rc = ensure_ctx_dims_impl(c, w, h, wp, hp, scratch, own_images, want_outf, stage_bytes ? stage_bytes : (size_t)w * h * 3);
@@ -214,6 +214,18 @@ static int launch_tail_rs(const rife_hip::Block& B, const unsigned char* in, int
         return launch<tail_rs_kernel<0, decltype(of)::value>>("tail_rs launch", dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a);
     });
 }
+// a motion call's tail_rs launch (include/rife_hip.h "motion export"): launch_tail_rs's arguments and grid, tail_rs_motion_kernel
+static int launch_tail_rs_motion(const rife_hip::Block& B, const unsigned char* in, int Hq, int Wq, const FinalArgs& fin, const MotionArgs& mo, hipStream_t st) {
+    const S16Geom G(Hq, Wq);
+    TailRsArgs a;
+    a.in = in; a.w = B.head.d_wh; a.bias = B.head.d_bias; a.img0 = fin.img0; a.img1 = fin.img1; a.F = fin.F; a.M = fin.M; a.out = fin.out;
+    a.w_ = fin.w; a.h_ = fin.h; a.wp = fin.wp; a.hp = fin.hp; a.Hq = Hq; a.Wq = Wq; a.pitch = G.pitch; a.plane = G.plane();
+    a.nunits = ((Wq + 31) / 32) * Hq;
+    const int nwg = std::min(2 * device_cus(), a.nunits);
+    return with_outfmt(fin.pixfmt, [&](auto of) {
+        return launch<tail_rs_motion_kernel<decltype(of)::value>>("tail_rs launch", dim3(nwg), dim3(TRS_NTHR), TRS_LDS, st, a, mo);
+    });
+}
 
 // can block b's two stems run as one stem_rs launch?  (64-channel block 3 at scale 1 on the S16 trunk, 12 -> 32 -> 64 channels, uniform shapes)
 static bool block_on_stem_rs(const rife_hip& E, const Ctx& c, int b) {
@@ -281,7 +293,8 @@ static bool flow_update_fused_into(const rife_hip& E, const Ctx& c, int b) {
 
 // upd_flow != null: the flow of block b - 1, whose update of F, M this block's stem applies itself (flow_update_fused_into); F, M swap with F2, M2
 static int run_block_convs(const rife_hip& E, Ctx& c, int b, float timestep, const FinalArgs* fin = nullptr, const float* tsp = nullptr, int phases = PH_ALL,
-                           const float* upd_flow = nullptr, const float* first_flow = nullptr) {
+                           const float* upd_flow = nullptr, const float* first_flow = nullptr, const MotionArgs* mo = nullptr) {
+    // mo (with fin): a motion call - the fused tail this function selects, whichever it is, in its motion form; the selection never looks at mo
     const rife_hip::Block& B = E.blk[b];
     hipStream_t st = c.stream;
     const int s = B.scale, Hb = c.hp / s, Wb = c.wp / s;
@@ -387,8 +400,8 @@ after_stem0:
         // is as fast or faster: head_b3 0.037 vs 0.039 ms per pair, same call)
         if (fin && E.tail_rs && b == 3 && B.c == 64 && B.head.cout == 24 && B.head.d_wh && Ht * 4 == c.hp && Wt * 4 == c.wp &&
             (E.tail_rs_always || ((Wt + 31) / 32) * Ht >= 32 * device_cus(true)))
-            return launch_tail_rs(B, PA, Ht, Wt, *fin, st);
-        return launch_conv(B.head, {reinterpret_cast<float*>(PA), B.c, 0}, Ht, Wt, {c.flow[b], 8, 0}, nullptr, st, fin, G.pitch, G.plane());
+            return mo ? launch_tail_rs_motion(B, PA, Ht, Wt, *fin, *mo, st) : launch_tail_rs(B, PA, Ht, Wt, *fin, st);
+        return launch_conv(B.head, {reinterpret_cast<float*>(PA), B.c, 0}, Ht, Wt, {c.flow[b], 8, 0}, nullptr, st, fin, G.pitch, G.plane(), nullptr, nullptr, nullptr, mo);
     }
     if (phases != PH_ALL) return fail(RIFE_HIP_EINVAL, "phased block execution needs the S16 trunk path");
     float* const stem_out = E.v40 ? c.T2 : c.T0;
@@ -411,7 +424,7 @@ after_stem0:
     }
     {
         Timed t(E.prof, B.head.cls, B.head.flops_per_pixel * Ht * Wt, st);
-        if ((rc = launch_conv(B.head, {cur, B.c, 0}, Ht, Wt, {c.flow[b], 8, 0}, nullptr, st, fin))) return rc;
+        if ((rc = launch_conv(B.head, {cur, B.c, 0}, Ht, Wt, {c.flow[b], 8, 0}, nullptr, st, fin, 0, 0, nullptr, nullptr, nullptr, mo))) return rc;
     }
     return 0;
 }
@@ -449,11 +462,28 @@ static void launch_final_scaled(hipStream_t st, const Ctx& c, int opf, uint8_t* 
     else if (opf == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_scaled<4>, g, dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
     else hipLaunchKernelGGL(k_final_scaled<0>, g, dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
 }
+// a motion call's final kernels (elementwise.h): the grids and arguments of the plain ladders, + where each pixel's final flow and blend weight go
+static void launch_final_scaled_motion(hipStream_t st, const Ctx& c, int opf, uint8_t* d_out, const MotionArgs& mo) {
+    (void)with_outfmt(opf, [&](auto of) {
+        hipLaunchKernelGGL(k_final_scaled_motion<decltype(of)::value>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp, mo);
+        return 0;
+    });
+}
+static void launch_final_motion(hipStream_t st, const uint32_t* img0, const uint32_t* img1, const float4* F, const float* M, const float* flow3, uint8_t* d_out, int w, int h,
+                                int wp, int hp, int opf, const MotionArgs& mo) {
+    (void)with_outfmt(opf, [&](auto of) {
+        hipLaunchKernelGGL(k_final_motion<decltype(of)::value>, grid2d(w, h), dim3(256), 0, st, img0, img1, F, M, flow3, d_out, w, h, wp, hp, mo);
+        return 0;
+    });
+}
 
 // RIFE::process_v4, non-TTA branch (rife.cpp:2931-3173) on device-resident frames.
 // pio != null (an image call, engine_image.h): the frames are the caller's strided planes, read and written in place by the pitched kernels of planes.h; d_in0 / d_in1 are
 // unused and d_out is the tight frame an RGB format's quantising kernels write
-static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t* d_in1, float timestep, uint8_t* d_out, const float* tsp = nullptr, const PlaneIO* pio = nullptr) {
+// mo != null (a motion call, engine_abi.h; plain rife-v4.6 only): the kernel that finishes the frame - whichever this schedule selects, and the selection never looks at
+// mo - runs in its motion form and stores each pixel's final flow and blend weight into the caller's device buffers
+static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t* d_in1, float timestep, uint8_t* d_out, const float* tsp = nullptr, const PlaneIO* pio = nullptr,
+                  const MotionArgs* mo = nullptr) {
     hipStream_t st = c.stream;
     int rc;
     {
@@ -489,7 +519,8 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
     // RIFE_HIP_FLOW_CASCADE=0 (A/B, test build): k_flow_update2 and k_flow_update<2, false>.
     const bool cascade = merge0 && sw.flow_cascade && !flow_update_fused_into(E, c, 3);
     for (int b = 0; b < 4; b++) {
-        if ((rc = run_block_convs(E, c, b, timestep, (b == 3 && fuse_tail) ? &fin : nullptr, tsp, PH_ALL, pending, (merge0 && b == 1) ? c.flow[0] : nullptr))) return rc;
+        if ((rc = run_block_convs(E, c, b, timestep, (b == 3 && fuse_tail) ? &fin : nullptr, tsp, PH_ALL, pending, (merge0 && b == 1) ? c.flow[0] : nullptr,
+                                  (b == 3 && fuse_tail) ? mo : nullptr))) return rc;
         pending = nullptr;
         if (merge0 && b == 0) continue;
         if (merge0 && b == 1) {
@@ -514,11 +545,13 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         HIPCHK(hipGetLastError());
     } else if (E.fscale == 2) {      // block 3's update and the tail in one pass (k_final_scaled)
         Timed t(E.prof, "final", 0, st);
-        launch_final_scaled(st, c, opf, d_out);
+        if (mo) launch_final_scaled_motion(st, c, opf, d_out, *mo);
+        else launch_final_scaled(st, c, opf, d_out);
         HIPCHK(hipGetLastError());
     } else if (!fuse_tail) {
         Timed t(E.prof, "final", 0, st);
-        if (opf == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
+        if (mo) launch_final_motion(st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp, opf, *mo);
+        else if (opf == RIFE_HIP_PIX_RGB10_U16) hipLaunchKernelGGL(k_final_px<1>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         else if (opf == RIFE_HIP_PIX_A2B10G10R10) hipLaunchKernelGGL(k_final_px<2>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         else if (opf == RIFE_HIP_PIX_RGBA8) hipLaunchKernelGGL(k_final_px<4>, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);

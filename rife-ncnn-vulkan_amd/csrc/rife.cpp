@@ -142,6 +142,38 @@ int RIFE::process_yuv(const void* in0, const void* in1, int w, int h, float time
     return ret;
 }
 
+// weak like the precision calls: an engine stand-in without the motion calls still links, and the call then reports -RIFE_HIP_ENOSYS
+extern "C" int rife_hip_process_motion(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt,
+                                       const rife_hip_motion_t* host_motion) __attribute__((weak));
+extern "C" int rife_hip_process_frames_motion(const rife_hip_t* r, const rife_hip_frame_t* frame0, const rife_hip_frame_t* frame1, float timestep, void* out,
+                                              const rife_hip_motion_t* host_motion) __attribute__((weak));
+
+int RIFE::process_motion(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, const rife_hip_motion_t& motion) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_process_motion)
+    {
+        fprintf(stderr, "RIFE::process_motion: this engine has no motion export\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_process_motion(engine, in0, in1, w, h, timestep, out, pixfmt, &motion);
+    if (ret) fprintf(stderr, "RIFE::process_motion: %s\n", rife_hip_last_error());
+    return ret;
+}
+
+int RIFE::process_frames_motion(const rife_hip_frame* frame0, const rife_hip_frame* frame1, float timestep, void* out, const rife_hip_motion_t& motion) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_process_frames_motion)
+    {
+        fprintf(stderr, "RIFE::process_frames_motion: this engine has no motion export\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_process_frames_motion(engine, frame0, frame1, timestep, out, &motion);
+    if (ret) fprintf(stderr, "RIFE::process_frames_motion: %s\n", rife_hip_last_error());
+    return ret;
+}
+
 rife_hip_frame* RIFE::upload_yuv(const void* frame, int w, int h, int pixfmt) const
 {
     if (!engine || !frame) return 0;

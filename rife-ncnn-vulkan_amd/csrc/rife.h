@@ -53,6 +53,12 @@ public:
     int process_yuv(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt) const;
     rife_hip_frame* upload_yuv(const void* frame, int w, int h, int pixfmt) const;
 
+    // Extension, not in the reference (include/rife_hip.h "motion export"): the frame AND the motion it was made from - the final flows (h rows of w pixels of dx0, dy0,
+    // dx1, dy1) and the blend mask (the weight of frame 0's warp), into the host buffers `motion` names with their pitches in bytes (either may be null).  Plain pointers
+    // to tightly packed frames of any _px format, as for process_yuv; the frame is byte for byte the one of the call without motion.  rife-v4.6, plain mode.
+    int process_motion(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, const rife_hip_motion_t& motion) const;
+    int process_frames_motion(const rife_hip_frame* frame0, const rife_hip_frame* frame1, float timestep, void* out, const rife_hip_motion_t& motion) const;
+
     // Extension, not in the reference (include/rife_hip.h "strides and planes"): frames as an AVFrame or a VapourSynth frame holds them - a pointer and a
     // pitch in BYTES per plane, any of the _px formats (planar RGB: R, G, B in plane[0..2]; ffmpeg's gbrp: permute them).  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
     // program that never calls them links against an engine without those two symbols as before; the message of a failure is rife_hip_last_error()).
