@@ -332,6 +332,69 @@ int rife_hip_process_device_motion(const rife_hip_t* r, const void* d_in0, const
 int rife_hip_process_frames_motion(const rife_hip_t* r, const rife_hip_frame_t* frame0, const rife_hip_frame_t* frame1, float timestep, void* out,
                                    const rife_hip_motion_t* host_motion);
 
+/* ---- apply motion: the exported motion applied to the caller's own planes - 16-bit, float, alpha, auxiliary data (absent in the reference) ----------------------------
+ * rife-v4.6 has no refinement network: its frame IS warp(in0, flow[0:2]) * mask + warp(in1, flow[2:4]) * (1 - mask).  The network needs ten bits to ESTIMATE motion;
+ * the BLEND of the caller's samples runs here at fp32 on planes of u8, u16, half or float samples: 12- and 16-bit and un-quantised float pictures, alpha at any depth,
+ * mattes, depth, ids, a grain layer, the raw frame when motion was estimated on a denoised proxy - anything that must move with the picture without influencing the
+ * flow.  The resident frame format and every existing call are untouched.
+ * Inputs: two plane sets of w x h, n planes each (1..4), one sample type; a motion field of the same w x h (F32 or F16, flow AND mask); an extent wp >= w, hp >= h
+ * (0, 0 = w, h); for integer samples a maxval (u8: 1..255, u16: 1..65535; float samples: 0).  Per output pixel (x, y) and plane k, all in fp32, in this order,
+ * products and sums rounded separately (no fused multiply-add):
+ *     S(p, xi, yi)  = (xi < w && yi < h) ? (float)p[yi][xi] : 0.f                  virtual zero padding up to the extent
+ *     W(p, dx, dy):   sx = x + dx; sy = y + dy; x0 = floor(sx); y0 = floor(sy); x1 = x0 + 1; y1 = y0 + 1;
+ *                     x0, x1 clamped to [0, wp-1];  y0, y1 clamped to [0, hp-1];  alpha = sx - x0; beta = sy - y0;      clamp, THEN alpha: src/warp.cpp:133-154
+ *                     (S(x0,y0)*(1-alpha) + S(x1,y0)*alpha)*(1-beta) + (S(x0,y1)*(1-alpha) + S(x1,y1)*alpha)*beta
+ *     v = W(p0[k], dx0, dy0) * m + W(p1[k], dx1, dy1) * (1 - m)
+ *     integer out: min(max((int)(v + 0.5f), 0), maxval)      float out: v      half out: v rounded to nearest even
+ * F16 motion samples are widened to fp32 first.  Integer inputs are read as stored; only the output is clamped to maxval.  A NaN or Inf sample may poison the pixels
+ * whose footprint holds it, and nothing else.
+ * The extent selects the border rule:
+ *   frame semantics  extent = the engine's padded frame size (32n; 64n at flow scale 2: rife_hip_padded_size): the engine's COLOUR path - zero padding, coordinates
+ *                    clamped at the padded edge.  On the R, G, B planes of an RGB8 pair with the motion of the same call this reproduces the call's frame up to
+ *                    the rounding of the last code (the engine scales by 1 / 255 first).
+ *   edge semantics   extent = w, h: ordinary edge clamping, and the engine's ALPHA path - with the edge value replicated into the padding both clamped taps read
+ *                    the same value, so the extrapolating alpha cancels.
+ * Rules (rife_hip_planes_check states them per plane set, every apply call repeats them before it touches anything; a violation is -RIFE_HIP_EINVAL with the fault
+ * named in the message): w, h > 0; n in 1..4; a known sample type; maxval in range for integer samples and 0 for float samples; planes non-NULL; each pitch positive,
+ * at least the row bytes and a multiple of the element size; each pointer element-aligned; h * pitch < 2^32.  The three plane sets of a call agree in w, h, n,
+ * sample and maxval, and the motion passes rife_hip_motion_check for that w, h with both buffers present; the extent is 0, 0 or at least w, h with wp * hp <= 2^27.
+ * Row padding and everything around the planes is never written.  The output planes must not overlap the inputs or the motion (documented, not checked).
+ * Argument checks come before "no HIP device".
+ * The two apply calls need an engine handle only for its device and stream: they work before rife_hip_load and on every model family and mode.
+ * The two process_*_apply calls are rife_hip_process_motion / rife_hip_process_device_motion with F32 motion held in tight device buffers of the workspace, followed
+ * by the apply launch on the same stream: the motion never leaves device memory.  in0 / in1 / out are tight frames of `pixfmt` (the proxy the motion is estimated
+ * on), p0 / p1 / planes_out the planes it is applied to, all w x h.
+ *   Contract    frame and planes are byte for byte those of rife_hip_process_motion (F32) followed by rife_hip_apply_motion on its output (device: likewise).
+ *   Scope       that of motion export; the families and modes it refuses get -RIFE_HIP_ENOSYS with a message that names them and the words "apply motion",
+ *               before anything is written.
+ *   Timestep    0 / 1: no network pass and no arithmetic - the frame as for the _px call, the planes of frame 0 / frame 1 copied, integer samples clamped to maxval.
+ * Out of scope: interleaved multi-channel samples (RGB48, RGBA64), planes at another resolution than the motion (4:2:0 chroma, proxy upscaling), the batch calls,
+ * image (strided-frame) calls with apply, other families for the combined calls, the command line. */
+#define RIFE_HIP_SAMPLE_U8  0
+#define RIFE_HIP_SAMPLE_U16 1   /* native byte order */
+#define RIFE_HIP_SAMPLE_F16 2   /* IEEE binary16 */
+#define RIFE_HIP_SAMPLE_F32 3   /* IEEE binary32 */
+typedef struct rife_hip_planes {
+    int w, h, n, sample, maxval;   /* n planes of w x h samples of type `sample`; maxval: integer samples only, else 0 */
+    void* plane[4];
+    ptrdiff_t pitch[4];            /* BYTES from one row of the plane to the next */
+} rife_hip_planes_t;
+int rife_hip_planes_check(const rife_hip_planes_t* p);                       /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
+/* the padded frame size of the engine for frames of w x h at the flow scale in force: the extent of "frame semantics" */
+int rife_hip_padded_size(const rife_hip_t* r, int w, int h, int* wp, int* hp);
+/* planes and motion in device memory: one launch; stream semantics as for the device _px call (NULL = the engine's own stream, synchronised before returning) */
+int rife_hip_apply_device_motion(const rife_hip_t* r, const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_motion_t* device_motion,
+                                 int wp, int hp, const rife_hip_planes_t* out, void* hip_stream);
+/* everything in host memory: upload, launch, download */
+int rife_hip_apply_motion(const rife_hip_t* r, const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_motion_t* host_motion, int wp, int hp,
+                          const rife_hip_planes_t* out);
+/* estimate on in0 / in1, apply to p0 / p1 in the same pass; host memory; out may be NULL (the frame is not wanted) */
+int rife_hip_process_apply(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt,
+                           const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, int wp, int hp, const rife_hip_planes_t* planes_out);
+/* the same in device memory (d_out is required); stream semantics as for the device _px call */
+int rife_hip_process_device_apply(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt,
+                                  const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, int wp, int hp, const rife_hip_planes_t* planes_out, void* hip_stream);
+
 const char* rife_hip_last_error(void);
 
 /* ---- measurement hooks (bench.py / profiles) ---------------------------------------------------------------

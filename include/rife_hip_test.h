@@ -134,6 +134,13 @@ int rife_hip_op_tail(int gpuid, int kernel, int pixfmt, int w, int h, const void
 int rife_hip_op_tail_motion(int gpuid, int kernel, int pixfmt, int w, int h, const void* trunk, const float* weight, const float* bias, const float* F, const float* M,
                             const uint32_t* img0, const uint32_t* img1, int cus, void* out, int motion_format, void* flow, size_t flow_pitch, void* mask, size_t mask_pitch);
 
+/* op_apply: the apply kernel alone (csrc/apply_motion.h; include/rife_hip.h "apply motion"), ONE launch, on planes and motion in HOST memory: the call uploads every
+ * plane and both motion buffers, gaps between rows included, into device allocations with the same pitches and the same pointer alignment modulo 16, so the form
+ * the host picks is the one it would pick for the caller's planes, and the output planes come back with every byte the kernel did not write as it went in.
+ * force_scalar: 0 = the host's choice, 1 = the one-pixel-per-lane form.  The rules of rife_hip_apply_motion hold (-RIFE_HIP_EINVAL before anything is uploaded). */
+int rife_hip_op_apply(int gpuid, const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_motion_t* host_motion, int wp, int hp,
+                      const rife_hip_planes_t* out, int force_scalar);
+
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */
 int rife_hip_pool_state(const rife_hip_t* r, int* pooled, int* leased, int* high_water);

@@ -36,6 +36,7 @@ C_ABI_SYMBOLS = [
     "rife_hip_set_flow_scale", "rife_hip_flow_scale",
     "rife_hip_set_precision", "rife_hip_precision",
     "rife_hip_motion_check", "rife_hip_process_motion", "rife_hip_process_device_motion", "rife_hip_process_frames_motion",
+    "rife_hip_planes_check", "rife_hip_padded_size", "rife_hip_apply_device_motion", "rife_hip_apply_motion", "rife_hip_process_apply", "rife_hip_process_device_apply",
 ]
 # include/rife_hip.h RIFE_HIP_PRECISION_*: FULL = two f16 products per weight tap of the residual trunks (fp32-equivalent), FAST = one, the skip at full precision
 PRECISION_FULL, PRECISION_FAST = 0, 1
@@ -57,11 +58,15 @@ ENOSYS = 6      # RIFE_HIP_ENOSYS: calls return its negative
 # motion export (include/rife_hip.h RIFE_HIP_MOTION_*): the sample type of the flow and mask buffers
 MOTION_F32, MOTION_F16 = 0, 1
 _MOTION_DTYPE = {MOTION_F32: np.float32, MOTION_F16: np.float16}
+# apply motion (include/rife_hip.h RIFE_HIP_SAMPLE_*): the sample type of the planes a motion field is applied to
+SAMPLE_U8, SAMPLE_U16, SAMPLE_F16, SAMPLE_F32 = 0, 1, 2, 3
+_SAMPLE_DTYPE = {SAMPLE_U8: np.uint8, SAMPLE_U16: np.uint16, SAMPLE_F16: np.float16, SAMPLE_F32: np.float32}
+_SAMPLE_OF = {np.dtype(v): k for k, v in _SAMPLE_DTYPE.items()}
 # include/rife_hip_test.h: exported by librife_hip_test.so (and the bench build) only
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
-                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion"]
+                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply"]
 # rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
 TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
 TAIL_GUARD = 256
@@ -79,6 +84,12 @@ class rife_hip_motion(ctypes.Structure):
     """rife_hip_motion_t of include/rife_hip.h: where a motion call puts the final flows (h rows of w pixels of dx0, dy0, dx1, dy1) and the blend mask (h rows of
     w samples); pitches in BYTES, either pointer may be null (not wanted)."""
     _fields_ = [("flow", ctypes.c_void_p), ("flow_pitch", ctypes.c_size_t), ("mask", ctypes.c_void_p), ("mask_pitch", ctypes.c_size_t), ("format", ctypes.c_int)]
+
+
+class rife_hip_planes(ctypes.Structure):
+    """rife_hip_planes_t of include/rife_hip.h: n (1..4) planes of w x h samples of one type, a pointer and a pitch in BYTES each; maxval for integer samples, else 0."""
+    _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("n", ctypes.c_int), ("sample", ctypes.c_int), ("maxval", ctypes.c_int), ("plane", ctypes.c_void_p * 4),
+                ("pitch", ctypes.c_ssize_t * 4)]
 
 
 def build(force=False):
@@ -149,7 +160,15 @@ def _load(path, with_test_surface):
     L.rife_hip_process_motion.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, mp]
     L.rife_hip_process_device_motion.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, mp, vp]
     L.rife_hip_process_frames_motion.argtypes = [vp, vp, vp, cf, vp, mp]
+    pp = ctypes.POINTER(rife_hip_planes)
+    L.rife_hip_planes_check.argtypes = [pp]
+    L.rife_hip_padded_size.argtypes = [vp, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.rife_hip_apply_device_motion.argtypes = [vp, pp, pp, mp, ci, ci, pp, vp]
+    L.rife_hip_apply_motion.argtypes = [vp, pp, pp, mp, ci, ci, pp]
+    L.rife_hip_process_apply.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, pp, pp, ci, ci, pp]
+    L.rife_hip_process_device_apply.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, pp, pp, ci, ci, pp, vp]
     if with_test_surface:
+        L.rife_hip_op_apply.argtypes = [ci, pp, pp, mp, ci, ci, pp, ci]
         L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
         L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
         L.rife_hip_v4_extract_flow.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp]
@@ -472,6 +491,72 @@ def _motion_host(w, h, dtype, flow, mask):
     return d, f, m
 
 
+def planes_desc(w, h, sample, planes, maxval=None):
+    """A rife_hip_planes from raw addresses: planes = [(address, pitch in bytes), ...] (1..4), device or host.  maxval: None = the sample type's maximum (0 for the
+    float types)."""
+    if maxval is None:
+        maxval = {SAMPLE_U8: 255, SAMPLE_U16: 65535}.get(sample, 0)
+    d = rife_hip_planes()
+    d.w, d.h, d.n, d.sample, d.maxval = int(w), int(h), len(planes), int(sample), int(maxval)
+    for i, (ptr, pitch) in enumerate(planes[:4]):
+        d.plane[i] = int(ptr) if ptr else None
+        d.pitch[i] = int(pitch)
+    return d
+
+
+def planes_check(d):
+    """rife_hip_planes_check (host only): raises RifeError with the fault."""
+    _check(lib().rife_hip_planes_check(ctypes.byref(d)), "planes_check")
+
+
+def planes_of(planes, maxval=None, what="planes", writable=False):
+    """The descriptor of host planes WITHOUT copying them: a tuple of 1..4 2-D arrays of one shape and dtype (uint8, uint16, float16, float32), or one (n, h, w) array;
+    row-padded arrays and views whose pixels are contiguous are taken as they are.  The dtype selects the sample type.  Raises ValueError."""
+    if isinstance(planes, np.ndarray) and planes.ndim == 3:
+        planes = tuple(planes)
+    elif isinstance(planes, np.ndarray) and planes.ndim == 2:
+        planes = (planes,)
+    planes = tuple(planes)
+    if not 1 <= len(planes) <= 4 or not all(isinstance(a, np.ndarray) and a.ndim == 2 and a.size for a in planes):
+        raise ValueError("%s: 1..4 two-dimensional arrays, or one (n, h, w) array" % what)
+    a0 = planes[0]
+    sample = _SAMPLE_OF.get(a0.dtype)
+    if sample is None:
+        raise ValueError("%s: the dtype is uint8, uint16, float16 or float32" % what)
+    for a in planes:
+        if a.dtype != a0.dtype or a.shape != a0.shape or not _rows_strided(a) or (writable and not a.flags.writeable):
+            raise ValueError("%s: each plane is a%s %s array of shape %s whose rows are contiguous" % (what, " writable" if writable else "", a0.dtype.name, a0.shape))
+    d = planes_desc(a0.shape[1], a0.shape[0], sample, [(a.ctypes.data, _pitch(a)) for a in planes], maxval)
+    d._keep = planes
+    return d
+
+
+def _planes_out(like, out):
+    """The output planes of an apply call: `out` (planes as for planes_of, written in place), or new tight arrays shaped like the input planes `like`."""
+    if out is None:
+        out = tuple(np.empty(a.shape, a.dtype) for a in like._keep)
+    d = planes_of(out, like.maxval, "out", writable=True)
+    return d, d._keep
+
+
+def _motion_in(w, h, flow, mask):
+    """The descriptor of host motion an apply call READS: flow (h, w, 4) and mask (h, w) of one dtype, float32 or float16; rows may be strided."""
+    if not isinstance(flow, np.ndarray) or not isinstance(mask, np.ndarray) or flow.dtype != mask.dtype:
+        raise ValueError("flow and mask are arrays of one dtype")
+    fmt = {np.dtype(np.float32): MOTION_F32, np.dtype(np.float16): MOTION_F16}.get(flow.dtype)
+    if fmt is None:
+        raise ValueError("the motion dtype is np.float32 or np.float16")
+    if flow.shape != (h, w, 4) or mask.shape != (h, w):
+        raise ValueError("flow is (h, w, 4) and mask (h, w) of the planes' size")
+    if not _rows_strided(flow):
+        flow = np.ascontiguousarray(flow)
+    if not _rows_strided(mask):
+        mask = np.ascontiguousarray(mask)
+    d = motion_desc(flow.ctypes.data, mask.ctypes.data, fmt, _pitch(flow), _pitch(mask))
+    d._keep = (flow, mask)
+    return d
+
+
 class Frame:
     """A frame resident in device memory (rife_hip_frame_t): upload once, use as either side of any number of pairs."""
 
@@ -744,6 +829,66 @@ class RIFE:
         place by the kernel that finishes the frame; enqueues on `stream` (hipStream_t as int; None = the engine's own stream, synchronised before returning)."""
         _check(self._L.rife_hip_process_device_motion(self._h, d_in0, d_in1, int(w), int(h), float(timestep), d_out, int(pixfmt), ctypes.byref(motion), stream),
                "process_device_motion", self._L)
+
+    def padded_size(self, w, h):
+        """(wp, hp): the engine's padded frame size for frames of w x h at the flow scale in force - the extent of apply_motion's frame semantics."""
+        wp, hp = ctypes.c_int(), ctypes.c_int()
+        _check(self._L.rife_hip_padded_size(self._h, int(w), int(h), ctypes.byref(wp), ctypes.byref(hp)), "padded_size", self._L)
+        return wp.value, hp.value
+
+    def apply_motion(self, planes0, planes1, flow, mask, maxval=None, extent=None, out=None):
+        """rife_hip_apply_motion (include/rife_hip.h "apply motion"): warp(planes0, flow[..., 0:2]) * mask + warp(planes1, flow[..., 2:4]) * (1 - mask) at fp32 on
+        the caller's planes - a tuple of 2-D arrays or one (n, h, w) array of uint8 / uint16 / float16 / float32 (the dtype selects the sample type; row-padded arrays
+        and views are taken without a copy).  flow (h, w, 4) and mask (h, w): float32 or float16, as process_motion() returns them.  maxval: integer samples, default
+        the dtype's maximum.  extent: None or (w, h) = edge clamping; padded_size(w, h) = the engine's frame semantics.  Returns the tuple of output planes (out=:
+        planes to fill in place).  Needs no loaded model."""
+        d0 = planes_of(planes0, maxval, "planes0"); d1 = planes_of(planes1, maxval, "planes1")
+        do, res = _planes_out(d0, out)
+        m = _motion_in(d0.w, d0.h, flow, mask)
+        wp, hp = extent if extent is not None else (0, 0)
+        _check(self._L.rife_hip_apply_motion(self._h, ctypes.byref(d0), ctypes.byref(d1), ctypes.byref(m), int(wp), int(hp), ctypes.byref(do)), "apply_motion", self._L)
+        return res
+
+    def apply_device_motion(self, planes0, planes1, motion, planes_out, extent=None, stream=None):
+        """rife_hip_apply_device_motion: planes_desc() descriptors of DEVICE planes and a motion_desc() of DEVICE buffers; one launch on `stream` (hipStream_t as int;
+        None = a stream of the engine's, synchronised before returning)."""
+        wp, hp = extent if extent is not None else (0, 0)
+        _check(self._L.rife_hip_apply_device_motion(self._h, ctypes.byref(planes0), ctypes.byref(planes1), ctypes.byref(motion), int(wp), int(hp), ctypes.byref(planes_out), stream),
+               "apply_device_motion", self._L)
+
+    def process_apply(self, in0image, in1image, timestep, planes0, planes1, maxval=None, extent=None, out=None, outimage=None, pixfmt=None, want_frame=True):
+        """rife_hip_process_apply: estimate the motion on the frames in0image / in1image (any packed RGB format, as process_motion()) and apply it to planes0 / planes1
+        in the same pass, the motion staying in device memory: (frame, planes).  want_frame=False: the frame is not downloaded and None comes back in its place.
+        Byte for byte process_motion() followed by apply_motion()."""
+        px = _pix_of(in0image, pixfmt)
+        if px is None:
+            a = np.ascontiguousarray(in0image, dtype=np.uint8); b = np.ascontiguousarray(in1image, dtype=np.uint8)
+            if a.ndim != 3 or a.shape[2] != 3 or a.shape != b.shape:
+                raise ValueError("frames must be (h, w, 3) uint8 arrays of equal size")
+            px = PIX_RGB8
+        else:
+            if _pix_of(in1image, px) != px or in1image.shape != in0image.shape:
+                raise ValueError("both frames must have the same pixel format and size")
+            a = np.ascontiguousarray(in0image); b = np.ascontiguousarray(in1image)
+        h, w = a.shape[:2]
+        frame = None
+        if want_frame:
+            frame = outimage if outimage is not None else np.empty_like(a)
+            if not isinstance(frame, np.ndarray) or frame.shape != a.shape or frame.dtype != a.dtype or not frame.flags.c_contiguous or not frame.flags.writeable:
+                raise ValueError("outimage must be a writable contiguous array of the frames' dtype and shape")
+        d0 = planes_of(planes0, maxval, "planes0"); d1 = planes_of(planes1, maxval, "planes1")
+        do, res = _planes_out(d0, out)
+        wp, hp = extent if extent is not None else (0, 0)
+        _check(self._L.rife_hip_process_apply(self._h, _p(a), _p(b), w, h, float(timestep), _p(frame), px, ctypes.byref(d0), ctypes.byref(d1), int(wp), int(hp), ctypes.byref(do)),
+               "process_apply", self._L)
+        return frame, res
+
+    def process_device_apply(self, d_in0, d_in1, w, h, timestep, d_out, planes0, planes1, planes_out, extent=None, stream=None, pixfmt=PIX_RGB8):
+        """rife_hip_process_device_apply: device pointers (ints) to tight frames of `pixfmt` and planes_desc() descriptors of DEVICE planes; enqueues on `stream`
+        (hipStream_t as int; None = the engine's own stream, synchronised before returning)."""
+        wp, hp = extent if extent is not None else (0, 0)
+        _check(self._L.rife_hip_process_device_apply(self._h, d_in0, d_in1, int(w), int(h), float(timestep), d_out, int(pixfmt), ctypes.byref(planes0), ctypes.byref(planes1),
+                                                     int(wp), int(hp), ctypes.byref(planes_out), stream), "process_device_apply", self._L)
 
     def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
         """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
@@ -1042,6 +1187,17 @@ def op_tail_motion(kernel, pixfmt, w, h, trunk, weight, bias, F, M, img0, img1, 
     _check(testlib().rife_hip_op_tail_motion(gpuid, int(kernel), int(pixfmt), int(w), int(h), _p(trunk), _p(weight), _p(bias), _p(F), _p(M), _p(img0), _p(img1), int(cus),
                                              _p(buf), int(fmt), _p(fb), int(flow_pitch), _p(mb), int(mask_pitch)), "op_tail_motion", testlib())
     return buf, fb, mb
+
+
+def op_apply(planes0, planes1, flow, mask, out, maxval=None, extent=None, force_scalar=0, gpuid=0):
+    """rife_hip_op_apply (test build): ONE launch of the apply kernel on host planes (as planes_of takes them) and host motion; `out` planes are written in place - every
+    byte the kernel did not write keeps its value.  force_scalar=1: the one-pixel-per-lane form."""
+    d0 = planes_of(planes0, maxval, "planes0"); d1 = planes_of(planes1, maxval, "planes1")
+    do = planes_of(out, d0.maxval, "out", writable=True)
+    m = _motion_in(d0.w, d0.h, flow, mask)
+    wp, hp = extent if extent is not None else (0, 0)
+    _check(testlib().rife_hip_op_apply(int(gpuid), ctypes.byref(d0), ctypes.byref(d1), ctypes.byref(m), int(wp), int(hp), ctypes.byref(do), int(force_scalar)), "op_apply", testlib())
+    return out
 
 
 def op_yuv_to_rgb10(buf, w, h, pixfmt, gpuid=0):

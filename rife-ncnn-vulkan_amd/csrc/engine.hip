@@ -43,6 +43,8 @@
 #include "planes.h"
 #include "image_check.h"
 #include "motion_check.h"
+#include "apply_check.h"
+#include "apply_motion.h"
 #include "elementwise_v2.h"
 #include "stem_fused.h"
 #include "stem_fused_v2.h"
@@ -69,3 +71,4 @@
 #include "engine_v1.h"
 #include "engine_abi.h"
 #include "engine_image.h"
+#include "engine_apply.h"

@@ -76,6 +76,7 @@ struct Ctx {
     float4* outf = nullptr;                                          // TTA only: out0 as float, padded
     uint32_t* yuv_rgb = nullptr;                                     // YUV calls only (allocated by the first): the pass's A2B10G10R10 frame, tight w x h in wp x hp dwords; k_postproc_yuv reads it
     uint8_t *mo_flow = nullptr, *mo_mask = nullptr;                  // host motion calls only (each allocated by the first that wants it): tight w x h x 16 B / w x h x 4 B, the D2H source
+    uint8_t* ap_planes = nullptr; size_t ap_bytes = 0;               // host apply calls only (process_apply): the tight staging of the three plane sets, grown by the first call that needs more
     // hipGraph replay of the plain v4 schedule for launch-bound frame sizes: fixed staging buffers (d_in0 / d_in1 / d_out), the
     // timestep in device memory, one warm-up pass (lazy allocations, kernel attributes), then capture once and replay
     float* d_ts = nullptr;

@@ -22,7 +22,7 @@ static int ensure_ctx_dims_impl(Ctx& c, int w, int h, int wp, int hp, const Ctx*
     c.g_warm = false; c.d_ts = nullptr;
     for (void* p : c.allocs) (void)hipFree(p);
     c.allocs.clear();
-    c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr; c.mo_flow = c.mo_mask = nullptr;
+    c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr; c.mo_flow = c.mo_mask = nullptr; c.ap_planes = nullptr; c.ap_bytes = 0;
     for (auto& pb : c.P) pb[0] = pb[1] = nullptr;                       // S16 trunk tensors: allocated by the first block that runs on them (ensure_s16)
     c.w = w; c.h = h; c.wp = wp; c.hp = hp;
     const size_t P = (size_t)wp * hp;
@@ -69,7 +69,7 @@ static void reset_ctx(Ctx& c) {
     if (c.gexec) { (void)hipGraphExecDestroy(c.gexec); c.gexec = nullptr; }
     for (void* p : c.allocs) (void)hipFree(p);
     c.allocs.clear();
-    c.w = c.h = c.wp = c.hp = 0; c.stage_bytes = 0; c.v2 = false; c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr; c.mo_flow = c.mo_mask = nullptr; c.d_ts = nullptr; c.g_warm = false; for (auto& pb : c.P) pb[0] = pb[1] = nullptr;
+    c.w = c.h = c.wp = c.hp = 0; c.stage_bytes = 0; c.v2 = false; c.outf = nullptr; c.F2 = nullptr; c.M2 = nullptr; c.yuv_rgb = nullptr; c.mo_flow = c.mo_mask = nullptr; c.ap_planes = nullptr; c.ap_bytes = 0; c.d_ts = nullptr; c.g_warm = false; for (auto& pb : c.P) pb[0] = pb[1] = nullptr;
 }
 static int ensure_ctx_dims(Ctx& c, int w, int h, int wp, int hp, const Ctx* scratch = nullptr, bool own_images = true, bool want_outf = false, size_t stage_bytes = 0) {
     const int rc = ensure_ctx_dims_impl(c, w, h, wp, hp, scratch, own_images, want_outf, stage_bytes ? stage_bytes : (size_t)w * h * 3);

@@ -174,6 +174,39 @@ int RIFE::process_frames_motion(const rife_hip_frame* frame0, const rife_hip_fra
     return ret;
 }
 
+// weak like the motion calls: an engine stand-in without the apply calls still links, and the call then reports -RIFE_HIP_ENOSYS
+extern "C" int rife_hip_apply_motion(const rife_hip_t* r, const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_motion_t* host_motion, int wp, int hp,
+                                     const rife_hip_planes_t* out) __attribute__((weak));
+extern "C" int rife_hip_process_apply(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt,
+                                      const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, int wp, int hp, const rife_hip_planes_t* planes_out) __attribute__((weak));
+
+int RIFE::apply_motion(const rife_hip_planes_t& p0, const rife_hip_planes_t& p1, const rife_hip_motion_t& motion, int wp, int hp, const rife_hip_planes_t& out) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_apply_motion)
+    {
+        fprintf(stderr, "RIFE::apply_motion: this engine has no apply motion\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_apply_motion(engine, &p0, &p1, &motion, wp, hp, &out);
+    if (ret) fprintf(stderr, "RIFE::apply_motion: %s\n", rife_hip_last_error());
+    return ret;
+}
+
+int RIFE::process_apply(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, const rife_hip_planes_t& p0, const rife_hip_planes_t& p1,
+                        int wp, int hp, const rife_hip_planes_t& planes_out) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_process_apply)
+    {
+        fprintf(stderr, "RIFE::process_apply: this engine has no apply motion\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_process_apply(engine, in0, in1, w, h, timestep, out, pixfmt, &p0, &p1, wp, hp, &planes_out);
+    if (ret) fprintf(stderr, "RIFE::process_apply: %s\n", rife_hip_last_error());
+    return ret;
+}
+
 rife_hip_frame* RIFE::upload_yuv(const void* frame, int w, int h, int pixfmt) const
 {
     if (!engine || !frame) return 0;

@@ -59,6 +59,14 @@ public:
     int process_motion(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, const rife_hip_motion_t& motion) const;
     int process_frames_motion(const rife_hip_frame* frame0, const rife_hip_frame* frame1, float timestep, void* out, const rife_hip_motion_t& motion) const;
 
+    // Extension, not in the reference (include/rife_hip.h "apply motion"): a motion field applied to the caller's own planes - n <= 4 planes of u8 / u16 / half / float
+    // samples, a pointer and a pitch in bytes each - at fp32: 16-bit and float pictures, alpha, mattes, depth, the raw frame behind a denoised proxy.  Host memory.
+    // apply_motion needs no loaded model; process_apply estimates on the tight frames in0 / in1 of `pixfmt` (out may be null: the frame is not wanted) and applies in
+    // the same pass, the motion staying in device memory.  wp, hp: the extent (0, 0 = edge clamping; rife_hip_padded_size = the engine's frame semantics).
+    int apply_motion(const rife_hip_planes_t& p0, const rife_hip_planes_t& p1, const rife_hip_motion_t& motion, int wp, int hp, const rife_hip_planes_t& out) const;
+    int process_apply(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, const rife_hip_planes_t& p0, const rife_hip_planes_t& p1,
+                      int wp, int hp, const rife_hip_planes_t& planes_out) const;
+
     // Extension, not in the reference (include/rife_hip.h "strides and planes"): frames as an AVFrame or a VapourSynth frame holds them - a pointer and a
     // pitch in BYTES per plane, any of the _px formats (planar RGB: R, G, B in plane[0..2]; ffmpeg's gbrp: permute them).  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
     // program that never calls them links against an engine without those two symbols as before; the message of a failure is rife_hip_last_error()).
