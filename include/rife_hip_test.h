@@ -45,7 +45,11 @@ int rife_hip_v4_extract_flow_px(const rife_hip_t* r, const void* in0, const void
 int rife_hip_v4_tap_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, int what, int b, const float* const* inject,
                        int n_inject, float* out_chw, int pixfmt);
 /* Flow scale (include/rife_hip.h rife_hip_set_flow_scale): rife_hip_v4_extract_flow, rife_hip_v4_flow_dims and rife_hip_v4_process_injected honour the engine's
- * divisor - at 2 the blobs flow0..3 are hp/16 .. hp/2 of the frame padded to 64n.  The gather taps (rife_hip_v4_tap) exist at divisor 1 only.
+ * divisor - at 2 the blobs flow0..3 are hp/16 .. hp/2 of the frame padded to 64n.  So do the gather taps (rife_hip_v4_tap, rife_hip_v4_tap_px): at divisor 2 hp, wp
+ * are the frame padded to 64n and s = 16, 8, 4, 2, and the taps run the launches of that mode - what = 0 the unfused assembly kernels at 1/16 .. 1/2, what = 1 the
+ * fused stem kernels of the mode (one-hot weights, the 10-bit forms for the 10-bit formats), what = 4 F and M after the three plain flow-update launches, what = 7 the
+ * block stems as a plain pass runs them.  what = 2, 3, 5, 6 are kernels of the divisor-1 schedule which the product does not launch at divisor 2: -RIFE_HIP_EINVAL
+ * with a message that says so.  At either divisor what = 0 also takes b = 0 (n_inject = 0): the 7-channel input of IFBlock 0, 7 x hp/s x wp/s (s = 8 or 16).
  * rife_hip_v4_process_injected_px: flow injection with frames of an RGB format `pixfmt` (out: the same format).  At divisor 2 n_inject may be 4: block 3's update
  * and the tail then run on the four injected blobs alone, in the product's final kernel (k_final_scaled).  At divisor 1: RGB8 and n_inject <= 3, the call above. */
 int rife_hip_v4_process_injected_px(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep,

@@ -994,7 +994,9 @@ class RIFE:
         4 / 3: F (4 channels) and M as block b's stem finds them, after k_flow_update / as written by the stem that applies the last update itself;
         5 (b = 3): the block input through the row-streaming stem kernel of the product;
         6 (b = 2, 3): F and M, (5, hp, wp), as k_flow_cascade<b> writes them from the b injected flows alone (4 is its sequential reference);
-        7 (b = 0..3, RGB8): the first S16 trunk tensor of block b after the block's stems, raw: a uint8 array of op_s16_geom(C, hp / 4 s, wp / 4 s)[3] bytes."""
+        7 (b = 0..3, RGB8): the first S16 trunk tensor of block b after the block's stems, raw: a uint8 array of op_s16_geom(C, hp / 4 s, wp / 4 s)[3] bytes.
+        what = 0 with b = 0 and no blobs: the 7-channel input of block 0.  The buffers follow the flow scale in force (padded_size(), block scales 8, 4, 2, 1 times
+        the divisor); at divisor 2 the library serves what = 0, 1, 4, 7 and refuses 2, 3, 5, 6 (kernels of the scale-1 schedule)."""
         self._need_taps()
         px = _pix_of(in0image, pixfmt)
         if px is not None and _pix_of(in1image, px) != px:
@@ -1004,13 +1006,13 @@ class RIFE:
         else:
             a = np.ascontiguousarray(in0image, dtype=np.uint8); bb = np.ascontiguousarray(in1image, dtype=np.uint8)
         h, w = a.shape[:2]
-        wp, hp = (w + 31) // 32 * 32, (h + 31) // 32 * 32
-        s = {1: 4, 2: 2, 3: 1}.get(b, 1)
+        wp, hp = self.padded_size(w, h)                              # 32n, flow scale 2: 64n
+        s = (8, 4, 2, 1)[b if 0 <= b <= 3 else 3] * self.flow_scale     # the block's scale at the divisor in force
         if what == 7:
-            s, C = {0: (8, 192), 1: (4, 128), 2: (2, 96), 3: (1, 64)}[b]
+            C = (192, 128, 96, 64)[b]
             out = np.empty(op_s16_geom(C, hp // (4 * s), wp // (4 * s))[3], np.uint8)
         else:
-            out = np.empty((4 if px == PIX_RGBA8 else 3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4, 6) else (12, hp // s, wp // s), np.float32)
+            out = np.empty((4 if px == PIX_RGBA8 else 3, hp, wp) if what == 2 else (5, hp, wp) if what in (3, 4, 6) else (7 if b == 0 else 12, hp // s, wp // s), np.float32)
         inj = [np.ascontiguousarray(f, dtype=np.float32) for f in inject]
         arr = (ctypes.c_void_p * max(1, len(inj)))(*[f.ctypes.data for f in inj])
         if px is not None:

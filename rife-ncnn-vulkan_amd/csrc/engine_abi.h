@@ -1086,7 +1086,8 @@ static int tap_prologue(const rife_hip_t* E, Ctx& c, const uint8_t* in0, const u
 }
 
 // what = 0: block input of IFBlock b (1..3; blobs 99 / 199 / 262 of models/rife-v4.6/flownet.param:62, 115, 165) as k_assemble<S> computes it
-//           (the unfused form of the same assemble_pixel<S> / warp_rgbx code);
+//           (the unfused form of the same assemble_pixel<S> / warp_rgbx code); b = 0 (n_inject = 0): the 7-channel input of block 0 (flownet.param:9-10) from
+//           k_assemble0 / k_assemble0_d10 / k_assemble0_s<16, D>, 7 x hp/S x wp/S;
 // what = 1: the same tensor read back THROUGH THE PRODUCT'S FUSED STEM KERNEL stem0_fused_kernel<S, ...> (stem_fused.h), which keeps it in
 //           LDS only: the kernel is run with one-hot weights (output channel 12 p + k = input channel k under tap (1 + p / 2, 1 + p % 2), bias 0,
 //           slope 1), so that its stride-2 output holds the block input's four pixel parities; the split-f16 matrix path returns hi + lo of
@@ -1097,20 +1098,28 @@ static int tap_prologue(const rife_hip_t* E, Ctx& c, const uint8_t* in0, const u
 // what = 6: F, M as k_flow_cascade<b> (flow_cascade.h) writes them from the b injected flows alone, b = 2 / 3; what = 4 is its sequential reference.
 // what = 7: the first S16 trunk tensor of block b (0..3), raw, after the block's stems as run_block_convs runs them (n_inject = b).
 // out: planar CHW fp32, 12 x hp/S x wp/S (what 0, 1) or 3 x hp x wp (what 2).  n_inject must be b (what 0, 1) or 4 (what 2).
+// Flow scale 2: S = 16, 8, 4, 2 and frames padded to 64n (E->blk[b].scale, E->pad()).  what = 0, 1, 4, 7 run the mode's own launches (run_assemble, the
+// stem0_fused_kernel instantiations of run_block_convs' flow-scale-2 branch, the three plain k_flow_update launches); what = 2, 3, 5, 6 are kernels of the
+// scale-1 schedule that the product never launches in this mode: -RIFE_HIP_EINVAL.
 static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, int what, int b,
                                 const float* const* inject, int n_inject, float* out, int pixfmt = RIFE_HIP_PIX_RGB8) {
     int rc;
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if (!E->v4 || E->v40) return fail(RIFE_HIP_EINVAL, "the gather taps exist for the rife-v4.6 graph only");
-    if (E->fscale != 1) return fail(RIFE_HIP_EINVAL, "the gather taps exist at flow scale 1 only");
     if (pix_bpp(pixfmt) == 0) return fail(RIFE_HIP_EINVAL, "unknown pixel format");
     if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if (pixfmt && what == 3) return fail(RIFE_HIP_EINVAL, "tap 3 (an A/B form the product does not run) is served for RGB8 frames only");
     if (what < 0 || what > 7) return fail(RIFE_HIP_EINVAL, "bad tap");
+    if (E->fscale != 1) {      // kernels of the scale-1 schedule only: nothing the product runs at this divisor would be under test
+        if (what == 2) return fail(RIFE_HIP_EINVAL, "tap 2: the unfused float tail (k_final_float) is a scale-1 kernel; at flow scale 2 the tail is k_final_scaled (rife_hip_v4_process_injected_px)");
+        if (what == 3) return fail(RIFE_HIP_EINVAL, "tap 3: no stem applies a flow update at flow scale 2 (the fused update is a scale-1 schedule)");
+        if (what == 5) return fail(RIFE_HIP_EINVAL, "tap 5: the row-streaming stem kernel (stem_rs) serves block 3 at scale 1 only; at flow scale 2 block 3 runs the fused tile stem");
+        if (what == 6) return fail(RIFE_HIP_EINVAL, "tap 6: the flow cascade is a scale-1 schedule; at flow scale 2 the updates are three plain launches (tap 4)");
+    }
     if (what == 7 && pixfmt) return fail(RIFE_HIP_EINVAL, "tap 7 (the block stems) is served for RGB8 frames only");
     if (what == 6 && b != 2 && b != 3) return fail(RIFE_HIP_EINVAL, "the flow cascade runs after block 1 (b = 2) or block 2 (b = 3)");
     if (what == 5 && b != 3) return fail(RIFE_HIP_EINVAL, "the row-streaming stem kernel serves block 3");
-    if (what == 2 ? n_inject != 4 : (b < (what == 7 ? 0 : 1) || b > 3 || n_inject != b)) return fail(RIFE_HIP_EINVAL, "bad block / injection count");
+    if (what == 2 ? n_inject != 4 : (b < ((what == 7 || what == 0) ? 0 : 1) || b > 3 || n_inject != b)) return fail(RIFE_HIP_EINVAL, "bad block / injection count");
     if ((rc = check_device(E->gpuid))) return rc;
     Ctx c; float* tmp = nullptr;
     const float* pending = nullptr;
@@ -1217,14 +1226,15 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
     const int s = B.scale, Hb = c.hp / s, Wb = c.wp / s;
     if (what == 0) {
         if ((rc = run_assemble(*E, c, b, timestep))) return rc;
-        hipLaunchKernelGGL(k_nhwc_to_chw, grid2d(Wb, Hb), dim3(256), 0, st, c.X, tmp, 12, Hb, Wb, 16);
+        const int nch = b == 0 ? 7 : 12, ld = b == 0 ? 8 : 16;      // block 0: X is NHWC8 {in0.rgb, in1.rgb, t, 0}
+        hipLaunchKernelGGL(k_nhwc_to_chw, grid2d(Wb, Hb), dim3(256), 0, st, c.X, tmp, nch, Hb, Wb, ld);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, tmp, (size_t)Hb * Wb * 12 * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(out, tmp, (size_t)Hb * Wb * nch * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         return 0;
     }
     // what == 1: the fused stem kernel of the product with one-hot weights
-    const int NT = s == 1 ? 32 : 64, cout = B.c / 2, per = std::min(4, cout / 12), nlaunch = (4 + per - 1) / per;
+    const int NT = 32 * B.stem0.NS, cout = B.c / 2, per = std::min(4, cout / 12), nlaunch = (4 + per - 1) / per;
     const int Ho = Hb / 2, Wo = Wb / 2;
     std::vector<float> hbias(64, 0.f), hslope(64, 1.f), host((size_t)Ho * Wo * cout);
     float *dbias = nullptr, *dslope = nullptr; uint16_t* dw = nullptr;
@@ -1244,7 +1254,17 @@ static int rife_hip_v4_tap_impl(const rife_hip_t* E, const uint8_t* in0, const u
         fa.tiles_x = (Wo + 31) / 32;
         const dim3 grid(fa.tiles_x * ((Ho + 3) / 4));
         const char* const lname = "hipGetLastError()";      // the error text this site has always had
-        if (pending && pix_deep(pixfmt)) {
+        if (E->fscale == 2) {      // the instantiations of run_block_convs' flow-scale-2 branch, selected as it selects them
+            const bool deep = pix_deep(pixfmt);
+            if (pending) return fail(RIFE_HIP_EINVAL, "no fused flow update at flow scale 2");
+            if (s == 8 && B.stem0.NS == 2) rc = deep ? launch<stem0_fused_kernel<8, 2, 0, 0, 10>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa)
+                                                     : launch<stem0_fused_kernel<8, 2>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (s == 4 && B.stem0.NS == 2) rc = deep ? launch<stem0_fused_kernel<4, 2, 0, 0, 10>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa)
+                                                          : launch<stem0_fused_kernel<4, 2>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
+            else if (s == 2 && B.stem0.NS == 1) rc = deep ? launch<stem0_fused_kernel<2, 1, 0, 0, 10>>(lname, grid, dim3(512), stemf_lds_bytes<1>(), st, fa)
+                                                          : launch<stem0_fused_kernel<2, 1>>(lname, grid, dim3(512), stemf_lds_bytes<1>(), st, fa);
+            else return fail(RIFE_HIP_EINVAL, "no fused stem for this block at flow scale 2");
+        } else if (pending && pix_deep(pixfmt)) {
             fa.pend.flow = pending; fa.pend.Fw = c.F2; fa.pend.Mw = c.M2;
             if (s == 2) rc = launch<stem0_fused_kernel<2, 2, 0, 1, 10>>(lname, grid, dim3(512), stemf_lds_bytes<2>(), st, fa);
             else rc = launch<stem0_fused_kernel<1, 1, 256, 1, 10>>(lname, grid, dim3(512), stemf_lds_bytes<1, 256>(), st, fa);

@@ -149,6 +149,98 @@ def expected_frame(oracle2, a, b, t, depth=8):
     return deep_ref.quantise(extract(oracle2, a, b, t, depth, "out0"), w, h, depth)
 
 
+def stage_blobs(text):
+    """Blob names of the stages of the REWRITTEN graph (text of its flownet.param), found by structure as rewrite_param finds its layers:
+      block0_in   the bottom of the first stride-2 Convolution (7 channels at 1/16)
+      block_in    the tops of the three two-input Concats (12 channels at 1/8, 1/4, 1/2)
+      stems       per block 0..3 the tops of its two stride-2 Convolutions
+      F, M        the running flow and mask logit after the update of block 0..3: F = the top of the scalar mul, then of the three weighted Eltwise sums; M = the
+                  Crop from channel 4 of the same upsampled flow, then the two-input adds that read that Crop (4 and 1 channels at full resolution; entries 0..2
+                  are the tensors blocks 1..3 read, entry 3 is what the tail warps with)
+    Split tops alias their bottom.  ValueError if the graph does not have that shape."""
+    layers = [_parse(s) for s in text.strip("\n").split("\n")[2:] if s.strip()]
+    prod = {t: l for l in layers for t in l["tops"]}
+
+    def src(b):
+        while b in prod and prod[b]["type"] == "Split":
+            b = prod[b]["bottoms"][0]
+        return b
+
+    s2 = [l for l in layers if l["type"] == "Convolution" and _get(l, 3) == "2"]
+    cats = [l for l in layers if l["type"] == "Concat" and len(l["bottoms"]) == 2]
+    scal = [l for l in layers if l["type"] == "BinaryOp" and len(l["bottoms"]) == 1 and _get(l, 1) == "1" and _get(l, 0) == "2"]
+    elt = [l for l in layers if l["type"] == "Eltwise" and _get(l, -23301)]
+    if len(s2) != 8 or len(cats) != 3 or len(scal) != 1 or len(elt) != 3:
+        raise ValueError("not the rewritten rife-v4.6 graph: 8 stride-2 Convolutions, 3 two-input Concats, 1 scalar mul and 3 weighted Eltwise sums expected")
+    F, M = [], []
+    for k, l in enumerate(scal + elt):
+        crop = prod.get(l["bottoms"][-1])                     # Crop of channels 0..3 of u = Interp(flow_k)
+        if crop is None or crop["type"] != "Crop" or prod[src(crop["bottoms"][0])]["type"] != "Interp":
+            raise ValueError("not the rewritten rife-v4.6 graph: update %d does not read a Crop of an upsampled flow" % k)
+        u = src(crop["bottoms"][0])
+        mc = [c for c in layers if c["type"] == "Crop" and src(c["bottoms"][0]) == u and _get(c, -23309) == "1,4"]
+        if len(mc) != 1:
+            raise ValueError("not the rewritten rife-v4.6 graph: one Crop of the mask channel per update expected")
+        m = mc[0]["tops"][0]
+        if k:
+            adds = [a for a in layers if a["type"] == "BinaryOp" and len(a["bottoms"]) == 2 and m in [src(b) for b in a["bottoms"]] and _get(a, 0) in (None, "0")]
+            if len(adds) != 1:
+                raise ValueError("not the rewritten rife-v4.6 graph: one add of the mask increment per update expected")
+            m = adds[0]["tops"][0]
+        F.append(l["tops"][0]); M.append(m)
+    return {"block0_in": src(s2[0]["bottoms"][0]), "block_in": [l["tops"][0] for l in cats],
+            "stems": [(s2[2 * b]["tops"][0], s2[2 * b + 1]["tops"][0]) for b in range(4)], "F": F, "M": M}
+
+
+SCALES = (16, 8, 4, 2)
+PEAK = (0.5, 0.12, 0.06, 0.03)      # peak displacement that blob k adds, as a share of the shorter padded side
+
+
+def injected_flows_scaled(w, h, seed, n):
+    """injected_flows with the amplitude tied to the frame: the same field recipe (sin x cos + noise, channels 4 and 5 as they are), but blob k moves samples by at
+    most about PEAK[k] * min(wp, hp) pixels after the x s of its update, whatever the frame's size - so that a good part of the sampling positions stays inside
+    the padded frame and a good part leaves it (inside_share; tests/test_flowscale_host.py holds that for every case of the GPU tests)."""
+    wp, hp = padded(w, h)
+    rng = np.random.default_rng(seed)
+    out = []
+    for k, s in enumerate(SCALES[:n]):
+        H, W = hp // s, wp // s
+        yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+        f = np.empty((6, H, W), np.float32)
+        amp = PEAK[k] * min(wp, hp) / s
+        for c in range(4):
+            ph = rng.uniform(0, 6.28, 2)
+            f[c] = amp * np.sin(xx * (rng.uniform(0.5, 3.0) * 6.28 / W) + ph[0]) * np.cos(yy * (rng.uniform(0.5, 3.0) * 6.28 / H) + ph[1]) + rng.normal(0, 0.3 * amp / 8, (H, W))
+        f[4] = rng.normal(0, 1.5, (H, W)); f[5] = rng.normal(0, 1.0, (H, W))
+        out.append(f.astype(np.float32))
+    return out
+
+
+def inside_share(F):
+    """F (4, hp, wp), the running flow at full resolution -> (share of the pixels whose sampling position (x + F.x, y + F.y) lies inside the padded frame, the
+    same for (x + F.z, y + F.w), largest |displacement| in pixels)."""
+    _, hp, wp = F.shape
+    yy, xx = np.mgrid[0:hp, 0:wp].astype(np.float64)
+    sh = []
+    for c in (0, 2):
+        px, py = xx + F[c], yy + F[c + 1]
+        sh.append(float(((px >= 0) & (px <= wp - 1) & (py >= 0) & (py <= hp - 1)).mean()))
+    return sh[0], sh[1], float(np.abs(F).max())
+
+
+# The cases of tests/test_gpu_flowscale_gather.py: (w, h, seed) - each size the smallest that still reaches its edge.  Frames are noise for odd seeds and smooth
+# for even ones; the flows are injected_flows_scaled(w, h, FLOW_SEED + seed, ..).
+GATHER_CASES = [(1, 1, 1),          # 64x64: flow0 is 4x4, block 0's trunk 1x1; up_coeff's in - 2 edge
+                (65, 64, 2),        # 128x64: one column past 64
+                (100, 60, 3),       # 128x64
+                (130, 9, 4),        # 192x64
+                (8, 300, 5),        # 64x320
+                (333, 241, 6),      # 384x256
+                (640, 360, 7)]      # 640x384: the first size with two 32-wide tiles across in the scale-8 stem (Wo = 40); the scale-4 stem has three, the scale-2 stem five
+FLOW_SEED = 100
+FINAL_CASES = [(100, 60, 1), (333, 241, 4)]      # test_gpu_flowscale.py: k_final_scaled on four injected blobs
+
+
 def injected_flows(w, h, seed, n):
     """tests/test_gpu_gather.py's injected_flows at the mode's sizes (its arguments fix 32n and the scales 8, 4, 2, 1): blobs flow0..flow{n-1},
     6 x hp/s x wp/s with s = 16, 8, 4, 2 of the frame padded to 64n - smooth fields + noise; after the x s of the flow update the coarse one moves samples by

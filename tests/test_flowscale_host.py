@@ -110,6 +110,72 @@ def test_injected_blobs_reach_the_rewritten_graph(scaled, oracle2):
     assert np.abs(got - want.numpy()).max() < 1e-4
 
 
+def test_stage_blobs_of_the_rewritten_graph(modeldirs, scaled, oracle2):
+    """flowscale_ref.stage_blobs: the names the gather tests of flow scale 2 extract - counts, the layers behind them, and their shapes on the oracle."""
+    with open(os.path.join(scaled, "flownet.param")) as f:
+        text = f.read()
+    sb = flowscale_ref.stage_blobs(text)
+    assert len(sb["block_in"]) == 3 and len(sb["stems"]) == 4 and len(sb["F"]) == 4 and len(sb["M"]) == 4
+    names = [sb["block0_in"]] + sb["block_in"] + [n for p in sb["stems"] for n in p] + sb["F"] + sb["M"]
+    assert len(set(names)) == len(names) == 20
+    layers = ncnn_param.parse(os.path.join(scaled, "flownet.param"))
+    prod = {t: l for l in layers for t in l["tops"]}
+    assert prod[sb["block0_in"]]["type"] == "Interp" and prod[sb["block0_in"]]["params"][1] == 1 / 16
+    assert all(prod[n]["type"] == "Concat" for n in sb["block_in"])
+    assert [prod[n]["params"][0] for p in sb["stems"] for n in p] == [96, 192, 64, 128, 48, 96, 32, 64]
+    assert [prod[n]["type"] for n in sb["F"]] == ["BinaryOp", "Eltwise", "Eltwise", "Eltwise"]
+    assert [list(prod[n]["arrays"][1]) for n in sb["F"][1:]] == [[1.0, 8.0], [1.0, 4.0], [1.0, 2.0]]
+    assert [prod[n]["type"] for n in sb["M"]] == ["Crop", "BinaryOp", "BinaryOp", "BinaryOp"]
+    with open(os.path.join(modeldirs["rife-v4"], "flownet.param")) as f:
+        with pytest.raises(ValueError):
+            flowscale_ref.stage_blobs(f.read())
+    for w, h, wp, hp in ((64, 64, 64, 64), (100, 60, 128, 64)):
+        a, b = gen_frames.smooth_pair(w, h, 5)
+        inj = flowscale_ref.injected_flows_scaled(w, h, 3, 4)
+        assert [f.shape for f in inj] == [(6, hp // s, wp // s) for s in flowscale_ref.SCALES]
+        ex = lambda n: flowscale_ref.extract(oracle2, a, b, 0.5, 8, n, flows=inj).shape
+        assert ex(sb["block0_in"]) == (7, hp // 16, wp // 16)
+        for k, s in enumerate((8, 4, 2)):
+            assert ex(sb["block_in"][k]) == (12, hp // s, wp // s)
+        for k, (s, C) in enumerate(zip(flowscale_ref.SCALES, (192, 128, 96, 64))):
+            assert ex(sb["stems"][k][0]) == (C // 2, hp // s // 2, wp // s // 2) and ex(sb["stems"][k][1]) == (C, hp // s // 4, wp // s // 4)
+        for k in range(4):
+            assert ex(sb["F"][k]) == (4, hp, wp) and ex(sb["M"][k]) == (1, hp, wp)
+
+
+def test_scaled_flows_keep_their_recipe_and_peak():
+    """injected_flows_scaled is injected_flows with another amplitude: the same draws in the same order (channels 4 and 5 bit for bit), peaks tied to the frame."""
+    for w, h in ((100, 60), (640, 360)):
+        wp, hp = flowscale_ref.padded(w, h)
+        old, new = flowscale_ref.injected_flows(w, h, 9, 4), flowscale_ref.injected_flows_scaled(w, h, 9, 4)
+        for k, s in enumerate(flowscale_ref.SCALES):
+            assert new[k].shape == old[k].shape and np.array_equal(new[k][4:], old[k][4:])
+            ratio = flowscale_ref.PEAK[k] * min(wp, hp) / s / (40.0, 6.0, 3.0, 1.5)[k]
+            assert np.allclose(new[k][:4], old[k][:4] * ratio, rtol=1e-5, atol=1e-6)
+            assert np.abs(new[k][:4]).max() * s <= 1.5 * flowscale_ref.PEAK[k] * min(wp, hp)
+
+
+_SHARE_CASES = [(w, h, flowscale_ref.FLOW_SEED + seed, n) for w, h, seed in flowscale_ref.GATHER_CASES for n in (1, 2, 3)] + \
+               [(w, h, flowscale_ref.FLOW_SEED + seed, 4) for w, h, seed in flowscale_ref.FINAL_CASES]
+
+
+@pytest.mark.parametrize("w,h,fseed,n", _SHARE_CASES)
+def test_injected_flows_look_inside_the_frame_and_outside(scaled, oracle2, w, h, fseed, n):
+    """The condition that keeps the injected-flow tests of flow scale 2 from looking at clamps only, or at none: for every case they use - the n blobs block n reads
+    (n = 1..3), or all four for k_final_scaled - the sampling positions x + F of BOTH frames, from the oracle's F blob after the last injected update, lie inside the
+    padded frame for at least a quarter and at most nine tenths of the pixels, and the largest displacement exceeds a quarter of the shorter padded side."""
+    with open(os.path.join(scaled, "flownet.param")) as f:
+        sb = flowscale_ref.stage_blobs(f.read())
+    wp, hp = flowscale_ref.padded(w, h)
+    a, b = gen_frames.smooth_pair(w, h, 1)
+    inj = flowscale_ref.injected_flows_scaled(w, h, fseed, n)
+    F = flowscale_ref.extract(oracle2, a, b, 0.5, 8, sb["F"][n - 1], flows=inj)
+    s0, s1, peak = flowscale_ref.inside_share(F)
+    print("flow scale 2 gather, %dx%d (%dx%d) %d blobs: inside share %.2f / %.2f, largest displacement %.1f px" % (w, h, wp, hp, n, s0, s1, peak))
+    assert 0.25 <= s0 <= 0.90 and 0.25 <= s1 <= 0.90
+    assert peak > min(wp, hp) / 4
+
+
 def test_header_declares_and_python_lists_the_calls():
     with open(os.path.join(ROOT, "include", "rife_hip.h")) as f:
         header = f.read()

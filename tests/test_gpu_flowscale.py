@@ -3,7 +3,8 @@
 Expected values: the oracle on the rewritten graph (tests/flowscale_ref.py; tests/test_flowscale_host.py pins that recipe without a GPU).
   1  parity: at most 1 code per channel against the oracle, RGB8 and both 10-bit formats
   2  stage flows flow0..3 within 1e-3 of the oracle's blobs
-  3  the final kernel (k_final_scaled) on injected flows that leave the frame, RGB8 / A2B10G10R10 / RGBA8
+  3  the final kernel (k_final_scaled) on injected flows that leave the frame, and on scaled ones that stay inside it for most pixels, RGB8 / A2B10G10R10 / RGBA8 /
+     RGB10_U16 (the gather code and the flow updates of the mode on injected flows: tests/test_gpu_flowscale_gather.py)
   4  identities, byte for byte: every entry point against process(), YUV against the A2B10G10R10 call, threads, repeat runs, timestep 0 / 1, scale 1
   5  refusals
   6  the command line (-d)"""
@@ -107,10 +108,17 @@ def test_stage_flows_match_the_rewritten_graph(t2, oracle2, w, h, depth):
 
 # ---- 3. the final kernel on injected flows ---------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("w,h,seed", [(100, 60, 1), (333, 241, 4)])
-def test_final_kernel_on_injected_flows_that_leave_the_frame(t2, oracle2, w, h, seed):
-    inj = fr.injected_flows(w, h, 100 + seed, 4)
-    assert np.abs(inj[0][:4]).max() * 16 > 100, "injected flows too small to exercise the clamps"
+@pytest.mark.parametrize("w,h,seed,scaled", [pytest.param(100, 60, 1, False, id="100-60-1"), pytest.param(333, 241, 4, False, id="333-241-4")] +
+                         [pytest.param(w, h, seed, True, id="%d-%d-%d-scaled" % (w, h, seed)) for w, h, seed in fr.FINAL_CASES])
+def test_final_kernel_on_injected_flows_that_leave_the_frame(t2, oracle2, w, h, seed, scaled):
+    """scaled: flowscale_ref.injected_flows_scaled - between a quarter and nine tenths of the sampling positions of each frame lie INSIDE the padded frame
+    (tests/test_flowscale_host.py holds that for these cases); the unscaled blobs copy the scale-1 amplitudes and at 100x60 leave the frame nearly everywhere."""
+    if scaled:
+        inj = fr.injected_flows_scaled(w, h, fr.FLOW_SEED + seed, 4)
+        assert np.abs(inj[0][:4]).max() * 16 > min(fr.padded(w, h)) / 4, "injected flows too small to exercise the clamps"
+    else:
+        inj = fr.injected_flows(w, h, 100 + seed, 4)
+        assert np.abs(inj[0][:4]).max() * 16 > 100, "injected flows too small to exercise the clamps"
     t = 0.4
     # PX 0
     a, b = gen_frames.noise_pair(w, h, seed) if seed % 2 else gen_frames.smooth_pair(w, h, seed)
@@ -132,6 +140,10 @@ def test_final_kernel_on_injected_flows_that_leave_the_frame(t2, oracle2, w, h, 
     worst, share = codes_off(got10, want10)
     print("k_final_scaled<2> %dx%d: max |diff| %d, %.3f %% differ" % (w, h, worst, 100 * share))
     assert worst <= 1
+    # PX 1: the RGB10_U16 frame is the unpacked A2B10G10R10 frame
+    got16 = t2.v4_process_injected(a10, b10, t, inj, pixfmt=U16)
+    assert got16.dtype == np.uint16 and got16.shape == (h, w, 3)
+    assert np.array_equal(got16, got10), "k_final_scaled<1>: %d of %d codes differ from k_final_scaled<2>'s" % (int((got16 != got10).sum()), got10.size)
 
 
 # ---- 4. identities -----------------------------------------------------------------------------------------------------------------------------------
