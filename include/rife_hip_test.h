@@ -145,6 +145,23 @@ int rife_hip_op_tail_motion(int gpuid, int kernel, int pixfmt, int w, int h, con
 int rife_hip_op_apply(int gpuid, const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_motion_t* host_motion, int wp, int hp,
                       const rife_hip_planes_t* out, int force_scalar);
 
+/* ---- the generic layer-wise graph executor (csrc/graph_exec.h, graph_run.h, graph_kernels.h: the v1 family) on any .param / .bin pair, one graph_run per call.
+ * graph_plan needs no device: it parses <base>.param as rife_hip_graph_check does and writes what the loader settled on, one line per layer, tab-separated:
+ *   <layer name> <kind> fold=<the layer that executes this one | -> out=<the blob the launch writes | -> class=<g_conv3x3 | g_conv3x3_s2 | g_conv5x5 | g_deconv4x4 | direct | ->
+ *   padded=<1: zero filters pad the output channels to a multiple of 4>
+ * into buf (cap bytes, NUL-terminated; too small: -RIFE_HIP_EINVAL).
+ * graph_eval loads <base>.param / .bin with the product's loader and runs the product's graph_run once.  Bound blobs: n_in names, planar CHW fp32 host arrays and
+ * in_dims[3 i .. 3 i + 2] = c, h, w; each is uploaded into a blob allocated as the executor allocates its own (pixel stride = channels rounded up to 16, pad
+ * channels zero; a 1 x 1 x C blob is a vector).  Wanted blobs: n_out names; out_chw[i] takes the blob as planar CHW if it has at most out_caps[i] ELEMENTS, and
+ * out_dims[3 i ..] its c, h, w.  keep != 0: the loaded net and its blob storage stay for the next call with the same base and gpuid, which then runs on them (the
+ * re-use of blob buffers across geometries); a call with keep = 0 releases them.
+ * Refused by name before anything is uploaded or launched, -RIFE_HIP_EINVAL: a wanted blob that no launch writes (the tops of the two BinaryOps folded into an SE
+ * tail, the top of a Convolution whose result goes to its PReLU's top), and a binding of such a blob (it would cut a fused pair or an SE tail).  -RIFE_HIP_EMODEL
+ * from graph_run: Interp from a blob one pixel wide or high, global Pooling over a channel count that is not a multiple of 4. */
+int rife_hip_graph_plan(const char* base, char* buf, size_t cap);
+int rife_hip_graph_eval(int gpuid, const char* base, int n_in, const char* const* in_names, const float* const* in_chw, const int* in_dims, int n_out,
+                        const char* const* out_names, float* const* out_chw, const size_t* out_caps, int* out_dims, int keep);
+
 /* ---- workspace pool of the host-buffer entry points (csrc/engine_abi.h: lease_ctx / release_ctx): pooled = idle workspaces the engine holds,
  * leased = workspaces in use by callers right now, high_water = the most callers in flight at any of the last 32 leases (the pool is trimmed to it). */
 int rife_hip_pool_state(const rife_hip_t* r, int* pooled, int* leased, int* high_water);

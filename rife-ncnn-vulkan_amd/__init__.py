@@ -66,7 +66,8 @@ _SAMPLE_OF = {np.dtype(v): k for k, v in _SAMPLE_DTYPE.items()}
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
-                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply"]
+                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply",
+                    "rife_hip_graph_plan", "rife_hip_graph_eval"]
 # rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
 TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
 TAIL_GUARD = 256
@@ -191,6 +192,8 @@ def _load(path, with_test_surface):
         L.rife_hip_op_head_ps.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp]
         L.rife_hip_op_tail.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.rife_hip_op_tail_motion.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t]
+        L.rife_hip_graph_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.rife_hip_graph_eval.argtypes = [ci, ctypes.c_char_p, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci]
     return L
 
 
@@ -1056,6 +1059,42 @@ def op_conv3x3(x, weight, bias, stride=1, residual=None, slope=None, gpuid=0):
     sl = None if slope is None else np.ascontiguousarray(slope, np.float32)
     _check(testlib().rife_hip_op_conv3x3(gpuid, _p(x), c, h, w, _p(weight), _p(bias), oc, stride, _p(res), _p(sl), _p(out)), "op_conv3x3", testlib())
     return out
+
+
+def graph_plan(param_base):
+    """rife_hip_graph_plan (host only): what the graph loader settled on for <param_base>.param, one dict per layer in file order -
+    name, kind, fold (the layer that executes this one, or None), out (the blob its launch writes, or None), cls (a convolution's profile class, "direct", or None),
+    padded (zero filters pad the output channels to a multiple of 4)."""
+    buf = ctypes.create_string_buffer(1 << 20)
+    _check(testlib().rife_hip_graph_plan(param_base.encode(), buf, len(buf)), "graph_plan", testlib())
+    plan = []
+    for line in buf.value.decode().splitlines():
+        name, kind, *kv = line.split("\t")
+        f = dict(x.split("=", 1) for x in kv)
+        plan.append(dict(name=name, kind=kind, fold=None if f["fold"] == "-" else f["fold"], out=None if f["out"] == "-" else f["out"],
+                         cls=None if f["class"] == "-" else f["class"], padded=f["padded"] == "1"))
+    return plan
+
+
+def graph_eval(param_base, inputs, wanted, keep=False, gpuid=0):
+    """rife_hip_graph_eval: one graph_run of the generic executor on <param_base>.param / .bin.  inputs: {blob: (C, H, W) float32} (a (C, 1, 1) array becomes a
+    vector blob); wanted: blob names.  Returns the wanted blobs as (C, H, W) float32 arrays.  keep: the net and its blob storage stay for the next call on the
+    same files (include/rife_hip_test.h)."""
+    names = list(inputs)
+    arrs = [np.ascontiguousarray(inputs[n], np.float32) for n in names]
+    if any(a.ndim != 3 for a in arrs):
+        raise ValueError("bound blobs are (C, H, W) arrays")
+    cn = (ctypes.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+    ca = (ctypes.c_void_p * max(1, len(names)))(*[a.ctypes.data for a in arrs])
+    dims = np.array([a.shape for a in arrs], np.int32).reshape(-1)
+    caps = [max([a.size for a in arrs] + [1 << 16]) * 64] * len(wanted)
+    outs = [np.empty(c, np.float32) for c in caps]
+    wn = (ctypes.c_char_p * len(wanted))(*[w.encode() for w in wanted])
+    wa = (ctypes.c_void_p * len(wanted))(*[o.ctypes.data for o in outs])
+    wc = (ctypes.c_size_t * len(wanted))(*caps)
+    od = np.zeros(3 * len(wanted), np.int32)
+    _check(testlib().rife_hip_graph_eval(gpuid, param_base.encode(), len(names), cn, ca, _p(dims), len(wanted), wn, wa, wc, _p(od), int(bool(keep))), "graph_eval", testlib())
+    return [o[: c * h * w].reshape(c, h, w).copy() for o, (c, h, w) in zip(outs, od.reshape(-1, 3))]
 
 
 def op_deconv4x4(x, weight, bias, slope=None, gpuid=0):

@@ -1379,6 +1379,102 @@ int rife_hip_v4_flow_dims(const rife_hip_t* E, int w, int h, int fi, int* channe
     return 0;
 }
 
+// ---- the generic graph executor on micro-graphs: the plan graph_load settles on (host only), and one graph_run with host blobs -----------------
+// One text line per layer, tab-separated: name, kind, fold=<layer that executes it | ->, out=<blob the result goes to | ->,
+// class=<profile class of a convolution | ->, padded=<1 when zero filters pad the output channels to a multiple of 4>
+static void graph_plan(const GraphNet& N, std::string& s) {
+    static const char* const kinds[] = {"Input", "Split", "Concat", "Crop", "Interp", "Convolution", "Deconvolution", "ConvolutionDirect", "PixelShuffle", "ReLU", "PReLU",
+                                        "Sigmoid", "Clip", "BinaryOp", "Eltwise", "UnaryOp", "Pooling", "InnerProduct", "rife.Warp"};
+    const std::vector<int> wr = graph_writers(N);
+    for (const GLayer& L : N.layers) {
+        const bool conv = L.kind == G_CONV || L.kind == G_DECONV, direct = L.kind == G_CONV_DIRECT;
+        const int ob = L.folded ? -1 : L.out_blob;
+        s += L.nl->name + "\t" + kinds[L.kind];
+        s += std::string("\tfold=") + (L.folded ? N.layers[L.folded_into].nl->name : "-");
+        s += std::string("\tout=") + (ob >= 0 && wr[ob] >= 0 ? N.blob_names[ob] : "-");
+        s += std::string("\tclass=") + (conv ? L.conv.cls : direct ? "direct" : "-");
+        s += std::string("\tpadded=") + (conv && L.nl->geti(0, 0) % 4 ? "1" : "0") + "\n";
+    }
+}
+
+int rife_hip_graph_plan(const char* base, char* buf, size_t cap) {
+    return guarded("rife_hip_graph_plan", [&] {
+        if (!base || !buf || !cap) return fail(RIFE_HIP_EINVAL, "null argument");
+        GraphNet n;
+        int rc;
+        if ((rc = graph_load(n, base, true))) return rc;
+        std::string s;
+        graph_plan(n, s);
+        if (s.size() + 1 > cap) return fail(RIFE_HIP_EINVAL, "rife_hip_graph_plan: the plan needs " + std::to_string(s.size() + 1) + " bytes");
+        std::memcpy(buf, s.c_str(), s.size() + 1);
+        return 0;
+    });
+}
+
+struct GraphEvalKept { std::string base; int gpuid = -1; std::unique_ptr<GraphNet> net; std::unique_ptr<GraphInst> inst; };
+// the net and blob storage of the last rife_hip_graph_eval(keep = 1) call: the next call on the same files runs on them.  Heap-allocated and never destroyed: what
+// a process leaves kept at exit must not be freed from a static destructor, after the HIP runtime has shut down.
+static GraphEvalKept& g_eval_kept = *new GraphEvalKept;
+static std::mutex g_eval_mu;
+
+static int rife_hip_graph_eval_impl(int gpuid, const char* base, int n_in, const char* const* in_names, const float* const* in_chw, const int* in_dims, int n_out,
+                                    const char* const* out_names, float* const* out_chw, const size_t* out_caps, int* out_dims, int keep) {
+    if (!base || n_in < 0 || n_out <= 0 || (n_in && (!in_names || !in_chw || !in_dims)) || !out_names || !out_chw || !out_caps || !out_dims)
+        return fail(RIFE_HIP_EINVAL, "rife_hip_graph_eval: null argument");
+    for (int i = 0; i < n_in; i++)
+        if (!in_names[i] || !in_chw[i] || in_dims[3 * i] <= 0 || in_dims[3 * i + 1] <= 0 || in_dims[3 * i + 2] <= 0) return fail(RIFE_HIP_EINVAL, "rife_hip_graph_eval: bad input blob");
+    for (int i = 0; i < n_out; i++) if (!out_names[i] || !out_chw[i]) return fail(RIFE_HIP_EINVAL, "rife_hip_graph_eval: bad output blob");
+    int rc;
+    if ((rc = check_device(gpuid))) return rc;
+    std::lock_guard<std::mutex> g(g_eval_mu);
+    std::unique_ptr<GraphNet> net; std::unique_ptr<GraphInst> inst;
+    if (g_eval_kept.net && g_eval_kept.base == base && g_eval_kept.gpuid == gpuid) { net = std::move(g_eval_kept.net); inst = std::move(g_eval_kept.inst); }
+    g_eval_kept.net.reset(); g_eval_kept.inst.reset();
+    if (!net) {
+        net.reset(new GraphNet); inst.reset(new GraphInst);
+        if ((rc = graph_load(*net, base))) return rc;
+    }
+    const GraphNet& N = *net; GraphInst& I = *inst;
+    std::vector<std::string> wanted(out_names, out_names + n_out);
+    if ((rc = graph_check_taps(N, std::vector<std::string>(in_names, in_names + n_in), wanted))) return rc;      // before anything is uploaded or launched
+    const size_t nb = N.blob_names.size();
+    if (I.v.size() != nb) { I.v.assign(nb, GView{nullptr, 0, 0, 0, 0}); I.owned.assign(nb, nullptr); I.cap.assign(nb, 0); }
+    std::vector<std::pair<std::string, GView>> bound;
+    std::vector<float> host;
+    for (int i = 0; i < n_in; i++) {
+        const int b = N.blob(in_names[i]);
+        if (b < 0) return fail(RIFE_HIP_EMODEL, N.name + ": no blob named " + in_names[i]);
+        const int c = in_dims[3 * i], h = in_dims[3 * i + 1], w = in_dims[3 * i + 2];
+        if ((rc = g_alloc(I, b, c, h, w, h == 1 && w == 1, nullptr))) return rc;      // a 1 x 1 x C blob is a vector, like the outputs of Pooling / InnerProduct
+        const GView v = I.v[b];
+        host.assign((size_t)h * w * v.ld, 0.f);                                       // pad channels go up as zeros, as g_alloc left them
+        for (int q = 0; q < c; q++)
+            for (size_t p = 0; p < (size_t)h * w; p++) host[p * v.ld + q] = in_chw[i][(size_t)q * h * w + p];
+        HIPCHK(hipMemcpy(v.p, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+        bound.emplace_back(in_names[i], v);
+    }
+    rife_hip E;                                                                      // graph_run wants the engine for its profiler only
+    E.gpuid = gpuid;
+    if ((rc = graph_run(E, N, I, nullptr, bound, wanted))) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    for (int i = 0; i < n_out; i++) {
+        const GView v = I.v[N.blob(out_names[i])];
+        const size_t npix = (size_t)v.h * v.w;
+        out_dims[3 * i] = v.c; out_dims[3 * i + 1] = v.h; out_dims[3 * i + 2] = v.w;
+        if (npix * v.c > out_caps[i]) return fail(RIFE_HIP_EINVAL, N.name + ": blob " + out_names[i] + " has " + std::to_string(npix * v.c) + " elements, more than its buffer holds");
+        host.resize(npix * v.ld);
+        HIPCHK(hipMemcpy(host.data(), v.p, host.size() * 4, hipMemcpyDeviceToHost));
+        for (int q = 0; q < v.c; q++)
+            for (size_t p = 0; p < npix; p++) out_chw[i][(size_t)q * npix + p] = host[p * v.ld + q];
+    }
+    if (keep) { g_eval_kept.base = base; g_eval_kept.gpuid = gpuid; g_eval_kept.net = std::move(net); g_eval_kept.inst = std::move(inst); }
+    return 0;
+}
+int rife_hip_graph_eval(int gpuid, const char* base, int n_in, const char* const* in_names, const float* const* in_chw, const int* in_dims, int n_out,
+                        const char* const* out_names, float* const* out_chw, const size_t* out_caps, int* out_dims, int keep) {
+    return guarded("rife_hip_graph_eval", [&] { return rife_hip_graph_eval_impl(gpuid, base, n_in, in_names, in_chw, in_dims, n_out, out_names, out_chw, out_caps, out_dims, keep); });
+}
+
 // ---- single-kernel entry points ------------------------------------------------------------------------------
 static int op_conv_common(int gpuid, const float* x, int c, int h, int w, const float* weight, const float* bias, int outc, int stride,
                           bool deconv, int epi, const float* residual, const float* slope, float* out) {

@@ -20,7 +20,8 @@ struct GLayer {
     ConvLayer conv;                                   // G_CONV / G_DECONV
     float *d_w = nullptr, *d_bias = nullptr, *d_slope = nullptr;   // G_CONV_DIRECT / G_INNER / G_PRELU
     int out_blob = -1;                                // where the result goes (the folded PReLU's top for conv + PReLU pairs)
-    bool folded = false;                              // PReLU executed by its producer
+    bool folded = false;                              // PReLU executed by its producer, BinaryOp executed by the PReLU that closes its SE block
+    int folded_into = -1;                             // the layer that executes a folded one
     int post_act = 0;                                 // activation the conv epilogue cannot apply (4 = sigmoid): extra pointwise pass
     int se_y = -1, se_scale = -1, se_skip = -1;       // G_PRELU closing an SE block: y * scale + skip is computed here too (kg_se_tail)
 };
@@ -132,8 +133,10 @@ static int graph_load(GraphNet& N, const std::string& base, bool check_only = fa
             const int top = L.tops[0];
             if (act == 0 && nuse[top] == 1 && N.layers[consumer[top]].nl->type == "PReLU") {
                 GLayer& P = N.layers[consumer[top]];
-                if (!check_only && (int)P.nl->slope.size() == outc) slope = P.nl->slope;
-                if (check_only || (int)P.nl->slope.size() == outc) { P.folded = true; L.out_blob = P.tops[0]; }
+                if (P.nl->geti(0, 0) == outc) {           // the slope count of the .param: load_bin reads exactly that many
+                    if (!check_only) slope = P.nl->slope;
+                    P.folded = true; P.folded_into = (int)li; L.out_blob = P.tops[0];
+                }
             }
             const bool mfma = deconv ? (k == 4 && stride == 2 && pad == 1) : ((k == 3 || k == 5) && pad == k / 2 && (stride == 1 || stride == 2));
             if (mfma) {
@@ -183,9 +186,22 @@ static int graph_load(GraphNet& N, const std::string& base, bool check_only = fa
         const int pv = N.producer[A.bottoms[1]];
         if (pv < 0 || N.layers[pv].kind != G_INNER) continue;                      // the scale must be the pooled FC output
         P.se_y = A.bottoms[0]; P.se_scale = A.bottoms[1]; P.se_skip = B.bottoms[1];
-        A.folded = true; B.folded = true;
+        A.folded = true; B.folded = true; A.folded_into = B.folded_into = (int)li;
     }
     return 0;
+}
+
+// blob -> the layer whose launch writes it (an alias for Split / identity Interp), -1 where no launch does: the tops of the two
+// folded BinaryOps of an SE tail, and the top of a Convolution whose result goes to its PReLU's top
+static std::vector<int> graph_writers(const GraphNet& N) {
+    std::vector<int> wr(N.blob_names.size(), -1);
+    for (size_t li = 0; li < N.layers.size(); li++) {
+        const GLayer& L = N.layers[li];
+        if (L.folded) continue;
+        if (L.kind == G_SPLIT || L.kind == G_INPUT) { for (int t : L.tops) wr[t] = (int)li; }
+        else if (L.out_blob >= 0) wr[L.out_blob] = (int)li;
+    }
+    return wr;
 }
 
 // blob storage of one running instance of a net (per context; re-used while the geometry stays the same)

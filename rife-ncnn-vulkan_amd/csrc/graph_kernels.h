@@ -104,7 +104,7 @@ __global__ void kg_pointwise(GView a, GView out, int mode, float p0, float p1, c
     if (mode == 0) v = -v;
     else if (mode == 1) v = 1.f / (1.f + expf(-v));
     else if (mode == 2) { if (v < p0) v = p0; if (v > p1) v = p1; }
-    else if (mode == 3) { if (v < 0.f) v = v * p0; }
+    else if (mode == 3) { if (v < 0.f) v = p0 == 0.f ? 0.f : v * p0; }      // ncnn ReLU: max(x, 0) for slope 0 (+0, where x * 0 would be -0)
     else { if (v < 0.f) v = v * slopes[q]; }
     out.p[p * out.ld + q] = v;
 }
@@ -192,7 +192,8 @@ __global__ void kg_inner(const float* __restrict__ x, int n, const float* __rest
     out[o] = s;
 }
 
-// Direct convolution for the kernel sizes the MFMA kernels do not cover (5 x 5, stride 1 | 2, pad 2: the rife-HD IFNet).
+// Direct convolution for the kernel sizes the MFMA kernels do not cover: every odd size but 3 x 3 and 5 x 5 (1 x 1, 7 x 7, ...), stride 1 | 2,
+// pad k / 2, output channels a multiple of 4.  No shipped model needs it (the 5 x 5 convs of the rife-HD IFNet run on conv_mfma_kernel).
 // weights repacked [ky][kx][ic][oc]; thread = (pixel, 4 output channels); fp32 FMA-free (mul + add) accumulation.
 __global__ void kg_conv_direct(GView in, GView out, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ slope,
                                int k, int stride, int pad) {

@@ -3,23 +3,41 @@
 
 namespace rife {
 
-static int graph_run(const rife_hip& E, const GraphNet& N, GraphInst& I, hipStream_t st, const std::vector<std::pair<std::string, GView>>& bound,
-                     const std::vector<std::string>& wanted) {
-    const size_t nb = N.blob_names.size();
-    if (I.v.size() != nb) { I.v.assign(nb, GView{nullptr, 0, 0, 0, 0}); I.owned.assign(nb, nullptr); I.cap.assign(nb, 0); }
-    std::vector<char> have(nb, 0);
-    for (const auto& kv : bound) {
-        const int b = N.blob(kv.first);
-        if (b < 0) return fail(RIFE_HIP_EMODEL, N.name + ": no blob named " + kv.first);
-        I.v[b] = kv.second; have[b] = 1;
+// Blobs that no launch writes (graph_writers) can be neither bound nor wanted: a value bound inside a Convolution + PReLU pair or an SE tail would be
+// ignored by the launch that replaces its reader, and a wanted one would be read from a view nothing filled.  Refused by name, before any device work.
+static int graph_check_taps(const GraphNet& N, const std::vector<std::string>& bound, const std::vector<std::string>& wanted) {
+    const std::vector<int> writer = graph_writers(N);
+    std::vector<char> have(N.blob_names.size(), 0);
+    for (const std::string& n : bound) {
+        const int b = N.blob(n);
+        if (b < 0) return fail(RIFE_HIP_EMODEL, N.name + ": no blob named " + n);
+        if (N.producer[b] >= 0 && writer[b] < 0) return fail(RIFE_HIP_EINVAL, N.name + ": binding blob " + n + " would cut a fused pair or a squeeze-and-excitation tail");
+        have[b] = 1;
     }
-    std::vector<char> need(N.layers.size(), 0);
-    std::vector<int> stack;
     for (const std::string& w : wanted) {
         const int b = N.blob(w);
         if (b < 0) return fail(RIFE_HIP_EMODEL, N.name + ": no blob named " + w);
-        if (!have[b]) stack.push_back(b);
+        if (!have[b] && N.producer[b] >= 0 && writer[b] < 0)
+            return fail(RIFE_HIP_EINVAL, N.name + ": no launch writes blob " + w + " (its layer " + N.layers[N.producer[b]].nl->name + " is fused with its neighbour)");
     }
+    return 0;
+}
+
+static int graph_run(const rife_hip& E, const GraphNet& N, GraphInst& I, hipStream_t st, const std::vector<std::pair<std::string, GView>>& bound,
+                     const std::vector<std::string>& wanted) {
+    int rc;
+    {
+        std::vector<std::string> names;
+        for (const auto& kv : bound) names.push_back(kv.first);
+        if ((rc = graph_check_taps(N, names, wanted))) return rc;
+    }
+    const size_t nb = N.blob_names.size();
+    if (I.v.size() != nb) { I.v.assign(nb, GView{nullptr, 0, 0, 0, 0}); I.owned.assign(nb, nullptr); I.cap.assign(nb, 0); }
+    std::vector<char> have(nb, 0);
+    for (const auto& kv : bound) { const int b = N.blob(kv.first); I.v[b] = kv.second; have[b] = 1; }
+    std::vector<char> need(N.layers.size(), 0);
+    std::vector<int> stack;
+    for (const std::string& w : wanted) { const int b = N.blob(w); if (!have[b]) stack.push_back(b); }
     while (!stack.empty()) {
         const int b = stack.back(); stack.pop_back();
         const int li = N.producer[b];
@@ -28,7 +46,6 @@ static int graph_run(const rife_hip& E, const GraphNet& N, GraphInst& I, hipStre
         need[li] = 1;
         for (int bb : N.layers[li].bottoms) if (!have[bb]) stack.push_back(bb);
     }
-    int rc;
     for (size_t li = 0; li < N.layers.size(); li++) {
         if (!need[li]) continue;
         const GLayer& L = N.layers[li];
@@ -90,6 +107,7 @@ static int graph_run(const rife_hip& E, const GraphNet& N, GraphInst& I, hipStre
                 const int oh = (int)(x.h * fh), ow = (int)(x.w * fw);
                 if (oh == x.h && ow == x.w) { I.v[ob] = x; have[ob] = 1; continue; }      // ncnn returns the input blob itself
                 if (oh <= 0 || ow <= 0) return fail(RIFE_HIP_EMODEL, N.name + ": Interp to an empty blob at " + nl.name);
+                if (x.h < 2 || x.w < 2) return fail(RIFE_HIP_EMODEL, N.name + ": Interp from a blob one pixel wide or high at " + nl.name);      // kg_interp reads rows / columns s, s + 1 with s = in - 2 at the far edge
                 if ((rc = out_alloc(x.c, oh, ow))) return rc;
                 Timed t(E.prof, "g_interp", 0, st);
                 hipLaunchKernelGGL(kg_interp, grid2d(ow, oh), dim3(256), 0, st, x, I.v[ob]);
@@ -177,9 +195,9 @@ static int graph_run(const rife_hip& E, const GraphNet& N, GraphInst& I, hipStre
                 break;
             }
             case G_POOL: {
+                if (x.c % 4 || x.c > 1024) return fail(RIFE_HIP_EMODEL, N.name + ": global pooling needs a channel count that is a multiple of 4 (<= 1024) at " + nl.name);
                 if ((rc = out_alloc(x.c, 1, 1, true))) return rc;
                 const size_t npix = (size_t)x.h * x.w;
-                if (x.c % 4 || x.c > 1024) return fail(RIFE_HIP_EMODEL, N.name + ": global pooling needs a channel count that is a multiple of 4 (<= 1024) at " + nl.name);
                 const int nchunks = (int)std::min<size_t>(512, (npix + 511) / 512);
                 const size_t needp = (size_t)nchunks * x.c;
                 if (I.partial_cap < needp) {

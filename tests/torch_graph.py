@@ -38,9 +38,13 @@ def load_bin(layers, path):
             n, oc = int(p[2]), int(p[0])
             (tag,) = struct.unpack_from("<I", raw, pos)
             pos += 4
-            assert tag == 0x01306B47
-            l["weight"] = torch.from_numpy(np.frombuffer(raw, "<f2", n, pos).astype(np.float32).copy()).reshape(oc, -1)
-            pos += (n * 2 + 3) // 4 * 4
+            if tag == 0x01306B47:
+                l["weight"] = torch.from_numpy(np.frombuffer(raw, "<f2", n, pos).astype(np.float32).copy()).reshape(oc, -1)
+                pos += (n * 2 + 3) // 4 * 4
+            else:
+                assert tag == 0
+                l["weight"] = torch.from_numpy(np.frombuffer(raw, "<f4", n, pos).copy()).reshape(oc, -1)
+                pos += n * 4
             l["bias"] = None
             if int(p.get(1, 0)):
                 l["bias"] = torch.from_numpy(np.frombuffer(raw, "<f4", oc, pos).copy())
@@ -55,14 +59,14 @@ def load_bin(layers, path):
 def warp(img, flow):
     """img (C,H,W), flow (2,H,W): literal restatement of the reference's CPU Warp::forward."""
     C, H, W = img.shape
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=img.dtype), torch.arange(W, dtype=img.dtype), indexing="ij")
     sx, sy = xs + flow[0], ys + flow[1]
     x0 = torch.floor(sx).to(torch.int64)
     y0 = torch.floor(sy).to(torch.int64)
     x1, y1 = x0 + 1, y0 + 1
     x0c, x1c = x0.clamp(0, W - 1), x1.clamp(0, W - 1)
     y0c, y1c = y0.clamp(0, H - 1), y1.clamp(0, H - 1)
-    alpha, beta = sx - x0c.to(torch.float32), sy - y0c.to(torch.float32)
+    alpha, beta = sx - x0c.to(img.dtype), sy - y0c.to(img.dtype)
     flat = img.reshape(C, -1)
     v0 = flat[:, (y0c * W + x0c).reshape(-1)].reshape(C, H, W)
     v1 = flat[:, (y0c * W + x1c).reshape(-1)].reshape(C, H, W)
@@ -74,9 +78,15 @@ def warp(img, flow):
 
 
 class TorchNet:
-    def __init__(self, param_path, bin_path):
+    def __init__(self, param_path, bin_path, dtype=torch.float32):
+        """dtype: the type every layer computes in (weights, biases and slopes are the file's fp32 values converted to it; inputs must come in it)."""
         self.layers = ncnn_param.parse(param_path)
         load_bin(self.layers, bin_path)
+        self.dtype = dtype
+        for l in self.layers:
+            for k in ("weight", "bias", "slope"):
+                if l.get(k) is not None:
+                    l[k] = l[k].to(dtype)
         self.producer = {}
         for l in self.layers:
             for t in l["tops"]:
@@ -120,7 +130,7 @@ class TorchNet:
             elif t == "PixelShuffle":
                 y = F.pixel_shuffle(x[0][None], int(p[0]))[0]
             elif t == "ReLU":
-                y = F.leaky_relu(x[0], p.get(0, 0.0))
+                y = torch.where(x[0] < 0, x[0] * float(np.float32(p.get(0, 0.0))), x[0])
             elif t == "PReLU":
                 y = F.prelu(x[0][None], l["slope"])[0]
             elif t == "Sigmoid":
@@ -138,13 +148,13 @@ class TorchNet:
                 y = -x[0]
             elif t == "BinaryOp":
                 op = int(p.get(0, 0))
-                b = x[1] if len(x) > 1 else torch.tensor(np.float32(p[2]))
+                b = x[1] if len(x) > 1 else torch.tensor(np.float32(p[2])).to(x[0].dtype)
                 if len(x) > 1 and b.dim() == 1 and x[0].dim() == 3:
                     b = b[:, None, None]                        # per-channel operand (SE scale)
                 y = {0: lambda: x[0] + b, 1: lambda: x[0] - b, 2: lambda: x[0] * b, 3: lambda: x[0] / b, 7: lambda: b - x[0]}[op]()
             elif t == "Eltwise":
-                c = a[1]
-                y = x[0] * np.float32(c[0]) + x[1] * np.float32(c[1])
+                c = a.get(1)
+                y = x[0] * float(np.float32(c[0])) + x[1] * float(np.float32(c[1])) if c else x[0] + x[1]
             elif t == "rife.Warp":
                 y = warp(x[0], x[1])
             else:
@@ -155,8 +165,10 @@ class TorchNet:
     @staticmethod
     def _act(y, p, a):
         act = int(p.get(9, 0))
+        if act == 1:
+            return torch.relu(y)
         if act == 2:
-            return F.leaky_relu(y, a[10][0])
+            return torch.where(y < 0, y * float(np.float32(a[10][0])), y)
         if act == 4:
             return torch.sigmoid(y)
         assert act == 0

@@ -569,6 +569,19 @@ def write_bin(path, weights):
                 f.write(b.astype("<f4").tobytes())
 
 
+def write_bin_f32(path, weights):
+    """write_bin with raw fp32 weights (ncnn storage tag 0): values that are not fp16 numbers survive, so the loaders take their fp32 kernel paths."""
+    with open(path, "wb") as f:
+        for kind, w, b, s in weights:
+            if kind == "prelu":
+                f.write(s.astype("<f4").tobytes())
+                continue
+            f.write(struct.pack("<I", 0))
+            f.write(w.astype("<f4").tobytes())
+            if b is not None:
+                f.write(b.astype("<f4").tobytes())
+
+
 def generate(outdir, family="rife-v4.6", seed=0x51FE, real_contextnet=None, flow_gain=1.0):
     """Write <outdir>/{flownet,...}.{param,bin}.  `real_contextnet`: optional path to the reference's real
     rife-v2.3 contextnet.bin (present in the reference tree); copied verbatim when given.  `flow_gain` multiplies the gain of the flow heads
