@@ -368,8 +368,8 @@ int rife_hip_process_frames_motion(const rife_hip_t* r, const rife_hip_frame_t* 
  *   Scope       that of motion export; the families and modes it refuses get -RIFE_HIP_ENOSYS with a message that names them and the words "apply motion",
  *               before anything is written.
  *   Timestep    0 / 1: no network pass and no arithmetic - the frame as for the _px call, the planes of frame 0 / frame 1 copied, integer samples clamped to maxval.
- * Out of scope: interleaved multi-channel samples (RGB48, RGBA64), planes at another resolution than the motion (4:2:0 chroma, proxy upscaling), the batch calls,
- * image (strided-frame) calls with apply, other families for the combined calls, the command line. */
+ * Out of scope: interleaved multi-channel samples (RGB48, RGBA64), the batch calls, image (strided-frame) calls with apply, other families for the combined calls,
+ * the command line.  Planes at half or twice the motion's resolution: the next section. */
 #define RIFE_HIP_SAMPLE_U8  0
 #define RIFE_HIP_SAMPLE_U16 1   /* native byte order */
 #define RIFE_HIP_SAMPLE_F16 2   /* IEEE binary16 */
@@ -394,6 +394,60 @@ int rife_hip_process_apply(const rife_hip_t* r, const void* in0, const void* in1
 /* the same in device memory (d_out is required); stream semantics as for the device _px call */
 int rife_hip_process_device_apply(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt,
                                   const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, int wp, int hp, const rife_hip_planes_t* planes_out, void* hip_stream);
+
+/* ---- apply motion at another resolution: planes at half or twice the motion's size - 4:2:0 / 4:2:2 chroma, proxy upscaling (absent in the reference) ----------------
+ * 12- and 16-bit Y'CbCr is 4:2:0 or 4:2:2 almost everywhere, and estimating on a half-size proxy costs a quarter of the arithmetic.  Both are the apply kernel with a
+ * different motion fetch in front of it: the motion box-averaged over the chroma block, or interpolated up by two.  A SET is three plane descriptors p0, p1, out
+ * (the rules of the apply section hold among them: they agree in w, h, n, sample and maxval), a pair of shifts and an extent; a call names a motion field of mw x mh
+ * (F32 or F16, both buffers, the rules of rife_hip_motion_check for mw x mh) and 1..4 sets, which may differ in everything: sample type, maxval, n, shift, extent.
+ * The admitted shift pairs and the plane size ws x hs each requires:
+ *     (0, 0)     mw x mh                                          the apply calls above, byte for byte
+ *     (-1, -1)   (mw + 1) / 2 x (mh + 1) / 2                      4:2:0 chroma
+ *     (-1, 0)    (mw + 1) / 2 x mh                                4:2:2 chroma
+ *     (+1, +1)   ws in {2 mw - 1, 2 mw}, hs in {2 mh - 1, 2 mh}   proxy upscaling
+ * Any other pair, or a plane size that does not fit, is -RIFE_HIP_EINVAL with the fault named.  The shift is explicit on purpose: at mw = 1 a plane of width 1 fits
+ * shift 0 and shift -1, and the two give different results.
+ * The result of a set is the apply definition above, unchanged, in the planes' OWN coordinates (w, h = ws, hs; the extent in plane pixels) on a resampled motion
+ * flow', mask' of ws x hs, computed in fp32 from the motion (F16 widened first, exactly), every product and sum rounded separately (no fused multiply-add), in
+ * exactly this order; M stands for any of dx0, dy0, dx1, dy1, m:
+ *   shift -1 on x   c0 = 2x, c1 = min(2x + 1, mw - 1);   shift -1 on y   r0 = 2y, r1 = min(2y + 1, mh - 1)      (an odd edge is the mean of the samples that exist)
+ *   (-1, -1)   s = ((M[r0][c0] + M[r0][c1]) + (M[r1][c0] + M[r1][c1])) * 0.25f;     dx' = s.dx * 0.5f, dy' = s.dy * 0.5f, m' = s.m
+ *   (-1, 0)    s = (M[y][c0] + M[y][c1]) * 0.5f;                                    dx' = s.dx * 0.5f, dy' = s.dy,        m' = s.m
+ *   (+1, +1)   a x2 bilinear resize with half-pixel centres and edge clamping, x first, then y:
+ *              j = x >> 1, jn = (x & 1) ? min(j + 1, mw - 1) : max(j - 1, 0);  i, in from y and mh likewise;  H(r) = M[r][j] * 0.75f + M[r][jn] * 0.25f;
+ *              s = H(i) * 0.75f + H(in) * 0.25f;                                    dx' = s.dx * 2.f, dy' = s.dy * 2.f, m' = s.m
+ *   (0, 0)     the motion itself
+ * This is the engine's own chroma convention (replicated up and box-averaged down, no net shift, siting tags ignored).  Frame semantics on chroma is the extent
+ * (wp / 2, hp / 2) of rife_hip_padded_size, which is always even; for shift +1 it is (2 wp, 2 hp) of the proxy's padded size; edge semantics is 0, 0.  A NaN or Inf
+ * motion sample poisons the plane pixels whose fetch neighbourhood holds it, and nothing else.
+ * Rules (rife_hip_apply_set_check states them for one set; every sets call repeats them per set, the message prefixed "set k:", before it touches anything; a
+ * violation is -RIFE_HIP_EINVAL): nsets in 1..4; each descriptor passes rife_hip_planes_check; the three agree; the shift pair is admitted and the plane size fits
+ * mw, mh; the extent is 0, 0 or at least the plane size with wp * hp <= 2^27.  Argument checks come before "no HIP device".
+ * The two apply_*_sets calls need an engine only for its device and stream: they work before rife_hip_load and on every family and mode.  One launch per set, the
+ * motion read once per set.
+ * The two process_*_apply_sets calls have motion export's scope and refuse everything else with -RIFE_HIP_ENOSYS and the words "apply motion", before anything is
+ * written.  They are byte for byte rife_hip_process_motion / rife_hip_process_device_motion (F32) followed by the _sets apply call: the motion, of the frame size
+ * w x h, is held in the workspace's tight device buffers; one apply launch per set on the same stream.  out may be NULL in the host call only.  At timestep 0 / 1
+ * there is no network pass and no arithmetic: every set is a copy of its frame-0 / frame-1 planes, integer samples clamped to maxval.
+ * Out of scope: making the proxy, shifts beyond +-1, mixed shifts other than (-1, 0), exporting the resampled motion, semi-planar or interleaved chroma, the batch and
+ * image calls, the command line, several sets in one launch. */
+typedef struct rife_hip_apply_set {
+    const rife_hip_planes_t* p0; const rife_hip_planes_t* p1; const rife_hip_planes_t* out;
+    int shift_x, shift_y;   /* the planes relative to the motion, per axis: 0 same size, -1 half (rounded up), +1 double */
+    int wp, hp;             /* extent in the planes' OWN pixels; 0, 0 = the plane size */
+} rife_hip_apply_set_t;
+int rife_hip_apply_set_check(const rife_hip_apply_set_t* s, int mw, int mh);   /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
+/* planes and motion in device memory: one launch per set; stream semantics as for the device _px call */
+int rife_hip_apply_device_motion_sets(const rife_hip_t* r, int nsets, const rife_hip_apply_set_t* sets, const rife_hip_motion_t* device_motion, int mw, int mh,
+                                      void* hip_stream);
+/* everything in host memory: upload, the launches, download */
+int rife_hip_apply_motion_sets(const rife_hip_t* r, int nsets, const rife_hip_apply_set_t* sets, const rife_hip_motion_t* host_motion, int mw, int mh);
+/* estimate on in0 / in1 (w x h = the motion size), apply to every set in the same pass; host memory; out may be NULL (the frame is not wanted) */
+int rife_hip_process_apply_sets(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, int nsets,
+                                const rife_hip_apply_set_t* sets);
+/* the same in device memory (d_out is required); stream semantics as for the device _px call */
+int rife_hip_process_device_apply_sets(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt, int nsets,
+                                       const rife_hip_apply_set_t* sets, void* hip_stream);
 
 const char* rife_hip_last_error(void);
 

@@ -144,6 +144,11 @@ int rife_hip_op_tail_motion(int gpuid, int kernel, int pixfmt, int w, int h, con
  * force_scalar: 0 = the host's choice, 1 = the one-pixel-per-lane form.  The rules of rife_hip_apply_motion hold (-RIFE_HIP_EINVAL before anything is uploaded). */
 int rife_hip_op_apply(int gpuid, const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_motion_t* host_motion, int wp, int hp,
                       const rife_hip_planes_t* out, int force_scalar);
+/* op_apply_scaled: the scaled apply kernel alone (csrc/apply_scaled.h; include/rife_hip.h "apply motion at another resolution"), ONE launch of one set on planes and
+ * a motion of mw x mh in HOST memory, uploaded as op_apply uploads them (pitches and pointer alignment modulo 16 kept; the output planes come back with every byte
+ * the kernel did not write as it went in).  A set of shift 0, 0 is the launch of op_apply.  force_scalar: 0 = the host's choice, 1 = the one-pixel-per-lane form.
+ * The rules of the sets calls hold (-RIFE_HIP_EINVAL before anything is uploaded). */
+int rife_hip_op_apply_scaled(int gpuid, const rife_hip_apply_set_t* set, const rife_hip_motion_t* host_motion, int mw, int mh, int force_scalar);
 
 /* ---- the generic layer-wise graph executor (csrc/graph_exec.h, graph_run.h, graph_kernels.h: the v1 family) on any .param / .bin pair, one graph_run per call.
  * graph_plan needs no device: it parses <base>.param as rife_hip_graph_check does and writes what the loader settled on, one line per layer, tab-separated:

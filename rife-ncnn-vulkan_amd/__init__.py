@@ -37,6 +37,7 @@ C_ABI_SYMBOLS = [
     "rife_hip_set_precision", "rife_hip_precision",
     "rife_hip_motion_check", "rife_hip_process_motion", "rife_hip_process_device_motion", "rife_hip_process_frames_motion",
     "rife_hip_planes_check", "rife_hip_padded_size", "rife_hip_apply_device_motion", "rife_hip_apply_motion", "rife_hip_process_apply", "rife_hip_process_device_apply",
+    "rife_hip_apply_set_check", "rife_hip_apply_device_motion_sets", "rife_hip_apply_motion_sets", "rife_hip_process_apply_sets", "rife_hip_process_device_apply_sets",
 ]
 # include/rife_hip.h RIFE_HIP_PRECISION_*: FULL = two f16 products per weight tap of the residual trunks (fp32-equivalent), FAST = one, the skip at full precision
 PRECISION_FULL, PRECISION_FAST = 0, 1
@@ -66,7 +67,7 @@ _SAMPLE_OF = {np.dtype(v): k for k, v in _SAMPLE_DTYPE.items()}
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
-                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply",
+                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply", "rife_hip_op_apply_scaled",
                     "rife_hip_graph_plan", "rife_hip_graph_eval"]
 # rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
 TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
@@ -91,6 +92,12 @@ class rife_hip_planes(ctypes.Structure):
     """rife_hip_planes_t of include/rife_hip.h: n (1..4) planes of w x h samples of one type, a pointer and a pitch in BYTES each; maxval for integer samples, else 0."""
     _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("n", ctypes.c_int), ("sample", ctypes.c_int), ("maxval", ctypes.c_int), ("plane", ctypes.c_void_p * 4),
                 ("pitch", ctypes.c_ssize_t * 4)]
+
+
+class rife_hip_apply_set(ctypes.Structure):
+    """rife_hip_apply_set_t of include/rife_hip.h: three plane descriptors, the shift of the planes relative to the motion per axis and the extent in plane pixels."""
+    _fields_ = [("p0", ctypes.POINTER(rife_hip_planes)), ("p1", ctypes.POINTER(rife_hip_planes)), ("out", ctypes.POINTER(rife_hip_planes)),
+                ("shift_x", ctypes.c_int), ("shift_y", ctypes.c_int), ("wp", ctypes.c_int), ("hp", ctypes.c_int)]
 
 
 def build(force=False):
@@ -168,8 +175,15 @@ def _load(path, with_test_surface):
     L.rife_hip_apply_motion.argtypes = [vp, pp, pp, mp, ci, ci, pp]
     L.rife_hip_process_apply.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, pp, pp, ci, ci, pp]
     L.rife_hip_process_device_apply.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, pp, pp, ci, ci, pp, vp]
+    sp = ctypes.POINTER(rife_hip_apply_set)
+    L.rife_hip_apply_set_check.argtypes = [sp, ci, ci]
+    L.rife_hip_apply_device_motion_sets.argtypes = [vp, ci, sp, mp, ci, ci, vp]
+    L.rife_hip_apply_motion_sets.argtypes = [vp, ci, sp, mp, ci, ci]
+    L.rife_hip_process_apply_sets.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, ci, sp]
+    L.rife_hip_process_device_apply_sets.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, ci, sp, vp]
     if with_test_surface:
         L.rife_hip_op_apply.argtypes = [ci, pp, pp, mp, ci, ci, pp, ci]
+        L.rife_hip_op_apply_scaled.argtypes = [ci, sp, mp, ci, ci, ci]
         L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
         L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
         L.rife_hip_v4_extract_flow.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp]
@@ -560,6 +574,53 @@ def _motion_in(w, h, flow, mask):
     return d
 
 
+def _packed_pair(in0image, in1image, pixfmt):
+    """The two frames of a host call as contiguous arrays and their pixel format: (h, w, 3) uint8 by default, else a packed RGB format as process_motion() takes it."""
+    px = _pix_of(in0image, pixfmt)
+    if px is None:
+        a = np.ascontiguousarray(in0image, dtype=np.uint8); b = np.ascontiguousarray(in1image, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3 or a.shape != b.shape:
+            raise ValueError("frames must be (h, w, 3) uint8 arrays of equal size")
+        return a, b, PIX_RGB8
+    if _pix_of(in1image, px) != px or in1image.shape != in0image.shape:
+        raise ValueError("both frames must have the same pixel format and size")
+    return np.ascontiguousarray(in0image), np.ascontiguousarray(in1image), px
+
+
+def apply_set_desc(planes0, planes1, planes_out, shift=(0, 0), extent=None):
+    """A rife_hip_apply_set from three rife_hip_planes descriptors (planes_desc() for device planes, planes_of() for host planes): shift = the planes relative to the
+    motion per axis, (0, 0), (-1, -1) 4:2:0 chroma, (-1, 0) 4:2:2 chroma or (1, 1) proxy upscaling; extent = (wp, hp) in the planes' own pixels, None = the plane size."""
+    wp, hp = extent if extent is not None else (0, 0)
+    s = rife_hip_apply_set(ctypes.pointer(planes0), ctypes.pointer(planes1), ctypes.pointer(planes_out), int(shift[0]), int(shift[1]), int(wp), int(hp))
+    s._keep = (planes0, planes1, planes_out)
+    return s
+
+
+def apply_set(planes0, planes1, shift=(0, 0), maxval=None, extent=None, out=None):
+    """One set of a sets call over HOST planes, as planes_of takes them (include/rife_hip.h "apply motion at another resolution"); out: planes to fill in place, None =
+    new tight arrays.  The output planes are `.planes` of the set."""
+    d0 = planes_of(planes0, maxval, "planes0"); d1 = planes_of(planes1, maxval, "planes1")
+    do, res = _planes_out(d0, out)
+    s = apply_set_desc(d0, d1, do, shift, extent)
+    s.planes = res
+    return s
+
+
+def apply_set_check(s, mw, mh):
+    """rife_hip_apply_set_check (host only): raises RifeError with the fault of set `s` against a motion of mw x mh."""
+    _check(lib().rife_hip_apply_set_check(ctypes.byref(s), int(mw), int(mh)), "apply_set_check")
+
+
+def _set_array(sets):
+    """1..n rife_hip_apply_set -> a C array (the count is checked by the library)."""
+    sets = list(sets)
+    arr = (rife_hip_apply_set * max(len(sets), 1))()
+    for k, s in enumerate(sets):
+        ctypes.memmove(ctypes.byref(arr[k]), ctypes.byref(s), ctypes.sizeof(rife_hip_apply_set))
+    arr._keep = sets
+    return len(sets), arr
+
+
 class Frame:
     """A frame resident in device memory (rife_hip_frame_t): upload once, use as either side of any number of pairs."""
 
@@ -892,6 +953,46 @@ class RIFE:
         wp, hp = extent if extent is not None else (0, 0)
         _check(self._L.rife_hip_process_device_apply(self._h, d_in0, d_in1, int(w), int(h), float(timestep), d_out, int(pixfmt), ctypes.byref(planes0), ctypes.byref(planes1),
                                                      int(wp), int(hp), ctypes.byref(planes_out), stream), "process_device_apply", self._L)
+
+    def apply_motion_sets(self, sets, flow, mask):
+        """rife_hip_apply_motion_sets (include/rife_hip.h "apply motion at another resolution"): one motion field flow (mh, mw, 4), mask (mh, mw), float32 or float16,
+        applied to 1..4 apply_set()s whose planes are the motion's size, half of it (4:2:0 / 4:2:2 chroma) or twice it (proxy upscaling).  Returns the list of the
+        sets' output plane tuples.  Needs no loaded model."""
+        if not isinstance(mask, np.ndarray) or mask.ndim != 2:
+            raise ValueError("mask is a (mh, mw) array")
+        mh, mw = mask.shape
+        m = _motion_in(mw, mh, flow, mask)
+        n, arr = _set_array(sets)
+        _check(self._L.rife_hip_apply_motion_sets(self._h, n, arr, ctypes.byref(m), mw, mh), "apply_motion_sets", self._L)
+        return [s.planes for s in arr._keep]
+
+    def apply_device_motion_sets(self, sets, motion, mw, mh, stream=None):
+        """rife_hip_apply_device_motion_sets: apply_set_desc() sets over DEVICE planes and a motion_desc() of DEVICE buffers of mw x mh; one launch per set on `stream`
+        (hipStream_t as int; None = a stream of the engine's, synchronised before returning)."""
+        n, arr = _set_array(sets)
+        _check(self._L.rife_hip_apply_device_motion_sets(self._h, n, arr, ctypes.byref(motion), int(mw), int(mh), stream), "apply_device_motion_sets", self._L)
+
+    def process_apply_sets(self, in0image, in1image, timestep, sets, outimage=None, pixfmt=None, want_frame=True):
+        """rife_hip_process_apply_sets: estimate the motion on the frames in0image / in1image (any packed RGB format, as process_motion()) and apply it to every
+        apply_set() of `sets` in the same pass, the motion staying in device memory: (frame, [planes of each set]).  want_frame=False: the frame is not downloaded and
+        None comes back in its place.  Byte for byte process_motion() followed by apply_motion_sets()."""
+        a, b, px = _packed_pair(in0image, in1image, pixfmt)
+        h, w = a.shape[:2]
+        frame = None
+        if want_frame:
+            frame = outimage if outimage is not None else np.empty_like(a)
+            if not isinstance(frame, np.ndarray) or frame.shape != a.shape or frame.dtype != a.dtype or not frame.flags.c_contiguous or not frame.flags.writeable:
+                raise ValueError("outimage must be a writable contiguous array of the frames' dtype and shape")
+        n, arr = _set_array(sets)
+        _check(self._L.rife_hip_process_apply_sets(self._h, _p(a), _p(b), w, h, float(timestep), _p(frame), px, n, arr), "process_apply_sets", self._L)
+        return frame, [s.planes for s in arr._keep]
+
+    def process_device_apply_sets(self, d_in0, d_in1, w, h, timestep, d_out, sets, stream=None, pixfmt=PIX_RGB8):
+        """rife_hip_process_device_apply_sets: device pointers (ints) to tight frames of `pixfmt` and apply_set_desc() sets over DEVICE planes; enqueues on `stream`
+        (hipStream_t as int; None = the engine's own stream, synchronised before returning)."""
+        n, arr = _set_array(sets)
+        _check(self._L.rife_hip_process_device_apply_sets(self._h, d_in0, d_in1, int(w), int(h), float(timestep), d_out, int(pixfmt), n, arr, stream),
+               "process_device_apply_sets", self._L)
 
     def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
         """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
@@ -1238,6 +1339,16 @@ def op_apply(planes0, planes1, flow, mask, out, maxval=None, extent=None, force_
     m = _motion_in(d0.w, d0.h, flow, mask)
     wp, hp = extent if extent is not None else (0, 0)
     _check(testlib().rife_hip_op_apply(int(gpuid), ctypes.byref(d0), ctypes.byref(d1), ctypes.byref(m), int(wp), int(hp), ctypes.byref(do), int(force_scalar)), "op_apply", testlib())
+    return out
+
+
+def op_apply_scaled(planes0, planes1, flow, mask, out, shift, maxval=None, extent=None, force_scalar=0, gpuid=0):
+    """rife_hip_op_apply_scaled (test build): ONE launch of one set - host planes of the size `shift` demands of the motion flow (mh, mw, 4), mask (mh, mw); row-strided
+    views of either are uploaded with their pitch.  `out` planes are written in place; every byte the kernel did not write keeps its value."""
+    mh, mw = mask.shape
+    s = apply_set(planes0, planes1, shift, maxval, extent, out)
+    m = _motion_in(mw, mh, flow, mask)
+    _check(testlib().rife_hip_op_apply_scaled(int(gpuid), ctypes.byref(s), ctypes.byref(m), mw, mh, int(force_scalar)), "op_apply_scaled", testlib())
     return out
 
 

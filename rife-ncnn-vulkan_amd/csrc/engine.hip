@@ -21,6 +21,7 @@
 #include <memory>
 #include <atomic>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -44,7 +45,9 @@
 #include "image_check.h"
 #include "motion_check.h"
 #include "apply_check.h"
+#include "apply_set_check.h"
 #include "apply_motion.h"
+#include "apply_scaled.h"
 #include "elementwise_v2.h"
 #include "stem_fused.h"
 #include "stem_fused_v2.h"
@@ -72,3 +75,4 @@
 #include "engine_abi.h"
 #include "engine_image.h"
 #include "engine_apply.h"
+#include "engine_apply_sets.h"

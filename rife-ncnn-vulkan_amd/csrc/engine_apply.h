@@ -5,6 +5,7 @@
 //   apply_motion          host planes and motion: tight device copies for the call's life, the launch, the planes back; needs no model and no workspace
 //   process_device_apply  the motion pass with F32 motion into the workspace's tight motion buffers (motion_stage), then the launch on the same stream
 //   process_apply         the same from host memory: frames and planes staged through workspace buffers (Ctx::ap_planes, allocated at the first such call)
+//                         (both: engine_apply_sets.h's combined calls with one set of shift 0, 0)
 // The rules and their words: csrc/apply_check.h.
 
 // 0, or -RIFE_HIP_EINVAL; then "no HIP device at all" (-RIFE_HIP_ENODEV) before anything looks at the engine
@@ -144,89 +145,25 @@ static int apply_motion_stage(Ctx& c, MotionArgs& mo) {
     return motion_stage(c, want, mo);
 }
 
+// the two combined calls are the sets calls of engine_apply_sets.h with ONE set of shift 0, 0 (the same staging, the same launch of k_apply_motion, the same copies)
+static int rife_hip_process_apply_sets_impl(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out, int pixfmt, int nsets,
+                                            const rife_hip_apply_set_t* sets);
+static int rife_hip_process_device_apply_sets_impl(const rife_hip_t* E, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt, int nsets,
+                                                   const rife_hip_apply_set_t* sets, void* hip_stream);
+static rife_hip_apply_set_t apply_one_set(const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_planes_t* pout, int wp, int hp) {
+    rife_hip_apply_set_t s{};
+    s.p0 = p0; s.p1 = p1; s.out = pout; s.wp = wp; s.hp = hp;
+    return s;
+}
 static int rife_hip_process_apply_impl(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out, int pixfmt,
                                        const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, int wp, int hp, const rife_hip_planes_t* pout) {
-    int rc;
-    if ((rc = process_common(E, w, h, timestep))) return rc;
-    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
-    if ((rc = apply_supported(E))) return rc;
-    const size_t nbytes = frame_bytes(w, h, pixfmt);
-    if (timestep == 0.f || timestep == 1.f) {                             // no pass, no arithmetic: the frame as rife_hip_process_px returns it, the planes of that frame
-        const uint8_t* src = timestep == 0.f ? in0 : in1;
-        if (out) { if (pix_deep(pixfmt)) canon10_host(out, src, w, h, pixfmt); else std::memmove(out, src, nbytes); }
-        apply_copy_host(timestep == 0.f ? *p0 : *p1, *pout);
-        return 0;
-    }
-    if ((rc = check_device(E->gpuid))) return rc;
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, pixfmt);
-    if (!rc) {
-        Ctx& C = *c;
-        MotionArgs mo;
-        rc = apply_motion_stage(C, mo);
-        const size_t need = apply_stage_bytes(*p0);
-        if (!rc && C.ap_bytes < need) { C.ap_planes = nullptr; C.ap_bytes = 0; if (!(rc = dalloc(C, C.ap_planes, need))) C.ap_bytes = need; }
-        hipError_t e = hipSuccess;
-        if (!rc) {
-            const ApplyStage s = apply_stage(C.ap_planes, *p0);
-            {
-                const bool token = process_switches().h2d_token;      // the upload token of enqueue_host_pair
-                std::unique_lock<std::mutex> g(E->h2d_mu, std::defer_lock);
-                if (token) g.lock();
-                e = hipMemcpyAsync(C.d_in0, in0, nbytes, hipMemcpyHostToDevice, C.stream);
-                if (e == hipSuccess) e = hipMemcpyAsync(C.d_in1, in1, nbytes, hipMemcpyHostToDevice, C.stream);
-                if (e == hipSuccess) e = apply_planes_copy(s.d0, *p0, hipMemcpyHostToDevice, C.stream);
-                if (e == hipSuccess) e = apply_planes_copy(s.d1, *p1, hipMemcpyHostToDevice, C.stream);
-                if (e == hipSuccess && token) e = hipStreamSynchronize(C.stream);
-            }
-            if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
-            if (!rc) rc = run_pass(E, C, C.d_in0, C.d_in1, w, h, timestep, C.d_out, &mo);
-            if (!rc) rc = apply_launch(E, C.stream, apply_args(s.d0, s.d1, s.dout, mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32, wp, hp), p0->sample);
-            if (!rc && out && (e = hipMemcpyAsync(out, C.d_out, nbytes, hipMemcpyDeviceToHost, C.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
-            if (!rc && (e = apply_planes_copy(*pout, s.dout, hipMemcpyDeviceToHost, C.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
-        }
-    }
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+    const rife_hip_apply_set_t s = apply_one_set(p0, p1, pout, wp, hp);
+    return rife_hip_process_apply_sets_impl(E, in0, in1, w, h, timestep, out, pixfmt, 1, &s);
 }
-
 static int rife_hip_process_device_apply_impl(const rife_hip_t* E, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt,
                                               const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, int wp, int hp, const rife_hip_planes_t* pout, void* hip_stream) {
-    int rc;
-    if ((rc = process_common(E, w, h, timestep))) return rc;
-    if ((rc = pixfmt_supported(E, pixfmt))) return rc;
-    if ((rc = apply_supported(E))) return rc;
-    if ((rc = check_device(E->gpuid))) return rc;
-    Ctx* c;
-    {      // the stream's workspace, as in rife_hip_process_device_impl
-        std::lock_guard<std::mutex> g(E->mu);
-        auto ps = E->part_streams.find(hip_stream);
-        if (ps != E->part_streams.end()) tl_cu_budget = ps->second;
-        auto& slot = E->stream_ctx[hip_stream];
-        if (!slot) {
-            slot.reset(new Ctx);
-            if (hip_stream) slot->stream = (hipStream_t)hip_stream;
-            else {
-                if (hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
-                slot->own_stream = true;
-            }
-        }
-        c = slot.get();
-    }
-    std::lock_guard<std::mutex> use(c->use);
-    if (timestep == 0.f || timestep == 1.f) {
-        if ((rc = copy_frame_device(c->stream, timestep == 0.f ? d_in0 : d_in1, d_out, w, h, pixfmt))) return rc;
-        if ((rc = apply_copy_device(c->stream, timestep == 0.f ? *p0 : *p1, *pout))) return rc;
-    } else {
-        MotionArgs mo;
-        if ((rc = ensure_ctx(*c, w, h, pixfmt, E->pad()))) return rc;
-        if ((rc = apply_motion_stage(*c, mo))) return rc;
-        if ((rc = run_pass(E, *c, static_cast<const uint8_t*>(d_in0), static_cast<const uint8_t*>(d_in1), w, h, timestep, static_cast<uint8_t*>(d_out), &mo))) return rc;
-        if ((rc = apply_launch(E, c->stream, apply_args(*p0, *p1, *pout, mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32, wp, hp), p0->sample))) return rc;
-    }
-    if (!hip_stream) HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    const rife_hip_apply_set_t s = apply_one_set(p0, p1, pout, wp, hp);
+    return rife_hip_process_device_apply_sets_impl(E, d_in0, d_in1, w, h, timestep, d_out, pixfmt, 1, &s, hip_stream);
 }
 
 extern "C" {

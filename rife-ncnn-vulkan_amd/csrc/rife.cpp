@@ -207,6 +207,38 @@ int RIFE::process_apply(const void* in0, const void* in1, int w, int h, float ti
     return ret;
 }
 
+// weak like the apply calls
+extern "C" int rife_hip_apply_motion_sets(const rife_hip_t* r, int nsets, const rife_hip_apply_set_t* sets, const rife_hip_motion_t* host_motion, int mw, int mh)
+    __attribute__((weak));
+extern "C" int rife_hip_process_apply_sets(const rife_hip_t* r, const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, int nsets,
+                                           const rife_hip_apply_set_t* sets) __attribute__((weak));
+
+int RIFE::apply_motion_sets(int nsets, const rife_hip_apply_set_t* sets, const rife_hip_motion_t& motion, int mw, int mh) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_apply_motion_sets)
+    {
+        fprintf(stderr, "RIFE::apply_motion_sets: this engine has no apply motion at another resolution\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_apply_motion_sets(engine, nsets, sets, &motion, mw, mh);
+    if (ret) fprintf(stderr, "RIFE::apply_motion_sets: %s\n", rife_hip_last_error());
+    return ret;
+}
+
+int RIFE::process_apply_sets(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, int nsets, const rife_hip_apply_set_t* sets) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_process_apply_sets)
+    {
+        fprintf(stderr, "RIFE::process_apply_sets: this engine has no apply motion at another resolution\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_process_apply_sets(engine, in0, in1, w, h, timestep, out, pixfmt, nsets, sets);
+    if (ret) fprintf(stderr, "RIFE::process_apply_sets: %s\n", rife_hip_last_error());
+    return ret;
+}
+
 rife_hip_frame* RIFE::upload_yuv(const void* frame, int w, int h, int pixfmt) const
 {
     if (!engine || !frame) return 0;

@@ -66,6 +66,10 @@ public:
     int apply_motion(const rife_hip_planes_t& p0, const rife_hip_planes_t& p1, const rife_hip_motion_t& motion, int wp, int hp, const rife_hip_planes_t& out) const;
     int process_apply(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, const rife_hip_planes_t& p0, const rife_hip_planes_t& p1,
                       int wp, int hp, const rife_hip_planes_t& planes_out) const;
+    // The same for planes at half or twice the motion's resolution (include/rife_hip.h "apply motion at another resolution"): 1..4 sets of three plane descriptors
+    // with a shift pair each - (0, 0), (-1, -1) 4:2:0 chroma, (-1, 0) 4:2:2 chroma, (1, 1) proxy upscaling - on a motion of mw x mh (process_apply_sets: w x h).
+    int apply_motion_sets(int nsets, const rife_hip_apply_set_t* sets, const rife_hip_motion_t& motion, int mw, int mh) const;
+    int process_apply_sets(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, int nsets, const rife_hip_apply_set_t* sets) const;
 
     // Extension, not in the reference (include/rife_hip.h "strides and planes"): frames as an AVFrame or a VapourSynth frame holds them - a pointer and a
     // pitch in BYTES per plane, any of the _px formats (planar RGB: R, G, B in plane[0..2]; ffmpeg's gbrp: permute them).  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
