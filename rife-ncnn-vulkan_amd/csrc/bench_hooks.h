@@ -115,6 +115,7 @@ int rife_hip_probe_f16_denorm(int gpuid, float* out) {
 // bench-only: what the matrix pipe alone sustains, on random operands, for the instruction mix of one 32 px x 64 ch trunk tile
 // (64 input channels x 10 taps): MIX 0 = today's 80 + 80 v_mfma_f32_32x32x16_f16 (hi + lo), MIX 1 = 80 f16 (hi) + 20
 // v_mfma_scale_f32_32x32x64_f8f6f4 (lo as scaled fp8), MIX 2 = the 80 hi instructions alone, MIX 3 = 80 f16 (hi) + 80 v_mfma_f32_32x32x16_fp8_fp8 (lo).  16 waves per CU like conv_h2b.
+// Bit 8: the products of MIX 0 (two chains) / MIX 4 (four chains) as 320 v_mfma_f32_16x16x32_f16, the shape of the conv_rs / conv_rs2 consumers (conv_rs.h).
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 extern "C++" {
 template <int MIX>
@@ -141,6 +142,31 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int n = 0; n < 2; n++)
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[n][r] = 0.f;
+    if (MIX & 8) {       // the same operands and FLOP per wave as MIX 0 (8) / MIX 4 (12) issued as v_mfma_f32_16x16x32_f16: two 32x32x16 (K = 32) = four 16x16 output tiles
+        constexpr int NC = (MIX & 4) ? 4 : 2;                            // over K = 32, so 320 instructions of 16 cycles per tile on four accumulators per chain
+        f32x4 t16[NC][4];
+#pragma unroll
+        for (int n = 0; n < NC; n++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) t16[n][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < tiles; t++) {
+#pragma unroll
+            for (int kk = 0; kk < 20; kk++)
+#pragma unroll
+                for (int j = 0; j < 4 / NC; j++)
+#pragma unroll
+                    for (int n = 0; n < NC; n++)
+#pragma unroll
+                        for (int q = 0; q < 4; q++)
+                            t16[n][q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[(2 * kk + n + j + (q >> 1)) & 3], xb[(2 * kk + 2 * j + (q & 1)) & 3], t16[n][q], 0, 0, 0);
+        }
+#pragma unroll
+        for (int n = 0; n < NC; n++)
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) acc[n & 1][4 * q + r] += t16[n][q][r];
+    } else
     if (MIX == 4) {      // round 6: FOUR independent accumulation chains per wave (160 instructions per tile like MIX 0): no wave ever waits for its own previous result
         f32x16 acc4[4];
 #pragma unroll
@@ -250,6 +276,8 @@ int rife_hip_bench_mfma_mix(int gpuid, int mix, int tiles, int iters, float* ms_
     auto launch = [&]() {
         if (one_wave) {
             if (mix == 4) hipLaunchKernelGGL(k_bench_mfma_mix<4>, dim3(256), dim3(256), 0, 0, d, o, tiles);
+            else if (mix == 8) hipLaunchKernelGGL(k_bench_mfma_mix<8>, dim3(256), dim3(256), 0, 0, d, o, tiles);
+            else if (mix == 12) hipLaunchKernelGGL(k_bench_mfma_mix<12>, dim3(256), dim3(256), 0, 0, d, o, tiles);
             else hipLaunchKernelGGL(k_bench_mfma_mix<0>, dim3(256), dim3(256), 0, 0, d, o, tiles);
             return;
         }
@@ -257,6 +285,8 @@ int rife_hip_bench_mfma_mix(int gpuid, int mix, int tiles, int iters, float* ms_
         else if (mix == 1) hipLaunchKernelGGL(k_bench_mfma_mix<1>, dim3(512), dim3(512), 0, 0, d, o, tiles);
         else if (mix == 3) hipLaunchKernelGGL(k_bench_mfma_mix<3>, dim3(512), dim3(512), 0, 0, d, o, tiles);
         else if (mix == 4) hipLaunchKernelGGL(k_bench_mfma_mix<4>, dim3(512), dim3(512), 0, 0, d, o, tiles);
+        else if (mix == 8) hipLaunchKernelGGL(k_bench_mfma_mix<8>, dim3(512), dim3(512), 0, 0, d, o, tiles);
+        else if (mix == 12) hipLaunchKernelGGL(k_bench_mfma_mix<12>, dim3(512), dim3(512), 0, 0, d, o, tiles);
         else hipLaunchKernelGGL(k_bench_mfma_mix<2>, dim3(512), dim3(512), 0, 0, d, o, tiles);
     };
     for (int i = 0; i < 3; i++) launch();

@@ -6,18 +6,23 @@
 //
 // One workgroup per CU, 8 waves, three jobs:
 //   * waves 0-3, "consumers" (one per SIMD): wave k owns output block n = k & 1 (32 channels) of output row (k >> 1) of the current row
-//     pair.  Its 36 weight fragments ([K chunk 4][tap 9] x 16 bytes per lane = 144 VGPRs) are loaded ONCE per launch and stay in registers:
+//     pair.  Its 36 weight fragments ([chunk pair 2][tap 9][channel half 2] x 16 bytes per lane = 144 VGPRs) are loaded ONCE per launch and stay in registers:
 //     no weight ever passes through LDS (conv_t64 re-streamed the 72 KB of weights per 8 x 32 tile: 1.2 GB of L2 -> LDS traffic per 4K
-//     launch, 4 x the activations).  A consumer issues ds_read_b128 (pixel fragments, three MFMA pairs ahead of their use - across the step
-//     boundary too) and MFMAs in two accumulation chains (hi products, lo products), and writes the raw fp32 sums of its row to an LDS
-//     staging buffer.  It never touches vector memory after the prologue and does no epilogue arithmetic.
+//     launch, 4 x the activations).  A consumer issues ds_read_b128 (pixel fragments, three units ahead of their use - across the step
+//     boundary too) and v_mfma_f32_16x16x32_f16 on four 16 channel x 16 pixel tiles in two accumulation chains (hi products, lo products), and
+//     writes the raw fp32 sums of its row to an LDS staging buffer.  It never touches vector memory after the prologue and does no epilogue
+//     arithmetic.  (RsRow below: the consumer body this kernel shares with conv_rs2_kernel; operand lane maps: rs_frag_geom.h.)
+//     The instruction: the same products were issued as 76 v_mfma_f32_32x32x16_f16 per step until the chip was found to hold a higher clock on
+//     the 16x16x32 form at equal matrix cycles on real operands (profiles/mfma_shape/: the bare loop 2,067 against 1,737 MHz inside the
+//     power cap = 1.19 x the FLOP/s; conv_rs2 on fixed random input 133.6 against 142.9 us per launch, a step 3,300 - 3,350 cycles at 1.91 GHz
+//     against 3,150 at 1.66; on zeros, where power does not limit, no gain: 4 % slower).
 //   * waves 4-5, "loaders": LDS-DMA (global_load_lds_dwordx4, 1 KiB per instruction, no registers) of the halo ROWS three steps ahead into a
 //     ring of 12 row slots.  A workgroup walks DOWN (or up) a 32-column strip, so every input row is loaded once per strip instead of once
 //     per 8-row tile: 34 / 32 of the tensor instead of 10 x 34 / (8 x 32) = 1.33 x.
 //   * waves 6-7, "storers": bias, LeakyReLU and the {hi, lo} split of the row pair staged two steps ago, then 1 KiB contiguous per store.
 //   Loads and stores are issued by different waves because vmcnt only retires in order within one kind of access: the loaders' counted
 //   waits (vmcnt(9) / vmcnt(18): the rows of the steps after next may still be in flight) would be meaningless with stores in the same queue.
-// A step = one row pair of one strip = 76 MFMAs per consumer (2,432 cycles of its SIMD's matrix pipe) and ends with ONE s_barrier:
+// A step = one row pair of one strip = 152 MFMAs of 16 cycles per consumer (2,432 cycles of its SIMD's matrix pipe) and ends with ONE s_barrier:
 //   iteration it:  consumers  MFMAs of step it -> staging[it % 3]; first fragments of step it + 1
 //                  loaders    rows of step it + 3 -> ring; wait for the rows of step it + 2
 //                  storers    staging[(it - 2) % 3] -> epilogue -> global
@@ -25,16 +30,19 @@
 // units over 256 workgroups = 31 or 32 steps each); a range that crosses into the next strip restarts the ring there (4 fresh rows).
 // Tensors are the S16 tensors of conv_t64.h ({hi, lo} f16 planes per 16-channel chunk, one pixel of zero border), the weight image is
 // conv_t64's (pack_t64_image), the products are conv_t64_kernel's.  The sums differ from conv_t64's in the last bits (two chains added at the
-// end instead of one): tests/test_gpu_t64.py and tools/rs_bench.py hold the two kernels together (<= 1 LSB on the u8 frame, < 1e-3 of the
+// end instead of one, K = 32 per instruction; per chain and tile: chunk pair 0 taps 0 - 8, the identity step of the skip if N = 0, chunk pair 1
+// taps 0 - 8, the identity step if N = 1): tests/test_gpu_t64.py and tools/rs_bench.py hold the two kernels together (<= 1 LSB on the u8 frame, < 1e-3 of the
 // bytes differ, block-3 flows to 1e-4) and check that conv_rs itself is run-to-run identical.
-// LDS: ring 12 x 8,704 B (row slot = [chunk 4][hi | lo][34 px][32 B], halves swapped where bit 3 of the column is set: conflict-free
-// ds_read_b128, applied to the DMA source addresses) + staging 3 x 2 rows x 8 KiB of fp32 sums + bias / slopes = 154,112 B.
+// LDS: ring 12 x 8,704 B (row slot = [chunk 4][hi | lo][34 px][32 B], the PLAIN image - pixel-major, no half swap: the 16x16x32 fragment read takes
+// the two chunks of a pair 2,176 B = 128 mod 256 apart, conflict-free in every ds_read_b128 lane group, where conv_t64's swap would make it 2-way;
+// tests/test_rs_frag_geom.py) + staging 3 x 2 rows x 8 KiB of fp32 sums + bias / slopes = 154,112 B.
 // Measured (MI355X, 4K, same-call A/B, profiles/r3/rs_bench.txt): 73.5 - 76 us per launch in the pass against 81.6 - 82.9 for conv_t64; matrix work
 // alone 45.8 us (2.22 GHz), memory alone 49.9 us, both 60.1 us at the 1.88 GHz the chip settles at under this load: the phases overlap.
 #pragma once
 #include <type_traits>
 #include "conv_t64.h"
 #include "conv_row.h"
+#include "rs_frag_geom.h"
 
 namespace rife {
 
@@ -50,6 +58,8 @@ constexpr int RS_LDS = RS_LDS_BS + 512;                    // 154,112 B: one wor
 constexpr int RS_AHEAD = 3;                                // the loaders run three steps ahead of the consumers
 constexpr int RS_MIN_PAIRS = 4;                            // ring capacity: at most one strip change among RS_AHEAD + 1 consecutive steps (4 + 4 + 2 + 2 rows)
 constexpr int RS_NTHR = 512;
+static_assert(RS_SEG == rsg::SEG && RS_ROWB == rsg::ROWB && RS_STG_ROW == rsg::STG_ROW && t64_wch(2) == rsg::WCH && rsg::IMG_W < T64_IMG, "rs_frag_geom.h restates these");
+static_assert(s16_row_channel(5) == rsg::row_channel(5) && s16_row_channel(26) == rsg::row_channel(26), "rs_frag_geom.h restates s16_row_channel");
 
 struct RsArgs {
     const unsigned char* in;     // S16 tensor, allocation start (= pixel (-1, -1) of plane 0)
@@ -94,53 +104,114 @@ __device__ __forceinline__ void rs_dma16(const unsigned char* base, unsigned vof
 #define RS_SYNC_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_barrier" ::: "memory")
 #define RS_SYNC_BARE() asm volatile("s_barrier" ::: "memory")
 
-// The matrix work of one (row, output block N) is a fixed sequence of 38 MFMA pairs (A fragment, pixel fragment {hi, lo}): per K chunk c the
-// nine taps in order, then - if chunk c carries the input channels of output block N - the identity tap of the skip connection
-// (conv_t64_kernel's order: the accumulation is bit-identical).
-struct RsPairDesc { int c, t; bool idn; };
-__host__ __device__ constexpr RsPairDesc rs_pair(int N, int m) {
-    for (int c = 0; c < 4; c++) {
-        const int cnt = 9 + ((c >> 1) == N ? 1 : 0);
-        if (m < cnt) return m < 9 ? RsPairDesc{c, m, false} : RsPairDesc{c, 4, true};
-        m -= cnt;
+// The matrix work of one (row, output block N) is a fixed sequence of RS_NPAIR = 38 units (rs_frag_geom.h: chunk pair, tap or identity step, pixel half),
+// each ONE pixel fragment {hi, lo} = two ds_read_b128, against the weight fragments of the two channel halves: four v_mfma_f32_16x16x32_f16 of 16 cycles
+// (FAST: two on a weight tap) - 152 instructions, 2,432 cycles of the SIMD's matrix pipe per row.
+constexpr int RS_NPAIR = rsg::NUNIT, RS_PF = 3;      // units per row; fragment prefetch distance in units (RS_PF + 1 fragment register sets)
+enum { RS2_NOFRAG = 0x10, RS2_NOLO = 0x20 };          // bench-only (conv_rs2.h): no LDS fragment reads (MFMAs on whatever the registers hold); hi products only
+
+// The products of one output row of output block N: the ONE consumer body of conv_rs_kernel and conv_rs2_kernel (rs_consumer below, rs2_consumer in
+// conv_rs2.h: they differ in which ring rows a step reads and where its sums are staged, not in a single product or in their order).
+// Registers: 36 weight fragments [chunk pair 2][tap 9][channel half 2] x 4 = 144, loaded once per launch from conv_t64's image (one 16-byte load each); two
+// identity fragments; 2 chains x 4 tiles (channel half, pixel half) x 4 = 32 accumulators; RS_PF + 1 pixel fragment sets {hi, lo}.
+// Order per chain (hi products, lo products) and tile: chunk pair 0 taps 0 - 8 (then the identity step if N = 0), chunk pair 1 taps 0 - 8 (then the identity
+// step if N = 1); the chains are added when the sums go to staging.  FAST (conv_t64.h): hi products only on the weight taps, hi and lo on the identity step,
+// whose lo instruction opens the lo chain.  Between two instructions on the same accumulator lie at least three on others.
+template <int N, int TAG>
+struct RsRow {
+    static constexpr bool FAST = (TAG & S16_FAST) != 0;
+    static constexpr int NF = RS_PF + 1;                                 // fragment register sets; unit m of a step of parity PAR uses set (m + 2 PAR) % NF (38 % 4 = 2)
+    static_assert(NF == 4 && RS_NPAIR % NF == 2, "fragment set rotation across steps");
+    f16x8 W[2][9][2], idf[2];
+    f16x8 fh[NF], fl[NF];
+    f32x4 acc[2][2][2];                                                  // [chain hi | lo][channel half][pixel half]
+    unsigned colo[3];                                                    // lane part of the fragment addresses per tap column
+    unsigned ad[9];                                                      // fragment addresses of the nine taps of the step being read: chunk pair 0, hi plane, pixel half 0
+    unsigned stgo;                                                       // lane part of the staging address
+
+    __device__ __forceinline__ void init(const unsigned char* const img, const int lane) {
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+            const unsigned char* const wsrc = img + rsg::w_lane(lane, N, half);
+#pragma unroll
+            for (int cp = 0; cp < 2; cp++)
+#pragma unroll
+                for (int t = 0; t < 9; t++) W[cp][t][half] = *reinterpret_cast<const f16x8*>(wsrc + rsg::w_frag(cp, t));
+#pragma unroll
+            for (int j = 0; j < 8; j++) idf[half][j] = rsg::id_one(lane, half, j) ? (_Float16)1.f : (_Float16)0.f;
+        }
+#pragma unroll
+        for (int dx = 0; dx < 3; dx++) colo[dx] = (unsigned)rsg::pix_lane(lane, dx);
+        stgo = (unsigned)rsg::stg_lane(lane, N);
     }
-    return RsPairDesc{0, 0, false};
-}
-constexpr int RS_NPAIR = 38, RS_PF = 3;      // pairs per row; fragment prefetch distance in pairs (RS_PF + 1 fragment register sets)
+    // tap row dy of the step being read lies in the ring row at LDS byte offset rb
+    __device__ __forceinline__ void set_row(const int dy, const unsigned rb) {
+#pragma unroll
+        for (int dx = 0; dx < 3; dx++) ad[dy * 3 + dx] = rb + colo[dx];
+    }
+    // fragment {hi, lo} of unit M of the step whose addresses are in ad[]; M >= RS_NPAIR: unit M - RS_NPAIR of the next step (the sets continue to rotate)
+    template <int M, int PAR>
+    __device__ __forceinline__ void read(const unsigned char* const ldsb) {
+        constexpr rsg::Unit u = rsg::unit(N, M % RS_NPAIR);
+        constexpr int st = (M + 2 * PAR) % NF;
+        if RIFE_ABL(TAG & RS2_NOFRAG) { asm volatile("" : "+v"(fh[st]), "+v"(fl[st])); return; }
+        fh[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[u.t] + rsg::pix_frag(u.cp, 0, u.ph));
+        if constexpr (FAST && !u.idn) return;
+        if (!RIFE_ABL(TAG & RS2_NOLO)) fl[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[u.t] + rsg::pix_frag(u.cp, 1, u.ph));
+    }
+    // the first fragments of a step of parity 0, before its products()
+    __device__ __forceinline__ void read_first(const unsigned char* const ldsb) {
+        for_each_slot<0, RS_PF>([&](auto mc) { read<decltype(mc)::value, 0>(ldsb); });
+    }
+    // One step.  The pixel fragments are read RS_PF units ahead of their MFMAs - across the step boundary too: the last RS_PF units of a step read the first
+    // fragments of the NEXT step, whose rows the loaders guarantee one barrier early; next() moves ad[] there once every read of this step is issued - and
+    // sched_barrier keeps the compiler from sinking the reads back to their uses (its waits are counted lgkmcnt: the LDS returns a wave's reads in order).
+    template <int PAR, class NEXT>
+    __device__ __forceinline__ void products(const unsigned char* const ldsb, NEXT&& next) {
+        for_each_slot<0, RS_NPAIR>([&](auto mc) {
+            constexpr int m = decltype(mc)::value;
+            constexpr rsg::Unit u = rsg::unit(N, m);
+            constexpr int st = (m + 2 * PAR) % NF;
+            constexpr bool open = !u.idn && u.cp == 0 && u.t == 0;       // the tiles' first instruction
+            if constexpr (m == RS_NPAIR - RS_PF) next();
+            read<m + RS_PF, PAR>(ldsb);
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int half = 0; half < 2; half++) {
+                const f16x8 A = u.idn ? idf[half] : W[u.cp][u.t][half];
+                acc[0][half][u.ph] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, fh[st], open ? z : acc[0][half][u.ph], 0, 0, 0);
+                if constexpr (FAST) {
+                    if constexpr (u.idn) acc[1][half][u.ph] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, fl[st], z, 0, 0, 0);
+                } else if (!RIFE_ABL(TAG & RS2_NOLO)) acc[1][half][u.ph] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, fl[st], open ? z : acc[1][half][u.ph], 0, 0, 0);
+                else if constexpr (open) acc[1][half][u.ph] = z;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    }
+    __device__ __forceinline__ void fill(const float v) {                // bench builds without the matrix work
+#pragma unroll
+        for (int i = 0; i < 4; i++) { acc[0][i >> 1][i & 1] = f32x4{v, v, v, v}; acc[1][i >> 1][i & 1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    }
+    // raw sums (hi chain + lo chain) -> the staged row at `row`: four ds_write_b128, quad l >> 4 of the lane's pixel in each tile's 64-byte record.  Bias,
+    // LeakyReLU and the {hi, lo} split are the epilogue waves' work two iterations later, by when these writes have long completed (no wait here: the LDS
+    // executes a wave's operations in order, and the next step's reads follow them)
+    __device__ __forceinline__ void stage(unsigned char* const row) {
+#pragma unroll
+        for (int half = 0; half < 2; half++)
+#pragma unroll
+            for (int ph = 0; ph < 2; ph++) *reinterpret_cast<f32x4*>(row + stgo + rsg::stg_tile(half, ph)) = acc[0][half][ph] + acc[1][half][ph];
+    }
+};
 
 // consumer wave: output block N of row `ro` of every row pair of the workgroup's range (see the header of this file)
 template <int N, int TAG>
 __device__ __forceinline__ void rs_consumer(const RsArgs& a, unsigned char* const ldsb, const int ro, const int lane, const int S, const int ufirst) {
-    const int h = lane >> 5, li = lane & 31;
-    constexpr bool FAST = (TAG & S16_FAST) != 0;                         // conv_t64.h: the lo chain carries the skip's identity products only; no lo fragment is read for a weight tap
-    // weights of output block N: [chunk][tap] A fragments, lane (li, h) = row li, k half h (conv_t64's image: [chunk][tap][k half][64 rows][8 f16])
-    f16x8 W[4][9];
-    {
-        const unsigned char* wsrc = a.img + h * 1024 + (N * 32 + li) * 16;
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-#pragma unroll
-            for (int t = 0; t < 9; t++) W[c][t] = *reinterpret_cast<const f16x8*>(wsrc + c * t64_wch(2) + t * 2048);
-    }
-    f16x8 idf[2];                                                        // identity A fragments of the skip connection (conv_t64.h)
-    {
-        const int ch = s16_row_channel(li);
-#pragma unroll
-        for (int hc = 0; hc < 2; hc++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) idf[hc][e] = ch == 16 * hc + 8 * h + e ? (_Float16)1.f : (_Float16)0.f;
-    }
-    unsigned colo[3];                                                    // column part of the fragment addresses
-#pragma unroll
-    for (int dx = 0; dx < 3; dx++) { const int px = li + dx; colo[dx] = (unsigned)(px * 32 + ((h ^ ((px >> 3) & 1)) << 4)); }
-    // staged record of this lane: 16 fp32 = channels 32 N + 16 h .. + 15 of pixel li, the four 16-byte quads XOR-swizzled by (li >> 1) & 3
-    // (the eight lanes of a ds_write_b128 group then cover all 32 banks)
-    unsigned char* const stg = ldsb + RS_LDS_STG + ro * RS_STG_ROW + ((2 * N + h) * 32 + li) * 64;
-    const int qs = (li >> 1) & 3;
+    RsRow<N, TAG> row;
+    row.init(a.img, lane);
+    unsigned char* const stg = ldsb + RS_LDS_STG + ro * RS_STG_ROW;
 
     RsCursor cur; cur.init(ufirst, a.npairs);
     int sq = 0;                                                          // rows loaded through the step `cur` points at, mod RS_NR
-    unsigned ad[9];                                                      // fragment addresses of the nine taps, chunk 0, hi plane
     // addresses of the step at `cur` (fresh: it starts a strip, all four halo rows are new)
     auto step_addresses = [&](const bool fresh) {
         sq += fresh ? 4 : 2; if (sq >= RS_NR) sq -= RS_NR;
@@ -149,89 +220,21 @@ __device__ __forceinline__ void rs_consumer(const RsArgs& a, unsigned char* cons
             const int j = ro + dy;                                       // row of the step's four halo rows, from the top
             int sl = a.descend ? sq + RS_NR - 1 - j : sq + RS_NR - 4 + j;
             if (sl >= RS_NR) sl -= RS_NR;
-            const unsigned rb = (unsigned)(RS_LDS_RING + sl * RS_ROWB);
-#pragma unroll
-            for (int dx = 0; dx < 3; dx++) ad[dy * 3 + dx] = rb + colo[dx];
+            row.set_row(dy, (unsigned)(RS_LDS_RING + sl * RS_ROWB));
         }
     };
-    constexpr int NF = RS_PF + 1;                                        // fragment register sets; pair m of a step of parity PAR uses set (m + 2 PAR) % NF (38 % 4 = 2)
-    static_assert(NF == 4 && RS_NPAIR % NF == 2, "fragment set rotation across steps");
-    f16x8 fh[NF], fl[NF];
     int it = 0;
-    // One step.  Two accumulation chains, the hi products and the lo products: an MFMA never waits for the result of the one issued just
-    // before it (one wave per SIMD: nobody else would fill the gap).  The pixel fragments are read RS_PF pairs ahead of their MFMAs -
-    // across the step boundary too: the last RS_PF pairs of a step read the first fragments of the NEXT step, whose rows the loaders
-    // guarantee one barrier early - and sched_barrier keeps the compiler from sinking the reads back to their uses.
     auto step = [&](auto par_c) {
         constexpr int PAR = decltype(par_c)::value;
-        auto frag_read = [&](auto mc) {                                  // pair m of the step whose addresses are in ad[]
-            constexpr int m = decltype(mc)::value;
-            constexpr RsPairDesc d = rs_pair(N, m % RS_NPAIR);
-            constexpr int st = (m + 2 * PAR) % NF;
-            fh[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG));
-            if constexpr (!FAST || d.idn) fl[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
-        };
-        f32x16 accH, accL;
-        if (!RIFE_ABL(TAG & RS_NOMATH)) {
-            for_each_slot<0, RS_NPAIR>([&](auto mc) {
-                constexpr int m = decltype(mc)::value;
-                constexpr RsPairDesc d = rs_pair(N, m);
-                constexpr int st = (m + 2 * PAR) % NF;
-                if constexpr (m == RS_NPAIR - RS_PF) step_addresses(cur.advance(a.npairs, a.descend));     // ad[] is dead: every read of this step is issued
-                frag_read(std::integral_constant<int, m + RS_PF>{});     // m + RS_PF >= 38: pair m + RS_PF - 38 of the next step (sets continue to rotate)
-                const f16x8 A = d.idn ? idf[d.c & 1] : W[d.c][d.t];
-                if constexpr (FAST) {                                    // the identity taps are those of chunks 2 N (the first: it opens the lo chain) and 2 N + 1
-                    if constexpr (m == 0) {
-                        f32x16 z;
-#pragma unroll
-                        for (int q = 0; q < 16; q++) z[q] = 0.f;
-                        accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], z, 0, 0, 0);
-                    } else accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], accH, 0, 0, 0);
-                    if constexpr (d.idn && (d.c & 1) == 0) {
-                        f32x16 z;
-#pragma unroll
-                        for (int q = 0; q < 16; q++) z[q] = 0.f;
-                        accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], z, 0, 0, 0);
-                    } else if constexpr (d.idn) accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], accL, 0, 0, 0);
-                } else
-                if constexpr (m == 0) {
-                    f32x16 z;
-#pragma unroll
-                    for (int q = 0; q < 16; q++) z[q] = 0.f;
-                    accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], z, 0, 0, 0);
-                    accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], z, 0, 0, 0);
-                } else {
-                    accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], accH, 0, 0, 0);
-                    accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], accL, 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        } else {
-#pragma unroll
-            for (int q = 0; q < 16; q++) { accH[q] = (float)lane; accL[q] = 0.f; }
-        }
-        // raw sums -> staging[it % 3]; bias, LeakyReLU and the {hi, lo} split are the storers' work two iterations later, by when these
-        // writes have long completed (no wait here: the LDS executes a wave's operations in order, and the next step's reads follow them)
-        int sb = it % RS_NSTG;
-        f32x4* const d4 = reinterpret_cast<f32x4*>(stg + sb * (2 * RS_STG_ROW));
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            f32x4 v;
-#pragma unroll
-            for (int k = 0; k < 4; k++) v[k] = accH[4 * q + k] + accL[4 * q + k];
-            d4[q ^ qs] = v;
-        }
+        if (!RIFE_ABL(TAG & RS_NOMATH)) row.template products<PAR>(ldsb, [&]() { step_addresses(cur.advance(a.npairs, a.descend)); });
+        else row.fill((float)lane);
+        row.stage(stg + (it % RS_NSTG) * (2 * RS_STG_ROW));              // staging[it % 3]
         RS_SYNC_BARE();
         it++;
     };
     RS_SYNC_LGKM();                                                      // ring rows of steps 0 and 1 landed (loaders), bias in LDS
     step_addresses(true);
-    if (!RIFE_ABL(TAG & RS_NOMATH)) for_each_slot<0, RS_PF>([&](auto mc) {       // first fragments of step 0 (parity 0)
-        constexpr int m = decltype(mc)::value;
-        constexpr RsPairDesc d = rs_pair(N, m);
-        fh[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG));
-        if constexpr (!FAST || d.idn) fl[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
-    });
+    if (!RIFE_ABL(TAG & RS_NOMATH)) row.read_first(ldsb);                // first fragments of step 0 (parity 0)
     while (it + 1 < S) { step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); }
     if (it < S) step(std::integral_constant<int, 0>{});
     RS_SYNC_LGKM();                                                      // the last step's staging writes have landed
@@ -299,8 +302,7 @@ __global__ __launch_bounds__(RS_NTHR) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const int u = min(i * 64 + lane, 543);
             const int seg = u / 68, within = u - seg * 68;
             const int px = within >> 1, pos = within & 1;
-            const int kh = pos ^ ((px >> 3) & 1);
-            soff[i] = (unsigned)seg * a.plane + (unsigned)(px * 32 + kh * 16);
+            soff[i] = (unsigned)seg * a.plane + (unsigned)(px * 32 + pos * 16);
         }
         RsCursor cur; cur.init(ufirst, a.npairs);
         int sq = 0;                                                      // rows loaded so far, mod RS_NR

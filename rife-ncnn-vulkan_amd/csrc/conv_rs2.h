@@ -7,8 +7,8 @@
 //
 // One workgroup per CU, 8 waves, the waves of conv_rs_kernel with other jobs:
 //   * wave 0, 1 "CA": consumer of layer A, output block N = wave (32 channels), ONE row per step.  36 weight fragments in registers, pixel
-//     fragments from ring A (the input rows, LDS-DMA), raw fp32 sums -> staging A.  The code of rs_consumer (conv_rs.h): the same products in
-//     the same order, two accumulation chains.
+//     fragments from ring A (the input rows, LDS-DMA), raw fp32 sums -> staging A.  The consumer body of conv_rs.h (RsRow, instantiated here
+//     and by rs_consumer): 152 v_mfma_f32_16x16x32_f16 per step, the same products in the same order, two accumulation chains.
 //   * wave 2, 3 "CB": the same for layer B on ring B (A's rows), raw sums -> staging B.
 //   * wave 4 "L": LDS-DMA of one input row per step into ring A (8 slots), RS2_AH rows in flight beyond the one the consumers need next.
 //   * wave 5, 6 "EA": epilogue of layer A, chunks {0, 1} / {2, 3}: staging A -> bias, LeakyReLU, {hi, lo} split, ZERO outside the image (B's zero
@@ -30,8 +30,9 @@
 //   LAG = 5 walking down, 6 walking up (the first fragments a consumer prefetches are tap row dy = 0: the NEWEST row when walking up).
 // A segment costs R + LAG + 2 iterations for R rows; the host cuts every strip into equal parts so that all CUs have one segment (4K, 256 CUs: 32
 // strips x 8 parts of 68 rows; on a CU-masked stream of 128 CUs: 4 parts of 136 rows).
-// Bit-exactness: per layer the products, their order and the epilogue arithmetic are conv_rs_kernel's, and ring B holds the {hi, lo} f16 pairs
+// Bit-exactness: per layer the products and their order are conv_rs_kernel's by construction (one body), the epilogue arithmetic too, and ring B holds the {hi, lo} f16 pairs
 // conv_rs_kernel would have written: the output equals two conv_rs launches byte for byte (tools/rs2_bench.py, tests/test_gpu_t64.py).
+// Both rings hold conv_rs's plain row image (pixel-major, no half swap; only the consumers read them): wave L's DMA source offsets and EA's writes.
 // LDS: ring A 8 x 8,704 + ring B 5 x 8,704 + staging 2 x 3 x 8 KiB + bias / slopes 1 KiB = 163,328 B of the CU's 163,840.
 #pragma once
 #include "conv_rs.h"
@@ -83,7 +84,7 @@ __device__ __forceinline__ Rs2Seg rs2_segment(const Rs2Args& a, const int seg) {
 #define RS2_NEXT(V, MOD) { V = V + 1 == (MOD) ? 0 : V + 1; }
 // bench builds, RIFE_ABL(TAG & RS2_STAMPS): lane 0 of every wave of workgroup a.stamp_wg records the shader clock when it arrives at a barrier and when it
 // leaves it: stamps[(wave * RS2_NSTAMP + barrier) * 2 + {0, 1}] (tools/rs2_bench.py prints who the others waited for, step by step)
-enum { RS2_STAMPS = 0x1000, RS2_NOFRAG = 0x10, RS2_NOLO = 0x20 };      // NOFRAG: no LDS fragment reads (MFMAs on whatever the registers hold); NOLO: hi products only
+enum { RS2_STAMPS = 0x1000 };                                          // (RS2_NOFRAG, RS2_NOLO: conv_rs.h, with the consumer body)
 constexpr int RS2_NSTAMP = 128;
 #define RS2_BAR(KIND)                                                                                                  \
     {                                                                                                                  \
@@ -99,105 +100,26 @@ constexpr int RS2_NSTAMP = 128;
 template <int N, int NR, int TAG>
 __device__ __forceinline__ void rs2_consumer(const Rs2Args& a, const unsigned char* const img, unsigned char* const ldsb, const unsigned ring, const unsigned stgbase,
                                              const int lead, const int extra, const int lag, const int lane) {
-    const int h = lane >> 5, li = lane & 31;
-    constexpr bool FAST = (TAG & S16_FAST) != 0;                         // conv_t64.h; both layers of the launch, the code of rs_consumer's fast form
-    f16x8 W[4][9];                                                       // rs_consumer's register-resident weights
-    {
-        const unsigned char* wsrc = img + h * 1024 + (N * 32 + li) * 16;
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-#pragma unroll
-            for (int t = 0; t < 9; t++) W[c][t] = *reinterpret_cast<const f16x8*>(wsrc + c * t64_wch(2) + t * 2048);
-    }
-    f16x8 idf[2];
-    {
-        const int ch = s16_row_channel(li);
-#pragma unroll
-        for (int hc = 0; hc < 2; hc++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) idf[hc][e] = ch == 16 * hc + 8 * h + e ? (_Float16)1.f : (_Float16)0.f;
-    }
-    unsigned colo[3];
-#pragma unroll
-    for (int dx = 0; dx < 3; dx++) { const int px = li + dx; colo[dx] = (unsigned)(px * 32 + ((h ^ ((px >> 3) & 1)) << 4)); }
-    unsigned char* const stg = ldsb + stgbase + ((2 * N + h) * 32 + li) * 64;
-    const int qs = (li >> 1) & 3;
+    RsRow<N, TAG> row;                                                   // conv_rs.h: the consumer body of both kernels
+    row.init(img, lane);
+    unsigned char* const stg = ldsb + stgbase;
 
     int bar = 0;
     int sq = 0;                                                          // ring slot of the step's first row in walking order
     int sbuf = 0;                                                        // staging buffer of the step (iteration % 3)
-    unsigned ad[9];
     auto step_addresses = [&]() {
 #pragma unroll
         for (int dy = 0; dy < 3; dy++) {
             int sl = sq + (a.descend ? 2 - dy : dy);                     // walking up: the first row of the sequence is the row BELOW (tap row dy = 2)
             if (sl >= NR) sl -= NR;
-            const unsigned rb = ring + (unsigned)(sl * RS_ROWB);
-#pragma unroll
-            for (int dx = 0; dx < 3; dx++) ad[dy * 3 + dx] = rb + colo[dx];
+            row.set_row(dy, ring + (unsigned)(sl * RS_ROWB));
         }
     };
-    constexpr int NF = RS_PF + 1;
-    static_assert(NF == 4 && RS_NPAIR % NF == 2, "fragment set rotation across steps");
-    f16x8 fh[NF], fl[NF];
     auto step = [&](auto par_c) {
         constexpr int PAR = decltype(par_c)::value;
-        auto frag_read = [&](auto mc) {
-            constexpr int m = decltype(mc)::value;
-            constexpr RsPairDesc d = rs_pair(N, m % RS_NPAIR);
-            constexpr int st = (m + 2 * PAR) % NF;
-            if RIFE_ABL(TAG & RS2_NOFRAG) { asm volatile("" : "+v"(fh[st]), "+v"(fl[st])); return; }
-            fh[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG));
-            if constexpr (FAST && !d.idn) return;
-            if (!RIFE_ABL(TAG & RS2_NOLO)) fl[st] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
-        };
-        f32x16 accH, accL;
-        if (!RIFE_ABL(TAG & RS_NOMATH)) {
-            for_each_slot<0, RS_NPAIR>([&](auto mc) {
-                constexpr int m = decltype(mc)::value;
-                constexpr RsPairDesc d = rs_pair(N, m);
-                constexpr int st = (m + 2 * PAR) % NF;
-                if constexpr (m == RS_NPAIR - RS_PF) { RS2_NEXT(sq, NR) step_addresses(); }      // ad[] is dead: every read of this step is issued
-                frag_read(std::integral_constant<int, m + RS_PF>{});
-                const f16x8 A = d.idn ? idf[d.c & 1] : W[d.c][d.t];
-                if constexpr (FAST) {                                    // conv_rs.h: the lo chain starts at the identity tap of chunk 2 N
-                    if constexpr (m == 0) {
-                        f32x16 z;
-#pragma unroll
-                        for (int q = 0; q < 16; q++) z[q] = 0.f;
-                        accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], z, 0, 0, 0);
-                    } else accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], accH, 0, 0, 0);
-                    if constexpr (d.idn && (d.c & 1) == 0) {
-                        f32x16 z;
-#pragma unroll
-                        for (int q = 0; q < 16; q++) z[q] = 0.f;
-                        accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], z, 0, 0, 0);
-                    } else if constexpr (d.idn) accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], accL, 0, 0, 0);
-                } else
-                if constexpr (m == 0) {
-                    f32x16 z;
-#pragma unroll
-                    for (int q = 0; q < 16; q++) z[q] = 0.f;
-                    accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], z, 0, 0, 0);
-                    if (!RIFE_ABL(TAG & RS2_NOLO)) accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], z, 0, 0, 0); else accL = z;
-                } else {
-                    accH = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fh[st], accH, 0, 0, 0);
-                    if (!RIFE_ABL(TAG & RS2_NOLO)) accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, fl[st], accL, 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        } else {
-#pragma unroll
-            for (int q = 0; q < 16; q++) { accH[q] = (float)lane; accL[q] = 0.f; }
-        }
-        f32x4* const d4 = reinterpret_cast<f32x4*>(stg + sbuf * RS_STG_ROW);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            f32x4 v;
-#pragma unroll
-            for (int k = 0; k < 4; k++) v[k] = accH[4 * q + k] + accL[4 * q + k];
-            d4[q ^ qs] = v;
-        }
+        if (!RIFE_ABL(TAG & RS_NOMATH)) row.template products<PAR>(ldsb, [&]() { RS2_NEXT(sq, NR) step_addresses(); });
+        else row.fill((float)lane);
+        row.stage(stg + sbuf * RS_STG_ROW);
         RS2_NEXT(sbuf, RS2_NSTG)
         RS2_BAR(BARE())
     };
@@ -208,12 +130,7 @@ __device__ __forceinline__ void rs2_consumer(const Rs2Args& a, const unsigned ch
         for (int i = 0; i < lead; i++) RS2_BAR(BARE())
         sq = 0; sbuf = lead % RS2_NSTG;
         step_addresses();
-        if (!RIFE_ABL(TAG & RS_NOMATH)) for_each_slot<0, RS_PF>([&](auto mc) {       // first fragments of the first step (parity 0)
-            constexpr int m = decltype(mc)::value;
-            constexpr RsPairDesc d = rs_pair(N, m);
-            fh[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG));
-            if constexpr (!FAST || d.idn) fl[m % NF] = *reinterpret_cast<const f16x8*>(ldsb + ad[d.t] + d.c * (2 * RS_SEG) + RS_SEG);
-        });
+        if (!RIFE_ABL(TAG & RS_NOMATH)) row.read_first(ldsb);            // first fragments of the first step (parity 0)
         int k = 0;
         for (; k + 1 < S; k += 2) { step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); }
         if (k < S) step(std::integral_constant<int, 0>{});
@@ -267,8 +184,7 @@ __global__ __launch_bounds__(RS2_NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))
             const int u = min(i * 64 + lane, 543);
             const int sg = u / 68, within = u - sg * 68;
             const int px = within >> 1, pos = within & 1;
-            const int kh = pos ^ ((px >> 3) & 1);
-            soff[i] = (int)((unsigned)sg * a.plane) + px * 32 + kh * 16;
+            soff[i] = (int)((unsigned)sg * a.plane) + px * 32 + pos * 16;
         }
         if RIFE_ABL(TAG & RS_NODMA) { for (int i = lane; i < RS2_LDS_SA / 16; i += 64) reinterpret_cast<f32x4*>(ldsb)[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         for (int seg = blockIdx.x; seg < a.nseg; seg += gridDim.x) {
@@ -308,7 +224,7 @@ __global__ __launch_bounds__(RS2_NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))
         int bar = 0;
         const int px = lane >> 1, jh = lane & 1, qs = (px >> 1) & 3;
         const float slope = reinterpret_cast<const float*>(a.imgA + 4 * t64_wch(2))[64];
-        const unsigned dcol = (unsigned)(px * 32 + ((jh ^ ((px >> 3) & 1)) << 4));
+        const unsigned dcol = (unsigned)(px * 32 + jh * 16);                 // ring B has ring A's image: pixel-major, no half swap
         for (int seg = blockIdx.x; seg < a.nseg; seg += gridDim.x) {
             const Rs2Seg s = rs2_segment(a, seg);
             const int NIT = s.R + lag + 2;

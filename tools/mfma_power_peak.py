@@ -2,7 +2,8 @@
 k_bench_mfma_mix (csrc/bench_hooks.h): nothing but v_mfma_f32_32x32x16_f16 on register operands (random f16 in [-1, 1), or all zeros), in bursts of seconds
 while a thread samples rocm-smi (socket power, shader clock).  Variants: one wave per SIMD (256 workgroups x 4 waves: how the matrix waves of conv_rs / conv_rs2
 run) with two or four accumulation chains per wave; four waves per SIMD (512 x 8) with two chains (stops at 70 % of the pipe on any data: wave arbitration) or
-four.  Result (profiles/r6/mfma_power_peak.txt): zeros 2,461 - 2,477 TFLOP/s at 2.40 GHz; random operands 1,743 - 1,761 at 1.80 GHz and 1,320 W.
+four; and the same products issued as v_mfma_f32_16x16x32_f16 (mix bit 8: one wave per SIMD with two chains, four waves per SIMD with four chains;
+profiles/mfma_shape/mfma_power_peak.txt).  Result (profiles/r6/mfma_power_peak.txt): zeros 2,461 - 2,477 TFLOP/s at 2.40 GHz; random operands 1,743 - 1,761 at 1.80 GHz and 1,320 W.
     python tools/mfma_power_peak.py [seconds]"""
 import ctypes, os, subprocess, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,7 +34,10 @@ for rep in range(2):
                              (0x200, "ONE wave per SIMD, two chains (hi + lo like a conv_rs consumer)", 160), (0x204, "ONE wave per SIMD, four chains", 160),(0, "160 x v_mfma_f32_32x32x16_f16 per tile (the hi + lo mix)", 160), (2, "80 x v_mfma_f32_32x32x16_f16 per tile (hi only)", 80),
                              (4, "160 per tile, FOUR accumulation chains per wave (no dependent issue)", 160),
                              (0x100, "160 per tile, ALL-ZERO operands (same instruction stream, no toggling)", 160),
-                             (0x104, "160 per tile, four chains, ALL-ZERO operands", 160)):
+                             (0x104, "160 per tile, four chains, ALL-ZERO operands", 160),
+                             # the same products as 320 x v_mfma_f32_16x16x32_f16 per tile (mix bit 8; nmfma stays in 32x32x16 units: equal FLOP), the two shapes in one run
+                             (0x308, "16x16x32: ONE wave per SIMD, two chains, ALL-ZERO operands", 160), (0x208, "16x16x32: ONE wave per SIMD, two chains (a conv_rs consumer)", 160),
+                             (0x10c, "16x16x32: four waves per SIMD, four chains, ALL-ZERO operands", 160), (0x00c, "16x16x32: four waves per SIMD, four chains", 160)):
         waves = 256 * 4 if mix & 0x200 else 512 * 8
         flop = waves * TILES * nmfma * 32 * 32 * 16 * 2.0
         ms = ctypes.c_float()
