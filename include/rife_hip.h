@@ -429,8 +429,8 @@ int rife_hip_process_device_apply(const rife_hip_t* r, const void* d_in0, const 
  * written.  They are byte for byte rife_hip_process_motion / rife_hip_process_device_motion (F32) followed by the _sets apply call: the motion, of the frame size
  * w x h, is held in the workspace's tight device buffers; one apply launch per set on the same stream.  out may be NULL in the host call only.  At timestep 0 / 1
  * there is no network pass and no arithmetic: every set is a copy of its frame-0 / frame-1 planes, integer samples clamped to maxval.
- * Out of scope: making the proxy, shifts beyond +-1, mixed shifts other than (-1, 0), exporting the resampled motion, semi-planar or interleaved chroma, the batch and
- * image calls, the command line, several sets in one launch. */
+ * Out of scope: shifts beyond +-1, mixed shifts other than (-1, 0), exporting the resampled motion, semi-planar or interleaved chroma, the batch and
+ * image calls, the command line, several sets in one launch.  Making the proxy: the next section ("high bit depth"). */
 typedef struct rife_hip_apply_set {
     const rife_hip_planes_t* p0; const rife_hip_planes_t* p1; const rife_hip_planes_t* out;
     int shift_x, shift_y;   /* the planes relative to the motion, per axis: 0 same size, -1 half (rounded up), +1 double */
@@ -448,6 +448,46 @@ int rife_hip_process_apply_sets(const rife_hip_t* r, const void* in0, const void
 /* the same in device memory (d_out is required); stream semantics as for the device _px call */
 int rife_hip_process_device_apply_sets(const rife_hip_t* r, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt, int nsets,
                                        const rife_hip_apply_set_t* sets, void* hip_stream);
+
+/* ---- high bit depth: 12- and 16-bit Y'CbCr and RGB planes in ONE call (absent in the reference) ------------------------------------------------------------------------
+ * The resident frame holds ten bits per channel, and the sets calls above already blend the caller's own u16 samples at fp32 on motion estimated from a ten-bit proxy.
+ * These calls make that proxy on the device: a caller holding yuv420p12, a 12-bit 4:2:2 mezzanine frame or gbrp16 planes hands them over as they are and gets
+ * interpolated planes of the same depth back.  An hbd image is a rife_hip_image_t plus a depth:
+ *   pixfmt   RIFE_HIP_PIX_I420P10, _I422P10, _I444P10 (with the usual colour bits) or RIFE_HIP_PIX_RGBP10 (none): the plane LAYOUT, and the ten-bit format the proxy
+ *            is made in;
+ *   depth    10..16: the samples are codes of `depth` bits in the LOW bits of native-endian u16.
+ * Definition, operation by operation (tests/hbd_ref.py states it in numpy):
+ *   proxy sample   every sample v of every plane is reduced to ten bits with integer arithmetic,
+ *                      depth > 10:  c = min((v + (1 << (depth - 11))) >> (depth - 10), 1023)        (round half up, saturate)
+ *                      depth = 10:  c = min(v, 1023)
+ *                  and the proxy is the TIGHT frame of the image's pixfmt that holds those codes.
+ *   result         byte for byte the planes that rife_hip_process_apply_sets(r, proxy0, proxy1, w, h, timestep, NULL, pixfmt, nsets, sets) writes (device planes:
+ *                  rife_hip_process_device_apply_sets), the sets made of the images' planes:
+ *                      I444P10, RGBP10   one set:  the three planes, n = 3, shift (0, 0)
+ *                      I420P10           set 0: the luma plane, n = 1, shift (0, 0);  set 1: Cb and Cr, n = 2, shift (-1, -1)
+ *                      I422P10           set 0: the luma plane, n = 1, shift (0, 0);  set 1: Cb and Cr, n = 2, shift (-1, 0)
+ *                  every set with sample RIFE_HIP_SAMPLE_U16, maxval (1 << depth) - 1 and extent 0, 0, i.e. EDGE semantics: zero padding is green in Y'CbCr, so the
+ *                  plane's own edge is the border rule, and RGB planes follow the same rule so that there is one.
+ *   timestep 0, 1  as in that call: the planes of frame 0 / frame 1 copied, clamped to maxval; no network pass.
+ * No proxy frame is returned.  Input samples above maxval are read as stored by the blend and clamped only in the proxy (the rule of the apply calls).  The motion is
+ * read once per set, and for I420P10 / I422P10 ONCE for both sets: where the luma stores (8 bytes) and the chroma stores (4 bytes) of the output planes are aligned
+ * and w >= 4, one fused launch blends the luma plane and both chroma planes (the same bytes; everything else takes the two launches of the sets call).  The staged host planes
+ * (2 bytes per sample, uploaded once, tight) feed the pre-processing and the blend.
+ * Scope: that of the combined apply calls - model family rife-v4.6, plain mode, flow scale 1 and 2, precision full and fast.  Any other family or mode (-x, -z, -u)
+ * returns -RIFE_HIP_ENOSYS with a message that names it and the words "high bit depth", before anything is written.
+ * Rules (rife_hip_hbd_check states them for one image; both calls repeat them for their three images before they touch anything; a violation is -RIFE_HIP_EINVAL with
+ * the fault named in the message): rife_hip_image_check passes (so full range is refused, as for every 10-bit format); pixfmt is one of the four layouts above (any
+ * other format is named in the message); depth is in 10..16; w * h <= 2^27 and rows * pitch < 2^32 per plane (the rules of the sets calls on the same planes); the
+ * three images of a call agree in w, h and pixfmt.  Argument checks come before "no HIP device".  Output planes must not overlap each other or the inputs (documented,
+ * not checked); row padding and everything around the output planes is never written.
+ * Out of scope: semi-planar or MSB-aligned samples (P012 / P016 / P210); alpha planes and float planes (the sets calls serve them); resident hbd frames (stream mode)
+ * and the batch calls; the command line (its .y4m reader is untouched and keeps refusing C420p12 by name). */
+int rife_hip_hbd_check(const rife_hip_image_t* img, int depth);               /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
+/* planes in host memory */
+int rife_hip_process_hbd(const rife_hip_t* r, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out, int depth);
+/* planes in device memory; stream semantics as for the device _px call (NULL = the engine's own stream, synchronised before returning) */
+int rife_hip_process_device_hbd(const rife_hip_t* r, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out, int depth,
+                                void* hip_stream);
 
 const char* rife_hip_last_error(void);
 

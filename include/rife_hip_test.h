@@ -149,6 +149,17 @@ int rife_hip_op_apply(int gpuid, const rife_hip_planes_t* p0, const rife_hip_pla
  * the kernel did not write as it went in).  A set of shift 0, 0 is the launch of op_apply.  force_scalar: 0 = the host's choice, 1 = the one-pixel-per-lane form.
  * The rules of the sets calls hold (-RIFE_HIP_EINVAL before anything is uploaded). */
 int rife_hip_op_apply_scaled(int gpuid, const rife_hip_apply_set_t* set, const rife_hip_motion_t* host_motion, int mw, int mh, int force_scalar);
+/* op_hbd_to_rgb10: the high-bit-depth pre-processing kernel alone (csrc/hbd.h; include/rife_hip.h "high bit depth"), ONE launch on an hbd image of HOST planes, uploaded
+ * as op_image_to_resident uploads them (pitches and pointer alignment modulo 16 kept, so the form the host picks is the one it would pick for the caller's planes):
+ * out_padded takes the resident form, hp x wp dwords R | G << 10 | B << 20 (hp, wp = h, w rounded up to 32n), padding included.  force_scalar: 0 = the host's choice,
+ * 1 = the scalar form.  The rules of rife_hip_hbd_check hold (-RIFE_HIP_EINVAL before anything is uploaded). */
+int rife_hip_op_hbd_to_rgb10(int gpuid, const rife_hip_image_t* img, int depth, uint32_t* out_padded, int force_scalar);
+/* op_apply_yuv: the apply launches of a subsampled high-bit-depth image alone (csrc/apply_yuv.h), on a luma set (shift 0, 0), a chroma set (shift -1, -1 or -1, 0) and a
+ * motion of mw x mh in HOST memory, uploaded as op_apply_scaled uploads them (pitches and pointer alignment modulo 16 kept; the output planes come back with every byte
+ * the launch did not write as it went in).  Where the host's rule admits it - u16 samples, at least 4 luma columns, luma output pointers and pitches aligned to 8 bytes
+ * and chroma ones to 4, RIFE_HIP_APPLY_YUV not 0 - this is ONE launch of k_apply_yuv and the call returns 1; everywhere else it is the two launches of the sets calls
+ * and the call returns 0.  The rules of the sets calls hold (-RIFE_HIP_EINVAL before anything is uploaded), and the two shifts must be as named. */
+int rife_hip_op_apply_yuv(int gpuid, const rife_hip_apply_set_t* luma_set, const rife_hip_apply_set_t* chroma_set, const rife_hip_motion_t* host_motion, int mw, int mh);
 
 /* ---- the generic layer-wise graph executor (csrc/graph_exec.h, graph_run.h, graph_kernels.h: the v1 family) on any .param / .bin pair, one graph_run per call.
  * graph_plan needs no device: it parses <base>.param as rife_hip_graph_check does and writes what the loader settled on, one line per layer, tab-separated:

@@ -38,6 +38,7 @@ C_ABI_SYMBOLS = [
     "rife_hip_motion_check", "rife_hip_process_motion", "rife_hip_process_device_motion", "rife_hip_process_frames_motion",
     "rife_hip_planes_check", "rife_hip_padded_size", "rife_hip_apply_device_motion", "rife_hip_apply_motion", "rife_hip_process_apply", "rife_hip_process_device_apply",
     "rife_hip_apply_set_check", "rife_hip_apply_device_motion_sets", "rife_hip_apply_motion_sets", "rife_hip_process_apply_sets", "rife_hip_process_device_apply_sets",
+    "rife_hip_hbd_check", "rife_hip_process_hbd", "rife_hip_process_device_hbd",
 ]
 # include/rife_hip.h RIFE_HIP_PRECISION_*: FULL = two f16 products per weight tap of the residual trunks (fp32-equivalent), FAST = one, the skip at full precision
 PRECISION_FULL, PRECISION_FAST = 0, 1
@@ -67,7 +68,7 @@ _SAMPLE_OF = {np.dtype(v): k for k, v in _SAMPLE_DTYPE.items()}
 TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_hip_v4_tap", "rife_hip_v4_process_injected", "rife_hip_op_conv3x3", "rife_hip_op_deconv4x4", "rife_hip_op_warp", "rife_hip_pool_state",
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
-                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply", "rife_hip_op_apply_scaled",
+                    "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply", "rife_hip_op_apply_scaled", "rife_hip_op_hbd_to_rgb10", "rife_hip_op_apply_yuv",
                     "rife_hip_graph_plan", "rife_hip_graph_eval"]
 # rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
 TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
@@ -181,9 +182,14 @@ def _load(path, with_test_surface):
     L.rife_hip_apply_motion_sets.argtypes = [vp, ci, sp, mp, ci, ci]
     L.rife_hip_process_apply_sets.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, ci, sp]
     L.rife_hip_process_device_apply_sets.argtypes = [vp, vp, vp, ci, ci, cf, vp, ci, ci, sp, vp]
+    L.rife_hip_hbd_check.argtypes = [ip, ci]
+    L.rife_hip_process_hbd.argtypes = [vp, ip, ip, cf, ip, ci]
+    L.rife_hip_process_device_hbd.argtypes = [vp, ip, ip, cf, ip, ci, vp]
     if with_test_surface:
         L.rife_hip_op_apply.argtypes = [ci, pp, pp, mp, ci, ci, pp, ci]
         L.rife_hip_op_apply_scaled.argtypes = [ci, sp, mp, ci, ci, ci]
+        L.rife_hip_op_hbd_to_rgb10.argtypes = [ci, ip, ci, vp, ci]
+        L.rife_hip_op_apply_yuv.argtypes = [ci, sp, sp, mp, ci, ci]
         L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
         L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
         L.rife_hip_v4_extract_flow.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp]
@@ -466,6 +472,12 @@ def planes_image(planes, w, h, pixfmt, what="planes", writable=False):
     im = device_image(w, h, pixfmt, [(a.ctypes.data, _pitch(a)) for a in planes])
     im._keep = tuple(planes)
     return im
+
+
+def hbd_check(img, depth):
+    """rife_hip_hbd_check (host only): raises RifeError with the fault of the high-bit-depth image `img` (a rife_hip_image of u16 planes: planes_image() with
+    PIX_I420P10 / I422P10 / I444P10 / RGBP10, or device_image()) whose samples carry `depth` bits, 10..16."""
+    _check(lib().rife_hip_hbd_check(ctypes.byref(img) if img is not None else None, int(depth)), "hbd_check")
 
 
 def _plane_tuple(planes):
@@ -994,6 +1006,28 @@ class RIFE:
         _check(self._L.rife_hip_process_device_apply_sets(self._h, d_in0, d_in1, int(w), int(h), float(timestep), d_out, int(pixfmt), n, arr, stream),
                "process_device_apply_sets", self._L)
 
+    def process_hbd(self, planes0, planes1, timestep, depth, pixfmt, out=None):
+        """rife_hip_process_hbd (include/rife_hip.h "high bit depth"): planes of `depth`-bit samples (10..16, codes in the low bits of uint16) in the layout of
+        pixfmt = PIX_I420P10 / PIX_I422P10 / PIX_I444P10 (OR-ed with CSP_*) or PIX_RGBP10, as process_planes() takes them - (h, w) and chroma-shaped arrays, views and
+        row-padded arrays without a copy.  The motion is estimated on a ten-bit proxy made on the device and applied to the planes themselves.  out: a tuple of writable
+        plane arrays to fill, or None; returns the output planes."""
+        planes0, planes1 = _plane_tuple(planes0), _plane_tuple(planes1)
+        if out is not None:
+            out = _plane_tuple(out)
+        h, w = planes0[0].shape if len(planes0) and isinstance(planes0[0], np.ndarray) and planes0[0].ndim == 2 else (0, 0)
+        a = planes_image(planes0, w, h, pixfmt, "planes0"); b = planes_image(planes1, w, h, pixfmt, "planes1")
+        if out is None:
+            out = tuple(np.empty(p.shape, p.dtype) for p in planes0)
+        o = planes_image(out, w, h, pixfmt, "out", writable=True)
+        _check(self._L.rife_hip_process_hbd(self._h, ctypes.byref(a), ctypes.byref(b), float(timestep), ctypes.byref(o), int(depth)), "process_hbd", self._L)
+        return tuple(out)
+
+    def process_device_hbd(self, img0, img1, timestep, out, depth, stream=None):
+        """rife_hip_process_device_hbd: three rife_hip_image descriptors of DEVICE planes (device_image(w, h, pixfmt, [(ptr, pitch), ...])) of `depth`-bit samples, read and
+        written in place; enqueues on `stream` (hipStream_t as int; None = the engine's own stream, synchronised before returning)."""
+        _check(self._L.rife_hip_process_device_hbd(self._h, ctypes.byref(img0), ctypes.byref(img1), float(timestep), ctypes.byref(out), int(depth), stream),
+               "process_device_hbd", self._L)
+
     def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
         """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
         if pixfmt not in _PIX_LAYOUT and pixfmt not in _RGBP_DTYPE:
@@ -1366,6 +1400,28 @@ def op_image_to_resident(img, force_scalar=0, gpuid=0):
     out = np.empty(((img.h + 31) // 32 * 32, (img.w + 31) // 32 * 32), np.uint32)
     _check(testlib().rife_hip_op_image_to_resident(gpuid, ctypes.byref(img), int(force_scalar), _p(out)), "op_image_to_resident", testlib())
     return out
+
+
+def op_hbd_to_rgb10(img, depth, force_scalar=0, gpuid=0):
+    """rife_hip_op_hbd_to_rgb10 (test build): the high-bit-depth pre-processing kernel alone on a rife_hip_image of HOST u16 planes of `depth`-bit samples -> the resident
+    form, (hp, wp) uint32.  force_scalar=1: the scalar form."""
+    out = np.empty(((img.h + 31) // 32 * 32, (img.w + 31) // 32 * 32), np.uint32)
+    _check(testlib().rife_hip_op_hbd_to_rgb10(int(gpuid), ctypes.byref(img), int(depth), _p(out), int(force_scalar)), "op_hbd_to_rgb10", testlib())
+    return out
+
+
+def op_apply_yuv(luma0, luma1, chroma0, chroma1, flow, mask, luma_out, chroma_out, shift, maxval=None, gpuid=0):
+    """rife_hip_op_apply_yuv (test build): the apply launches of a subsampled high-bit-depth image alone - one luma plane and two chroma planes per frame (host
+    arrays as planes_of takes them, uploaded with their pitch and alignment), shift = (-1, -1) 4:2:0 or (-1, 0) 4:2:2 for the chroma planes, a motion flow (mh, mw, 4),
+    mask (mh, mw).  The output planes are written in place.  Returns True where this was ONE launch of k_apply_yuv, False where it was the two launches of the sets calls."""
+    mh, mw = mask.shape
+    sy = apply_set(luma0, luma1, (0, 0), maxval, None, luma_out)
+    sc = apply_set(chroma0, chroma1, shift, maxval, None, chroma_out)
+    m = _motion_in(mw, mh, flow, mask)
+    rc = testlib().rife_hip_op_apply_yuv(int(gpuid), ctypes.byref(sy), ctypes.byref(sc), ctypes.byref(m), mw, mh)
+    if rc < 0:
+        _check(rc, "op_apply_yuv", testlib())
+    return rc == 1
 
 
 def op_resident_to_image(tight, img, force_scalar=0, gpuid=0):

@@ -42,12 +42,15 @@
 #include "flow_cascade.h"
 #include "yuv.h"
 #include "planes.h"
+#include "hbd.h"
 #include "image_check.h"
 #include "motion_check.h"
 #include "apply_check.h"
 #include "apply_set_check.h"
+#include "hbd_check.h"
 #include "apply_motion.h"
 #include "apply_scaled.h"
+#include "apply_yuv.h"
 #include "elementwise_v2.h"
 #include "stem_fused.h"
 #include "stem_fused_v2.h"
@@ -76,3 +79,4 @@
 #include "engine_image.h"
 #include "engine_apply.h"
 #include "engine_apply_sets.h"
+#include "engine_hbd.h"

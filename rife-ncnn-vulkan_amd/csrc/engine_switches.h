@@ -47,6 +47,7 @@ struct Switches {
     // ---- call scope
     bool merge_flow0;          // RIFE_HIP_MERGE_FLOW0=0: three separate flow updates
     bool flow_cascade;         // RIFE_HIP_FLOW_CASCADE=0: k_flow_update2 / k_flow_update after blocks 1 / 2 instead of k_flow_cascade (flow_cascade.h)
+    bool apply_yuv;            // RIFE_HIP_APPLY_YUV=0: the luma and chroma sets of a subsampled hbd image as two launches instead of k_apply_yuv (apply_yuv.h)
     int batch_groups;          // RIFE_HIP_BATCH_GROUPS=1 / 0: force / forbid the lockstep groups of process_batch; -1 = by grid size
     bool profile_fine;         // RIFE_HIP_PROFILE_FINE=1 (product): per-layer profile classes
     int probe_lds; const char* probe_scrub; bool probe_quiet;      // RIFE_HIP_PROBE_LDS / SCRUB / QUIET: parameters of rife_hip_bench_stem_probe (bench build, bench_hooks.h)
@@ -91,6 +92,7 @@ static Switches read_switches() {
     s.fuse_flow = on(ab("RIFE_HIP_FUSE_FLOW"));
     s.merge_flow0 = not_off(ab("RIFE_HIP_MERGE_FLOW0"));
     s.flow_cascade = not_off(ab("RIFE_HIP_FLOW_CASCADE"));
+    s.apply_yuv = not_off(ab("RIFE_HIP_APPLY_YUV"));
     { const char* e = ab("RIFE_HIP_BATCH_GROUPS"); s.batch_groups = e ? (e[0] != '0' ? 1 : 0) : -1; }
     { const char* e = ab("RIFE_HIP_PROBE_LDS"); s.probe_lds = e ? atoi(e) : -1; }
     s.probe_scrub = ab("RIFE_HIP_PROBE_SCRUB");

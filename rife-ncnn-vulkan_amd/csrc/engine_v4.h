@@ -482,13 +482,19 @@ static void launch_final_motion(hipStream_t st, const uint32_t* img0, const uint
 // unused and d_out is the tight frame an RGB format's quantising kernels write
 // mo != null (a motion call, engine_abi.h; plain rife-v4.6 only): the kernel that finishes the frame - whichever this schedule selects, and the selection never looks at
 // mo - runs in its motion form and stores each pixel's final flow and blend weight into the caller's device buffers
+// hbd != null (a high-bit-depth call, engine_hbd.h; with mo): the frames are the caller's u16 planes at hbd->depth bits, reduced to ten bits by the pre-processing
+// kernels of hbd.h; the pass ends with the tight A2B10G10R10 frame in the workspace (Ctx::yuv_rgb) - nobody wants the proxy's planes, so no post-processing launch;
+// d_in0 / d_in1 / d_out are unused
 static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t* d_in1, float timestep, uint8_t* d_out, const float* tsp = nullptr, const PlaneIO* pio = nullptr,
-                  const MotionArgs* mo = nullptr) {
+                  const MotionArgs* mo = nullptr, const HbdIO* hbd = nullptr) {
     hipStream_t st = c.stream;
     int rc;
     {
         Timed t(E.prof, "preproc", 0, st);
-        if (pio) {      // an image call: the caller's planes with their pitches (planes.h)
+        if (hbd) {
+            launch_preproc_hbd(st, hbd->in0, c.w, c.h, c.img0, c.wp, c.hp, c.pixfmt, hbd->depth);
+            launch_preproc_hbd(st, hbd->in1, c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt, hbd->depth);
+        } else if (pio) {      // an image call: the caller's planes with their pitches (planes.h)
             launch_preproc_planes(st, pio->in0, c.w, c.h, c.img0, c.wp, c.hp, c.pixfmt);
             launch_preproc_planes(st, pio->in1, c.w, c.h, c.img1, c.wp, c.hp, c.pixfmt);
         } else {
@@ -557,7 +563,7 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
         else hipLaunchKernelGGL(k_final, grid2d(c.w, c.h), dim3(256), 0, st, c.img0, c.img1, c.F, c.M, c.flow[3], d_out, c.w, c.h, c.wp, c.hp);
         HIPCHK(hipGetLastError());
     }
-    if (pix_conv(c.pixfmt)) {
+    if (pix_conv(c.pixfmt) && !hbd) {
         Timed t(E.prof, postproc_class(c.pixfmt), 0, st);
         if (pio) launch_postproc_yuv_planes(st, c.yuv_rgb, c.w, c.h, pio->out, c.pixfmt);
         else launch_postproc_conv(st, c.yuv_rgb, c.w, c.h, caller_out, c.pixfmt);

@@ -239,6 +239,23 @@ int RIFE::process_apply_sets(const void* in0, const void* in1, int w, int h, flo
     return ret;
 }
 
+// weak like the apply calls
+extern "C" int rife_hip_process_hbd(const rife_hip_t* r, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out, int depth)
+    __attribute__((weak));
+
+int RIFE::process_hbd(const rife_hip_image_t& in0, const rife_hip_image_t& in1, float timestep, const rife_hip_image_t& out, int depth) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_process_hbd)
+    {
+        fprintf(stderr, "RIFE::process_hbd: this engine has no high bit depth call\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_process_hbd(engine, &in0, &in1, timestep, &out, depth);
+    if (ret) fprintf(stderr, "RIFE::process_hbd: %s\n", rife_hip_last_error());
+    return ret;
+}
+
 rife_hip_frame* RIFE::upload_yuv(const void* frame, int w, int h, int pixfmt) const
 {
     if (!engine || !frame) return 0;

@@ -70,6 +70,9 @@ public:
     // with a shift pair each - (0, 0), (-1, -1) 4:2:0 chroma, (-1, 0) 4:2:2 chroma, (1, 1) proxy upscaling - on a motion of mw x mh (process_apply_sets: w x h).
     int apply_motion_sets(int nsets, const rife_hip_apply_set_t* sets, const rife_hip_motion_t& motion, int mw, int mh) const;
     int process_apply_sets(const void* in0, const void* in1, int w, int h, float timestep, void* out, int pixfmt, int nsets, const rife_hip_apply_set_t* sets) const;
+    // High-bit-depth planes in one call (include/rife_hip.h "high bit depth"): host planes of `depth`-bit samples (10..16) in u16, laid out as RIFE_HIP_PIX_I420P10 /
+    // _I422P10 / _I444P10 / _RGBP10 images; the ten-bit proxy the motion is estimated on is made on the device, the blend runs on the planes themselves.
+    int process_hbd(const rife_hip_image_t& in0, const rife_hip_image_t& in1, float timestep, const rife_hip_image_t& out, int depth) const;
 
     // Extension, not in the reference (include/rife_hip.h "strides and planes"): frames as an AVFrame or a VapourSynth frame holds them - a pointer and a
     // pitch in BYTES per plane, any of the _px formats (planar RGB: R, G, B in plane[0..2]; ffmpeg's gbrp: permute them).  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
