@@ -489,6 +489,47 @@ int rife_hip_process_hbd(const rife_hip_t* r, const rife_hip_image_t* in0, const
 int rife_hip_process_device_hbd(const rife_hip_t* r, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out, int depth,
                                 void* hip_stream);
 
+/* ---- 16-bit packed RGB and RGBA: interleaved 10..16-bit samples in ONE call - 16-bit PNG / PPM stills with or without a matte (absent in the reference) --------------
+ * The hbd calls above take planes; a decoded 16-bit PNG is interleaved, R G B (A) per pixel.  These calls take such frames as they are: the same mechanism - motion
+ * estimated on a ten-bit proxy made on the device, the caller's own samples blended at fp32 - with kernels that read and write packed pixels, so nobody de-interleaves.
+ * The resident frame format, every trunk kernel and every existing call are untouched; there is no new pixfmt number.  A packed image is a descriptor of its own
+ * (rife_hip_packed_t below): h rows of w pixels of `channels` interleaved native-endian u16 samples, codes of `depth` bits in the LOW bits.
+ * Definition, operation by operation (tests/packed_ref.py states it in numpy); P_k(img) is the w x h plane of channel k of a packed image:
+ *   proxy          the TIGHT RIFE_HIP_PIX_RGBP10 frame whose planes are reduce10(P_0), reduce10(P_1), reduce10(P_2), with the hbd section's reduction
+ *                      depth > 10:  c = min((v + (1 << (depth - 11))) >> (depth - 10), 1023)        depth = 10:  c = min(v, 1023)
+ *                  Alpha never reaches the network.
+ *   result         channel k of `out` is, byte for byte, plane k of rife_hip_process_apply_sets(r, proxy0, proxy1, w, h, timestep, NULL, RIFE_HIP_PIX_RGBP10, 1, set)
+ *                  with the set of n = channels planes P_k(in0), P_k(in1), shift (0, 0), RIFE_HIP_SAMPLE_U16, maxval = (1 << depth) - 1, extent 0, 0 (edge
+ *                  semantics).  For channels = 3 this is rife_hip_process_hbd with the RGBP10 layout on the de-interleaved planes.  The alpha channel is a fourth
+ *                  plane of the same set: warped by the flow estimated from the colour it belongs to, blended by the same mask, with edge clamping - the engine's
+ *                  alpha rule.  Opaque in (A = maxval everywhere) gives maxval everywhere.  Straight or premultiplied: the four channels are interpolated as given.
+ *   timestep 0, 1  no network pass: the samples of frame 0 / frame 1 copied, each clamped to maxval.
+ * Input samples above maxval are read as stored by the blend and clamped only in the proxy (the rule of the apply calls).  The host call stages both frames once
+ * (2 bytes per sample, tight) and brings the result back with one 2-D copy; the device call reads and writes the caller's frames in place, stream semantics as for the
+ * device _px call.
+ * Scope: that of the hbd calls - model family rife-v4.6, plain mode, flow scale 1 and 2, precision full and fast.  Any other family or mode (-x, -z, -u) returns
+ * -RIFE_HIP_ENOSYS with a message that names it and the words "high bit depth", before anything is written.
+ * Rules (rife_hip_packed_check states them for one image; both calls repeat them for their three images before they touch anything; a violation is -RIFE_HIP_EINVAL with
+ * the fault named and the prefix "high bit depth: image 0: " / "image 1: " / "image out: "): w, h > 0; channels is 3 or 4; depth is in 10..16; data is non-NULL and
+ * aligned to 2; pitch is positive, at least w * channels * 2, a multiple of 2 and at most INT32_MAX; w * h <= 2^27; h * pitch < 2^32; the three images of a call agree
+ * in w, h, channels and depth.  Argument checks come before "no HIP device".  Row padding and everything around `out` is never written.  The output must not overlap the
+ * inputs (documented, not checked).
+ * Out of scope: a public apply-only call on packed frames; packed float or u8 frames; BGR(A) channel order; resident packed frames (stream mode) and the batch calls;
+ * MSB-aligned samples. */
+typedef struct rife_hip_packed {
+    int w, h;
+    int channels;      /* 3: R G B;  4: R G B A */
+    int depth;         /* 10..16: codes of `depth` bits in the LOW bits of native-endian u16 */
+    void* data;        /* h rows of w pixels of `channels` interleaved u16 samples */
+    ptrdiff_t pitch;   /* BYTES from one row to the next */
+} rife_hip_packed_t;
+int rife_hip_packed_check(const rife_hip_packed_t* img);                     /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
+/* frames in host memory */
+int rife_hip_process_hbd_packed(const rife_hip_t* r, const rife_hip_packed_t* in0, const rife_hip_packed_t* in1, float timestep, const rife_hip_packed_t* out);
+/* frames in device memory; stream semantics as for the device _px call (NULL = the engine's own stream, synchronised before returning) */
+int rife_hip_process_device_hbd_packed(const rife_hip_t* r, const rife_hip_packed_t* in0, const rife_hip_packed_t* in1, float timestep, const rife_hip_packed_t* out,
+                                       void* hip_stream);
+
 const char* rife_hip_last_error(void);
 
 /* ---- measurement hooks (bench.py / profiles) ---------------------------------------------------------------

@@ -160,6 +160,16 @@ int rife_hip_op_hbd_to_rgb10(int gpuid, const rife_hip_image_t* img, int depth, 
  * and chroma ones to 4, RIFE_HIP_APPLY_YUV not 0 - this is ONE launch of k_apply_yuv and the call returns 1; everywhere else it is the two launches of the sets calls
  * and the call returns 0.  The rules of the sets calls hold (-RIFE_HIP_EINVAL before anything is uploaded), and the two shifts must be as named. */
 int rife_hip_op_apply_yuv(int gpuid, const rife_hip_apply_set_t* luma_set, const rife_hip_apply_set_t* chroma_set, const rife_hip_motion_t* host_motion, int mw, int mh);
+/* op_packed_to_rgb10: the packed pre-processing kernel alone (csrc/hbd_packed.h; include/rife_hip.h "16-bit packed RGB and RGBA"), ONE launch on a packed image in HOST
+ * memory, uploaded as op_apply uploads a plane (pitch and pointer alignment modulo 16 kept, so the form the host picks is the one it would pick for the caller's frame):
+ * out_padded takes the resident form, hp x wp dwords R | G << 10 | B << 20 (hp, wp = h, w rounded up to 32n), padding included.  force_scalar: 0 = the host's choice,
+ * 1 = the scalar form.  Returns 1 where the vector form ran, 0 for the scalar form.  The rules of rife_hip_packed_check hold (-RIFE_HIP_EINVAL before anything is uploaded). */
+int rife_hip_op_packed_to_rgb10(int gpuid, const rife_hip_packed_t* img, uint32_t* out_padded, int force_scalar);
+/* op_apply_packed: the packed blend alone (csrc/hbd_packed.h), ONE launch on three packed images and a motion of w x h in HOST memory, uploaded as op_apply uploads them
+ * (the output comes back with every byte the kernel did not write as it went in).  force_scalar: 0 = the host's choice, 1 = the one-pixel-per-lane form.  Returns 1 where
+ * the vector form ran, 0 for the scalar form.  The rules of the packed calls and of the motion hold (-RIFE_HIP_EINVAL before anything is uploaded). */
+int rife_hip_op_apply_packed(int gpuid, const rife_hip_packed_t* p0, const rife_hip_packed_t* p1, const rife_hip_packed_t* out, const rife_hip_motion_t* host_motion,
+                             int force_scalar);
 
 /* ---- the generic layer-wise graph executor (csrc/graph_exec.h, graph_run.h, graph_kernels.h: the v1 family) on any .param / .bin pair, one graph_run per call.
  * graph_plan needs no device: it parses <base>.param as rife_hip_graph_check does and writes what the loader settled on, one line per layer, tab-separated:

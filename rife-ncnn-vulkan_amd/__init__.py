@@ -39,6 +39,7 @@ C_ABI_SYMBOLS = [
     "rife_hip_planes_check", "rife_hip_padded_size", "rife_hip_apply_device_motion", "rife_hip_apply_motion", "rife_hip_process_apply", "rife_hip_process_device_apply",
     "rife_hip_apply_set_check", "rife_hip_apply_device_motion_sets", "rife_hip_apply_motion_sets", "rife_hip_process_apply_sets", "rife_hip_process_device_apply_sets",
     "rife_hip_hbd_check", "rife_hip_process_hbd", "rife_hip_process_device_hbd",
+    "rife_hip_packed_check", "rife_hip_process_hbd_packed", "rife_hip_process_device_hbd_packed",
 ]
 # include/rife_hip.h RIFE_HIP_PRECISION_*: FULL = two f16 products per weight tap of the residual trunks (fp32-equivalent), FAST = one, the skip at full precision
 PRECISION_FULL, PRECISION_FAST = 0, 1
@@ -69,6 +70,7 @@ TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_h
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
                     "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply", "rife_hip_op_apply_scaled", "rife_hip_op_hbd_to_rgb10", "rife_hip_op_apply_yuv",
+                    "rife_hip_op_packed_to_rgb10", "rife_hip_op_apply_packed",
                     "rife_hip_graph_plan", "rife_hip_graph_eval"]
 # rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
 TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
@@ -93,6 +95,11 @@ class rife_hip_planes(ctypes.Structure):
     """rife_hip_planes_t of include/rife_hip.h: n (1..4) planes of w x h samples of one type, a pointer and a pitch in BYTES each; maxval for integer samples, else 0."""
     _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("n", ctypes.c_int), ("sample", ctypes.c_int), ("maxval", ctypes.c_int), ("plane", ctypes.c_void_p * 4),
                 ("pitch", ctypes.c_ssize_t * 4)]
+
+
+class rife_hip_packed(ctypes.Structure):
+    """rife_hip_packed_t of include/rife_hip.h: h rows of w pixels of `channels` (3, 4) interleaved u16 samples of `depth` bits, a pointer and a pitch in BYTES."""
+    _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("channels", ctypes.c_int), ("depth", ctypes.c_int), ("data", ctypes.c_void_p), ("pitch", ctypes.c_ssize_t)]
 
 
 class rife_hip_apply_set(ctypes.Structure):
@@ -185,11 +192,17 @@ def _load(path, with_test_surface):
     L.rife_hip_hbd_check.argtypes = [ip, ci]
     L.rife_hip_process_hbd.argtypes = [vp, ip, ip, cf, ip, ci]
     L.rife_hip_process_device_hbd.argtypes = [vp, ip, ip, cf, ip, ci, vp]
+    kp = ctypes.POINTER(rife_hip_packed)
+    L.rife_hip_packed_check.argtypes = [kp]
+    L.rife_hip_process_hbd_packed.argtypes = [vp, kp, kp, cf, kp]
+    L.rife_hip_process_device_hbd_packed.argtypes = [vp, kp, kp, cf, kp, vp]
     if with_test_surface:
         L.rife_hip_op_apply.argtypes = [ci, pp, pp, mp, ci, ci, pp, ci]
         L.rife_hip_op_apply_scaled.argtypes = [ci, sp, mp, ci, ci, ci]
         L.rife_hip_op_hbd_to_rgb10.argtypes = [ci, ip, ci, vp, ci]
         L.rife_hip_op_apply_yuv.argtypes = [ci, sp, sp, mp, ci, ci]
+        L.rife_hip_op_packed_to_rgb10.argtypes = [ci, kp, vp, ci]
+        L.rife_hip_op_apply_packed.argtypes = [ci, kp, kp, kp, mp, ci]
         L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
         L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
         L.rife_hip_v4_extract_flow.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp]
@@ -478,6 +491,29 @@ def hbd_check(img, depth):
     """rife_hip_hbd_check (host only): raises RifeError with the fault of the high-bit-depth image `img` (a rife_hip_image of u16 planes: planes_image() with
     PIX_I420P10 / I422P10 / I444P10 / RGBP10, or device_image()) whose samples carry `depth` bits, 10..16."""
     _check(lib().rife_hip_hbd_check(ctypes.byref(img) if img is not None else None, int(depth)), "hbd_check")
+
+
+def packed_desc(w, h, channels, depth, data, pitch):
+    """A rife_hip_packed from a raw address (int; device memory for process_device_hbd_packed(), or any of the C calls) and a pitch in bytes."""
+    return rife_hip_packed(int(w), int(h), int(channels), int(depth), int(data) or None, int(pitch))
+
+
+def packed_of(arr, depth, what="frame", writable=False):
+    """The descriptor of a packed 16-bit frame WITHOUT copying it: an (h, w, 3 | 4) uint16 array of `depth`-bit samples whose last two axes are contiguous - a tight
+    array, a crop or an array with padded rows.  Raises ValueError."""
+    if (not isinstance(arr, np.ndarray) or arr.dtype != np.uint16 or arr.ndim != 3 or arr.shape[2] not in (3, 4) or arr.size == 0 or not _rows_strided(arr)
+            or (writable and not arr.flags.writeable)):
+        raise ValueError("%s: a%s uint16 array of shape (h, w, 3) or (h, w, 4) whose last two axes are contiguous" % (what, " writable" if writable else ""))
+    d = packed_desc(arr.shape[1], arr.shape[0], arr.shape[2], depth, arr.ctypes.data, _pitch(arr))
+    d._keep = arr      # the descriptor holds a raw address: the array lives as long as it does
+    return d
+
+
+def packed_check(arr, depth):
+    """rife_hip_packed_check (host only): raises RifeError with the fault of the packed frame `arr` - an (h, w, 3 | 4) uint16 array as packed_of() takes it, or a
+    rife_hip_packed descriptor (packed_desc()) - whose samples carry `depth` bits, 10..16."""
+    d = arr if isinstance(arr, rife_hip_packed) or arr is None else packed_of(arr, depth)
+    _check(lib().rife_hip_packed_check(ctypes.byref(d) if d is not None else None), "packed_check")
 
 
 def _plane_tuple(planes):
@@ -1028,6 +1064,24 @@ class RIFE:
         _check(self._L.rife_hip_process_device_hbd(self._h, ctypes.byref(img0), ctypes.byref(img1), float(timestep), ctypes.byref(out), int(depth), stream),
                "process_device_hbd", self._L)
 
+    def process_hbd_packed(self, in0, in1, timestep, depth, out=None):
+        """rife_hip_process_hbd_packed (include/rife_hip.h "16-bit packed RGB and RGBA"): two (h, w, 3) or (h, w, 4) uint16 frames of `depth`-bit samples (10..16, codes
+        in the low bits), R G B (A) interleaved; views and row-padded arrays are taken without a copy (the last two axes contiguous).  The motion is estimated on a
+        ten-bit proxy of the colour channels made on the device and applied to all channels of the frames themselves.  out: a writable array to fill, or None;
+        returns the output frame."""
+        a = packed_of(in0, depth, "in0"); b = packed_of(in1, depth, "in1")
+        if out is None:
+            out = np.empty(in0.shape, np.uint16)
+        o = packed_of(out, depth, "out", writable=True)
+        _check(self._L.rife_hip_process_hbd_packed(self._h, ctypes.byref(a), ctypes.byref(b), float(timestep), ctypes.byref(o)), "process_hbd_packed", self._L)
+        return out
+
+    def process_device_hbd_packed(self, img0, img1, timestep, out, stream=None):
+        """rife_hip_process_device_hbd_packed: three rife_hip_packed descriptors of DEVICE frames (packed_desc(w, h, channels, depth, ptr, pitch)), read and written in
+        place; enqueues on `stream` (hipStream_t as int; None = the engine's own stream, synchronised before returning)."""
+        _check(self._L.rife_hip_process_device_hbd_packed(self._h, ctypes.byref(img0), ctypes.byref(img1), float(timestep), ctypes.byref(out), stream),
+               "process_device_hbd_packed", self._L)
+
     def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
         """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
         if pixfmt not in _PIX_LAYOUT and pixfmt not in _RGBP_DTYPE:
@@ -1408,6 +1462,28 @@ def op_hbd_to_rgb10(img, depth, force_scalar=0, gpuid=0):
     out = np.empty(((img.h + 31) // 32 * 32, (img.w + 31) // 32 * 32), np.uint32)
     _check(testlib().rife_hip_op_hbd_to_rgb10(int(gpuid), ctypes.byref(img), int(depth), _p(out), int(force_scalar)), "op_hbd_to_rgb10", testlib())
     return out
+
+
+def op_packed_to_rgb10(arr, depth, force_scalar=0, gpuid=0):
+    """rife_hip_op_packed_to_rgb10 (test build): the packed pre-processing kernel alone on an (h, w, 3 | 4) uint16 HOST frame (as packed_of takes it, uploaded with its
+    pitch and alignment) -> (the resident form, (hp, wp) uint32; True where the vector form ran).  force_scalar=1: the scalar form."""
+    d = packed_of(arr, depth)
+    out = np.empty(((d.h + 31) // 32 * 32, (d.w + 31) // 32 * 32), np.uint32)
+    rc = testlib().rife_hip_op_packed_to_rgb10(int(gpuid), ctypes.byref(d), _p(out), int(force_scalar))
+    if rc < 0:
+        _check(rc, "op_packed_to_rgb10", testlib())
+    return out, rc == 1
+
+
+def op_apply_packed(in0, in1, flow, mask, out, depth, force_scalar=0, gpuid=0):
+    """rife_hip_op_apply_packed (test build): ONE launch of the packed blend on (h, w, 3 | 4) uint16 HOST frames (as packed_of takes them) and host motion flow
+    (h, w, 4), mask (h, w); `out` is written in place - every byte the kernel did not write keeps its value.  Returns True where the vector form ran."""
+    d0 = packed_of(in0, depth, "in0"); d1 = packed_of(in1, depth, "in1"); do = packed_of(out, depth, "out", writable=True)
+    m = _motion_in(d0.w, d0.h, flow, mask)
+    rc = testlib().rife_hip_op_apply_packed(int(gpuid), ctypes.byref(d0), ctypes.byref(d1), ctypes.byref(do), ctypes.byref(m), int(force_scalar))
+    if rc < 0:
+        _check(rc, "op_apply_packed", testlib())
+    return rc == 1
 
 
 def op_apply_yuv(luma0, luma1, chroma0, chroma1, flow, mask, luma_out, chroma_out, shift, maxval=None, gpuid=0):

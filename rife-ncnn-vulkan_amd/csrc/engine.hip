@@ -51,6 +51,8 @@
 #include "apply_motion.h"
 #include "apply_scaled.h"
 #include "apply_yuv.h"
+#include "hbd_packed.h"
+#include "packed_check.h"
 #include "elementwise_v2.h"
 #include "stem_fused.h"
 #include "stem_fused_v2.h"
@@ -80,3 +82,4 @@
 #include "engine_apply.h"
 #include "engine_apply_sets.h"
 #include "engine_hbd.h"
+#include "engine_hbd_packed.h"

@@ -489,7 +489,14 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
                   const MotionArgs* mo = nullptr, const HbdIO* hbd = nullptr) {
     hipStream_t st = c.stream;
     int rc;
-    {
+    if (hbd && hbd->packed) {      // a packed 16-bit call (engine_hbd_packed.h): one launch per input, a profiler class of its own
+        for (int i = 0; i < 2; i++) {
+            const PlaneSet& in = i ? hbd->in1 : hbd->in0;
+            Timed t(E.prof, "preproc_packed", 0, st);
+            launch_preproc_packed(st, in.p[0], in.pitch[0], hbd->packed, c.w, c.h, i ? c.img1 : c.img0, c.wp, c.hp, hbd->depth);
+            HIPCHK(hipGetLastError());
+        }
+    } else {
         Timed t(E.prof, "preproc", 0, st);
         if (hbd) {
             launch_preproc_hbd(st, hbd->in0, c.w, c.h, c.img0, c.wp, c.hp, c.pixfmt, hbd->depth);

@@ -155,6 +155,7 @@ static inline void launch_preproc_hbd(hipStream_t st, const PlaneSet& s, int w, 
 struct HbdIO {
     PlaneSet in0, in1;
     int depth;
+    int packed = 0;      // 3 / 4: in0.p[0], in1.p[0] are packed frames of that many interleaved samples per pixel (hbd_packed.h); 0: planes
 };
 
 }  // namespace rife

@@ -79,8 +79,9 @@ static int paeth(int a, int b, int c) {
 // `alpha` != null (-a): the file's alpha as w x h bytes - the alpha channel of colour types 4 / 6 (16-bit: its high byte, like the colour), the tRNS chunk of a
 // palette file (entries beyond it are opaque) or the tRNS colour key of a grey / RGB file (the pixel that equals the key in every bit is clear, all others
 // opaque); it stays EMPTY for a file that has neither
+// `wide_alpha` != null (-b 16 -a, with `wide`): the alpha channel of a 16-bit file of colour type 4 / 6 with its full samples (w x h, host order); empty otherwise
 static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std::vector<unsigned char>& rgb, std::vector<uint16_t>* wide = nullptr,
-                       std::vector<unsigned char>* alpha = nullptr) {
+                       std::vector<unsigned char>* alpha = nullptr, std::vector<uint16_t>* wide_alpha = nullptr) {
     static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     if (d.size() < 33 || memcmp(d.data(), sig, 8)) return false;
     size_t pos = 8;
@@ -131,6 +132,8 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
     if (has_alpha) alpha->assign((size_t)w * h, 255);
     if (wide) wide->clear();
     if (wide && depth == 16) wide->assign((size_t)w * h * 3, 0);
+    if (wide_alpha) wide_alpha->clear();
+    if (wide_alpha && wide && depth == 16 && (ctype == 4 || ctype == 6)) wide_alpha->assign((size_t)w * h, 0);
     const int gscale = depth == 1 ? 255 : depth == 2 ? 85 : depth == 4 ? 17 : 1;
     size_t off = 0;
     for (int p = 0; p < npass; p++) {
@@ -177,6 +180,10 @@ static bool decode_png(const std::vector<unsigned char>& d, int& w, int& h, std:
                     for (int c = 0; c < 3; c++) {
                         const unsigned char* s16 = &row[((size_t)x * ch + (ch >= 3 ? c : 0)) * 2];
                         o16[c] = (uint16_t)((s16[0] << 8) | s16[1]);
+                    }
+                    if (wide_alpha && !wide_alpha->empty()) {
+                        const unsigned char* s16 = &row[((size_t)x * ch + (ch - 1)) * 2];
+                        (*wide_alpha)[(size_t)oy * w + ox] = (uint16_t)((s16[0] << 8) | s16[1]);
                     }
                 }
                 if (has_alpha) {
@@ -557,6 +564,60 @@ static bool encode_image10(const std::string& path, int w, int h, const uint16_t
     return encode_png(path, w, h, be.data(), 16);
 }
 
+// ---- -b 16 [-a]: frames as 16-bit samples (u16 x 3 or x 4 per pixel, R G B (A) interleaved; include/rife_hip.h rife_hip_packed_t) ----
+// a 16-bit PNG (colour types 0, 2, 4, 6) or a PPM with maxval 65535: the full samples; a PPM with maxval 1023: (c << 6) | (c >> 4); every 8-bit file: v * 257.
+// ch = 4 (-a): a 16-bit alpha channel in full, 8-bit alpha (and a tRNS colour key or palette entry, 0 / 255 / the entry) as a * 257, a file without alpha opaque
+static bool decode_image16(const std::string& path, int& w, int& h, int ch, std::vector<uint16_t>& px) {
+    std::vector<unsigned char> d, rgb, al;
+    if (!read_file(path, d)) return false;
+    std::vector<uint16_t> wide, wal;
+    int maxval = 0;
+    if (decode_png(d, w, h, rgb, &wide, ch == 4 ? &al : nullptr, ch == 4 ? &wal : nullptr)) {
+    } else if (decode_ppm(d, w, h, rgb, &wide, &maxval)) {
+        al.clear(); wal.clear();
+        if (maxval == 1023) for (uint16_t& c : wide) c = (uint16_t)((c << 6) | (c >> 4));
+    } else {
+        wide.clear(); wal.clear();
+        if (ch == 4) {                                                   // WebP, BMP, JPEG: the 8-bit readers of -a
+            std::vector<unsigned char> rgba;
+            if (!decode_image_rgba(path, w, h, rgba)) return false;
+            px.resize(rgba.size());
+            for (size_t i = 0; i < rgba.size(); i++) px[i] = (uint16_t)(rgba[i] * 257);
+            return true;
+        }
+        if (!(decode_webp(d, w, h, rgb) || decode_bmp(d, w, h, rgb))) {
+            std::string why;
+            if (!jpeg::decode(d, w, h, rgb, &why)) {
+                if (d.size() > 2 && d[0] == 0xFF && d[1] == 0xD8) fprintf(stderr, "%s: %s\n", path.c_str(), why.c_str());
+                return false;
+            }
+        }
+    }
+    const size_t n = (size_t)w * h;
+    if ((wide.empty() ? rgb.size() : wide.size()) != n * 3 || (!wal.empty() && wal.size() != n) || (!al.empty() && al.size() != n)) return false;
+    px.resize(n * ch);
+    for (size_t i = 0; i < n; i++) {
+        for (int c = 0; c < 3; c++) px[i * ch + c] = wide.empty() ? (uint16_t)(rgb[3 * i + c] * 257) : wide[3 * i + c];
+        if (ch == 4) px[i * 4 + 3] = !wal.empty() ? wal[i] : !al.empty() ? (uint16_t)(al[i] * 257) : (uint16_t)65535;
+    }
+    return true;
+}
+
+// .png: 16-bit RGB, or colour type 6 for ch = 4, the samples as they are; .ppm: P6 with maxval 65535, ch = 3 only
+static bool encode_image16(const std::string& path, int w, int h, int ch, const uint16_t* px) {
+    const std::string e = ext_of(path);
+    if (e == "webp" || e == "jpg" || e == "jpeg" || (e == "ppm" && ch != 3)) return false;      // refused at start-up
+    std::vector<unsigned char> be((size_t)w * h * ch * 2);
+    for (size_t i = 0; i < (size_t)w * h * ch; i++) { be[2 * i] = (unsigned char)(px[i] >> 8); be[2 * i + 1] = (unsigned char)px[i]; }
+    if (e != "ppm") return encode_png(path, w, h, be.data(), 16, ch);
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "P6\n%d %d\n65535\n", w, h);
+    const bool ok = fwrite(be.data(), 1, be.size(), f) == be.size();
+    fclose(f);
+    return ok;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // tasks and queues (src/main.cpp:231-295)
 // ---------------------------------------------------------------------------------------------------------------
@@ -567,6 +628,7 @@ struct SharedFrame {
     int w = 0, h = 0;
     std::vector<unsigned char> px;
     std::vector<uint16_t> px10;                                       // -b 10: the frame as 10-bit codes instead of px
+    std::vector<uint16_t> px16;                                       // -b 16: the frame as 16-bit samples, three or (-a) four per pixel, instead of px; never resident
     bool rgba = false;                                                // -a: px holds four bytes per pixel, R G B A
     int yuv = 0;                                                      // video mode: px holds one 4:2:0 frame of this pixfmt (RIFE_HIP_PIX_I420 / I420P10 | RIFE_HIP_CSP_*)
     const rife_hip_frame* on(const RIFE* r) {
@@ -592,6 +654,7 @@ struct Task {
     std::shared_ptr<SharedFrame> fr0, fr1;                            // decoded frames are shared between the tasks that use them
     std::vector<unsigned char> out;
     std::vector<uint16_t> out10;                                      // -b 10
+    std::vector<uint16_t> out16;                                      // -b 16
     int w = 0, h = 0;
 };
 
@@ -800,11 +863,13 @@ static void print_usage() {
     fprintf(stderr, "  -d divisor           estimate flow at 1/divisor resolution (1 or 2; rife-v4.6; for UHD material)\n");
     fprintf(stderr, "  -p precision         full (default) or fast: one f16 product per weight tap of the residual trunks (rife-v4.6; not with -x/-z)\n");
     fprintf(stderr, "  -f pattern-format    output image filename pattern format (%%08d.jpg/png/webp/ppm, default=ext/%%08d.png)\n");
-    fprintf(stderr, "  -b bit-depth         bits per sample, 8 or 10 (default=8); 10: rife-v4.6 only, 16-bit png / maxval-1023 ppm output\n");
+    fprintf(stderr, "  -b bit-depth         bits per sample, 8, 10 or 16 (default=8); 10: rife-v4.6 only, 16-bit png / maxval-1023 ppm output;\n");
+    fprintf(stderr, "                       16: rife-v4.6 only, not with -x/-z/-u; 16-bit png / maxval-65535 ppm in and out with their full samples, with -a png only\n");
     fprintf(stderr, "  -c matrix[:range]    video mode (-i in.y4m): colour description, 709 / 601 / 2020 and limited / full (default=709:limited, or the file's XCOLORRANGE);\n");
     fprintf(stderr, "                       4:2:0 YUV4MPEG2 at 8 or 10 bits, rife-v4.6 only, not with -x/-z/-u/-a/-b 10; -o - writes to stdout; -i - (stdin) is not served;\n");
     fprintf(stderr, "                       the header line must end within 256 bytes and every frame must start with a plain FRAME line (no frame parameters)\n");
-    fprintf(stderr, "  -a                   keep the alpha channel (png/webp/32-bit bmp in, png/webp out); rife-v4.6 only, not with -x/-z/-u/-b 10\n");
+    fprintf(stderr, "  -a                   keep the alpha channel (png/webp/32-bit bmp in, png/webp out); rife-v4.6 only, not with -x/-z/-u/-b 10;\n");
+    fprintf(stderr, "                       with -b 16: 16-bit RGBA png out, the alpha channel at its full depth\n");
 }
 
 static bool is_dir(const std::string& p) { struct stat s; return stat(p.c_str(), &s) == 0 && S_ISDIR(s.st_mode); }
@@ -868,6 +933,18 @@ int main(int argc, char** argv) {
         if (!encode_image10(argv[3], w, h, codes.data())) { fprintf(stderr, "encode image %s failed\n", argv[3]); return 1; }
         return 0;
     }
+    // the same for the 16-bit codecs:  rife-hip --transcode16 in.(png|ppm|...) out.(png|ppm), and with alpha  --transcode16a in out.png
+    if (argc == 4 && (std::string(argv[1]) == "--transcode16" || std::string(argv[1]) == "--transcode16a")) {
+        const int ch = std::string(argv[1]) == "--transcode16a" ? 4 : 3;
+        int w = 0, h = 0;
+        std::vector<uint16_t> px;
+        g_png_helpers = std::max(0, std::min(15, (int)std::thread::hardware_concurrency() - 1));
+        if (!decode_image16(argv[2], w, h, ch, px)) { fprintf(stderr, "decode image %s failed\n", argv[2]); return 1; }
+        const std::string e = ext_of(argv[3]);
+        if (e != "png" && !(e == "ppm" && ch == 3)) { fprintf(stderr, "16-bit frames are written as png or (without alpha) ppm with maxval 65535 only\n"); return 1; }
+        if (!encode_image16(argv[3], w, h, ch, px.data())) { fprintf(stderr, "encode image %s failed\n", argv[3]); return 1; }
+        return 0;
+    }
     std::string input0, input1, inputpath, outputpath, model = "rife-v2.3", pattern_format = "%08d.png", colour, precision_arg = "full";
     int numframe = 0;
     float timestep = 0.5f;
@@ -917,8 +994,8 @@ int main(int argc, char** argv) {
     if (jobs_load < 1 || jobs_save < 1) { fprintf(stderr, "invalid thread count argument\n"); return -1; }
     if (!jobs_proc.empty() && jobs_proc.size() != (gpuid.empty() ? 1 : gpuid.size())) { fprintf(stderr, "invalid jobs_proc thread count argument\n"); return -1; }
     for (int j : jobs_proc) if (j < 1) { fprintf(stderr, "invalid jobs_proc thread count argument\n"); return -1; }
-    if (bits != 8 && bits != 10) { fprintf(stderr, "invalid bit depth argument, must be 8 or 10\n"); return -1; }
-    const bool deep = bits == 10;
+    if (bits != 8 && bits != 10 && bits != 16) { fprintf(stderr, "invalid bit depth argument, must be 8, 10 or 16\n"); return -1; }
+    const bool deep = bits == 10, wide16 = bits == 16;
     if (flow_divisor != 1 && flow_divisor != 2) { fprintf(stderr, "invalid flow scale divisor argument (-d), must be 1 or 2\n"); return -1; }
     if (flow_divisor == 2 && (tta || tta_temporal)) {
         fprintf(stderr, "flow scale 2 (-d 2) is served in plain mode only, not with %s\n", tta ? "-x (TTA mode)" : "-z (temporal TTA mode)");
@@ -931,6 +1008,10 @@ int main(int argc, char** argv) {
         return -1;
     }
     if (keep_alpha && deep) { fprintf(stderr, "alpha (-a) is served at depth 8 only, not with -b 10 (A2B10G10R10 has two alpha bits)\n"); return -1; }
+    if (wide16 && (tta || tta_temporal || uhd)) {
+        fprintf(stderr, "16-bit frames (-b 16) are served in plain mode only, not with %s\n", tta ? "-x (TTA mode)" : tta_temporal ? "-z (temporal TTA mode)" : "-u (UHD mode)");
+        return -1;
+    }
     if (keep_alpha && (tta || tta_temporal || uhd)) {
         fprintf(stderr, "alpha (-a) is served in plain mode only, not with %s\n", tta ? "-x (TTA mode)" : tta_temporal ? "-z (temporal TTA mode)" : "-u (UHD mode)");
         return -1;
@@ -946,7 +1027,10 @@ int main(int argc, char** argv) {
     if (video) {
         const char* mode = tta ? "TTA mode (-x)" : tta_temporal ? "temporal TTA mode (-z)" : uhd ? "UHD mode (-u)" : nullptr;
         if (mode) { fprintf(stderr, "4:2:0 YUV frames are served for model family rife-v4.6 in plain mode only, not for %s\n", mode); return 1; }
-        if (keep_alpha || deep) { fprintf(stderr, "%s goes with image files, not with a .y4m video (its depth comes from the file, and it has no alpha)\n", keep_alpha ? "-a" : "-b 10"); return 1; }
+        if (keep_alpha || deep || wide16) {
+            fprintf(stderr, "%s goes with image files, not with a .y4m video (its depth comes from the file, and it has no alpha)\n", wide16 ? "-b 16" : keep_alpha ? "-a" : "-b 10");
+            return 1;
+        }
         if (outputpath != "-" && (is_dir(outputpath) || ext_of(outputpath) != "y4m")) { fprintf(stderr, "a .y4m input goes to a .y4m file or to - (stdout)\n"); return 1; }
         std::string err;
         if (!y4m_open(inputpath, y4m, err)) { fprintf(stderr, "%s: %s\n", inputpath.c_str(), err.c_str()); return 1; }
@@ -980,6 +1064,10 @@ int main(int argc, char** argv) {
     }
     if (!video && format != "png" && format != "ppm" && format != "webp" && format != "jpg") { fprintf(stderr, "invalid format argument\n"); return -1; }
     if (deep && format != "png" && format != "ppm") { fprintf(stderr, "10-bit frames (-b 10) are written as png (16-bit) or ppm (maxval 1023) only, not %s\n", format.c_str()); return -1; }
+    if (wide16 && format != "png" && !(format == "ppm" && !keep_alpha)) {
+        fprintf(stderr, "16-bit frames (-b 16) are written as png%s only, not %s%s\n", keep_alpha ? "" : " or ppm (maxval 65535)", format.c_str(), keep_alpha ? " (-a: it has no 16-bit alpha)" : "");
+        return -1;
+    }
     if (keep_alpha && format != "png" && format != "webp") { fprintf(stderr, "RGBA frames (-a) are written as png or webp only, %s has no alpha\n", format.c_str()); return -1; }
 #ifndef RIFE_HIP_WITH_WEBP
     if (format == "webp") { fprintf(stderr, "this rife-hip was built without libwebp\n"); return -1; }
@@ -989,6 +1077,7 @@ int main(int argc, char** argv) {
     if (model.find("rife-v2") != std::string::npos || model.find("rife-v3") != std::string::npos) rife_v2 = true;
     else if (model.find("rife-v4") != std::string::npos) rife_v4 = true;
     else if (model.find("rife") == std::string::npos) { fprintf(stderr, "unknown model dir type\n"); return -1; }
+    if (wide16 && !rife_v4) { fprintf(stderr, "16-bit frames (-b 16) are served for model family rife-v4.6 only, not for %s\n", model.c_str()); return -1; }
     if (keep_alpha && !rife_v4) { fprintf(stderr, "alpha (-a) is served for model family rife-v4.6 only, not for %s\n", model.c_str()); return -1; }
     if (video && !rife_v4) { fprintf(stderr, "4:2:0 YUV frames are served for model family rife-v4.6 in plain mode only, not for %s\n", model.c_str()); return 1; }
     if (flow_divisor == 2 && !rife_v4) { fprintf(stderr, "flow scale 2 (-d 2) is served for model family rife-v4.6 only, not for %s\n", model.c_str()); return -1; }
@@ -1066,7 +1155,12 @@ int main(int argc, char** argv) {
             if (!f) { fprintf(stderr, "-b 10 is not available: %s\n", rife_hip_last_error()); return -1; }
             RIFE::release(f);
         }
-        if (keep_alpha) {      // likewise: rife-v4 (4.0) shares the directory prefix and is told apart by the engine
+        if (wide16) {      // likewise, through the call the proc threads make: one pixel at timestep 0 reaches the engine's scope check and copies one sample
+            uint16_t one[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+            rife_hip_packed_t d[3];
+            for (int i = 0; i < 3; i++) { d[i].w = d[i].h = 1; d[i].channels = keep_alpha ? 4 : 3; d[i].depth = 16; d[i].data = one[i]; d[i].pitch = 8; }
+            if (r->process_hbd_packed(d[0], d[1], 0.f, d[2]) != 0) { fprintf(stderr, "-b 16 is not available: %s\n", rife_hip_last_error()); return -1; }
+        } else if (keep_alpha) {      // likewise: rife-v4 (4.0) shares the directory prefix and is told apart by the engine
             unsigned char one[4] = {0, 0, 0, 0};
             rife_hip_frame* f = r->upload(ncnn::Mat(1, 1, (void*)one, (size_t)4, 4));
             if (!f) { fprintf(stderr, "-a is not available: %s\n", rife_hip_last_error()); return -1; }
@@ -1103,6 +1197,7 @@ int main(int argc, char** argv) {
                     fr.w = y4m.w; fr.h = y4m.h; fr.yuv = yuv_pixfmt;
                     return y4m.read_frame(atoll(p.c_str() + 6), fr.px);         // "frame <k>"
                 }
+                if (wide16) return decode_image16(p, fr.w, fr.h, keep_alpha ? 4 : 3, fr.px16);
                 fr.rgba = keep_alpha;
                 return deep ? decode_image10(p, fr.w, fr.h, fr.px10) : keep_alpha ? decode_image_rgba(p, fr.w, fr.h, fr.px) : decode_image(p, fr.w, fr.h, fr.px);
             };
@@ -1131,6 +1226,15 @@ int main(int argc, char** argv) {
                 t.out.resize(y4m.frame_bytes);
                 ncnn::Mat out(t.w, t.h, (void*)t.out.data(), (size_t)1, 1);    // process() writes one frame of the resident frames' format behind .data
                 if (!d0 || !d1 || r->process(d0, d1, t.timestep, out) != 0) { fprintf(stderr, "process %s failed: %s\n", t.outpath.c_str(), rife_hip_last_error()); y4m_out.fail(); continue; }
+            }
+            else if (wide16 && (t.timestep == 0.f || t.timestep == 1.f)) t.out16 = (t.timestep == 0.f ? t.fr0 : t.fr1)->px16;      // the input's samples
+            else if (wide16) {      // host frames, never resident: the engine stages them and blends the samples themselves
+                const int nch = keep_alpha ? 4 : 3;
+                t.out16.resize((size_t)t.w * t.h * nch);
+                rife_hip_packed_t d[3];
+                void* const data[3] = {(void*)t.fr0->px16.data(), (void*)t.fr1->px16.data(), (void*)t.out16.data()};
+                for (int i = 0; i < 3; i++) { d[i].w = t.w; d[i].h = t.h; d[i].channels = nch; d[i].depth = 16; d[i].data = data[i]; d[i].pitch = (ptrdiff_t)t.w * nch * 2; }
+                if (r->process_hbd_packed(d[0], d[1], t.timestep, d[2]) != 0) { fprintf(stderr, "process %s failed: %s\n", t.outpath.c_str(), rife_hip_last_error()); continue; }
             }
             else if (deep && (t.timestep == 0.f || t.timestep == 1.f)) t.out10 = (t.timestep == 0.f ? t.fr0 : t.fr1)->px10;
             else if (t.timestep == 0.f || t.timestep == 1.f) t.out = (t.timestep == 0.f ? t.fr0 : t.fr1)->px;      // rife.cpp:2470-2480: an input frame, unchanged
@@ -1161,7 +1265,7 @@ int main(int argc, char** argv) {
                 if (verbose) fprintf(stderr, "%s %s %f -> %s done\n", t.in0path.c_str(), t.in1path.c_str(), t.timestep, t.outpath.c_str());
                 continue;
             }
-            const bool ok = deep ? encode_image10(t.outpath, t.w, t.h, t.out10.data()) : keep_alpha ? encode_image_rgba(t.outpath, t.w, t.h, t.out.data())
+            const bool ok = wide16 ? encode_image16(t.outpath, t.w, t.h, keep_alpha ? 4 : 3, t.out16.data()) : deep ? encode_image10(t.outpath, t.w, t.h, t.out10.data()) : keep_alpha ? encode_image_rgba(t.outpath, t.w, t.h, t.out.data())
                                                                                               : encode_image(t.outpath, t.w, t.h, t.out.data());
             if (!ok) fprintf(stderr, "encode image %s failed\n", t.outpath.c_str());
             else if (verbose) fprintf(stderr, "%s %s %f -> %s done\n", t.in0path.c_str(), t.in1path.c_str(), t.timestep, t.outpath.c_str());

@@ -73,6 +73,9 @@ public:
     // High-bit-depth planes in one call (include/rife_hip.h "high bit depth"): host planes of `depth`-bit samples (10..16) in u16, laid out as RIFE_HIP_PIX_I420P10 /
     // _I422P10 / _I444P10 / _RGBP10 images; the ten-bit proxy the motion is estimated on is made on the device, the blend runs on the planes themselves.
     int process_hbd(const rife_hip_image_t& in0, const rife_hip_image_t& in1, float timestep, const rife_hip_image_t& out, int depth) const;
+    // Packed 16-bit RGB / RGBA frames in one call (include/rife_hip.h "16-bit packed RGB and RGBA"): host frames of 3 or 4 interleaved u16 samples per pixel as
+    // descriptors (an ncnn::Mat with elemsize 6, elempack 3 already means RGB10_U16 and is not overloaded); alpha is warped and blended with the colour.
+    int process_hbd_packed(const rife_hip_packed_t& in0, const rife_hip_packed_t& in1, float timestep, const rife_hip_packed_t& out) const;
 
     // Extension, not in the reference (include/rife_hip.h "strides and planes"): frames as an AVFrame or a VapourSynth frame holds them - a pointer and a
     // pitch in BYTES per plane, any of the _px formats (planar RGB: R, G, B in plane[0..2]; ffmpeg's gbrp: permute them).  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
