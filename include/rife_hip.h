@@ -480,7 +480,7 @@ int rife_hip_process_device_apply_sets(const rife_hip_t* r, const void* d_in0, c
  * other format is named in the message); depth is in 10..16; w * h <= 2^27 and rows * pitch < 2^32 per plane (the rules of the sets calls on the same planes); the
  * three images of a call agree in w, h and pixfmt.  Argument checks come before "no HIP device".  Output planes must not overlap each other or the inputs (documented,
  * not checked); row padding and everything around the output planes is never written.
- * Out of scope: semi-planar or MSB-aligned samples (P012 / P016 / P210); alpha planes and float planes (the sets calls serve them); resident hbd frames (stream mode)
+ * Out of scope: MSB-aligned planar and LSB-aligned semi-planar samples (P010 .. P216 as decoders hold them: "semi-planar high bit depth" below); alpha planes and float planes (the sets calls serve them); resident hbd frames (stream mode)
  * and the batch calls; the command line (its .y4m reader is untouched and keeps refusing C420p12 by name). */
 int rife_hip_hbd_check(const rife_hip_image_t* img, int depth);               /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
 /* planes in host memory */
@@ -529,6 +529,53 @@ int rife_hip_process_hbd_packed(const rife_hip_t* r, const rife_hip_packed_t* in
 /* frames in device memory; stream semantics as for the device _px call (NULL = the engine's own stream, synchronised before returning) */
 int rife_hip_process_device_hbd_packed(const rife_hip_t* r, const rife_hip_packed_t* in0, const rife_hip_packed_t* in1, float timestep, const rife_hip_packed_t* out,
                                        void* hip_stream);
+
+/* ---- semi-planar high bit depth: decoder surfaces - P010 / P012 / P016 and P210 / P212 / P216 - in ONE call (absent in the reference) ---------------------------------
+ * The hbd calls above take three planes with the code in the LOW bits.  A hardware decoder surface, and every ffmpeg hw-frame format above 8 bits, is a Y plane plus ONE
+ * plane of interleaved Cb, Cr pairs with the code in the HIGH bits of each u16.  These calls take such surfaces as they are: the same mechanism - motion estimated on a
+ * ten-bit proxy made on the device, the caller's own samples blended at fp32 - with kernels that read and write interleaved chroma and shift on the way, so nobody
+ * de-interleaves or shifts.  The resident frame format, every trunk kernel and every existing call are untouched; there is no new pixfmt number (rife_hip_hbd_check keeps
+ * refusing RIFE_HIP_PIX_P010, which stays the ten-bit 4:2:0 format of the _px and image calls).  A semi-planar image is a descriptor of its own (rife_hip_semiplanar_t
+ * below).
+ * Definition, operation by operation (tests/semiplanar_ref.py states it in numpy); s = 16 - depth:
+ *   split(img)     the three planes Y >> s (h x w), Cb >> s and Cr >> s (each ch x cw, cw = (w + 1) / 2, ch = (h + 1) / 2 for chroma 1 and h for chroma 2): sample 2 i of
+ *                  a cbcr row is Cb of chroma pixel i, sample 2 i + 1 its Cr.  The low s bits of an input sample are ignored.
+ *   join(planes)   the inverse on codes: Y << s, and Cb << s, Cr << s interleaved; the low s bits are zero.
+ *   result         byte for byte join(planes << s) of the planes rife_hip_process_hbd(r, split(in0), split(in1), timestep, planes, depth) writes (device surfaces:
+ *                  rife_hip_process_device_hbd), the planar images of pixfmt RIFE_HIP_PIX_I420P10 | csp (chroma 1) or RIFE_HIP_PIX_I422P10 | csp (chroma 2).
+ *                  Everything of the hbd definition carries over unchanged: the proxy sample c = min((v + (1 << (depth - 11))) >> (depth - 10), 1023) (depth 10:
+ *                  c = min(v, 1023)) of every code v, the luma set at shift (0, 0) and the chroma set at (-1, -1) or (-1, 0), edge semantics, u16 samples,
+ *                  maxval = (1 << depth) - 1.
+ *   timestep 0, 1  no network pass: (v >> s) << s of every sample of frame 0 / frame 1.
+ * The host call stages both images once (2 bytes per sample, tight) and brings the result back with two 2-D copies; the device call reads and writes the caller's
+ * surfaces in place, stream semantics as for the device _px call.  ONE launch blends the luma plane and the interleaved chroma plane; a chroma tap row is one load of
+ * the four samples Cb, Cr, Cb, Cr of two neighbouring chroma pixels.
+ * Scope: that of the hbd calls - model family rife-v4.6, plain mode, flow scale 1 and 2, precision full and fast.  Any other family or mode (-x, -z, -u) returns
+ * -RIFE_HIP_ENOSYS with a message that names it and the words "high bit depth", before anything is written.
+ * Rules (rife_hip_semiplanar_check states them for one image; both calls repeat them for their three images before they touch anything; a violation is
+ * -RIFE_HIP_EINVAL with the fault named and the prefix "high bit depth: image 0: " / "image 1: " / "image out: "): w, h > 0; chroma is 1 or 2 (3 is refused with a
+ * message that says 4:4:4 semi-planar is not served); csp is one of the three matrices (RIFE_HIP_CSP_FULL is refused by name, as for every 10-bit format); depth is in
+ * 10..16; y and cbcr are non-NULL and aligned to 2; both pitches are positive, multiples of 2 and at most INT32_MAX; pitch_y >= 2 w; pitch_c >= 4 ((w + 1) / 2);
+ * w * h <= 2^27; rows * pitch < 2^32 for each plane; the three images of a call agree in w, h, chroma, csp and depth.  Argument checks come before "no HIP device".
+ * Row padding and everything around the output planes is never written.  The output must not overlap the inputs (documented, not checked).
+ * Out of scope: 4:4:4 semi-planar (P410 / P416); Cr, Cb order (NV21-like); LSB-aligned semi-planar and MSB-aligned planar samples; 8-bit NV12 / NV16 through this
+ * path; a public apply-only call on semi-planar surfaces; resident semi-planar frames (stream mode) and the batch calls; the command line (no container it reads holds
+ * these layouts). */
+typedef struct rife_hip_semiplanar {
+    int w, h;            /* luma size; chroma is (w + 1) / 2 pairs wide, (h + 1) / 2 rows (chroma 1) or h rows (chroma 2) */
+    int chroma;          /* 1: 4:2:0 (P010 / P012 / P016)   2: 4:2:2 (P210 / P212 / P216) */
+    int csp;             /* RIFE_HIP_CSP_BT709 / _BT601 / _BT2020NCL; RIFE_HIP_CSP_FULL is refused, as for every 10-bit format */
+    int depth;           /* 10..16: codes of `depth` bits in the HIGH bits of little-endian u16; low bits ignored on input, written as zero */
+    void* y;    ptrdiff_t pitch_y;   /* BYTES per row */
+    void* cbcr; ptrdiff_t pitch_c;   /* rows of interleaved Cb, Cr pairs */
+} rife_hip_semiplanar_t;
+int rife_hip_semiplanar_check(const rife_hip_semiplanar_t* img);             /* host only, no device needed: 0, or -RIFE_HIP_EINVAL with the fault in the last-error message */
+/* surfaces in host memory */
+int rife_hip_process_hbd_semiplanar(const rife_hip_t* r, const rife_hip_semiplanar_t* in0, const rife_hip_semiplanar_t* in1, float timestep,
+                                    const rife_hip_semiplanar_t* out);
+/* surfaces in device memory; stream semantics as for the device _px call (NULL = the engine's own stream, synchronised before returning) */
+int rife_hip_process_device_hbd_semiplanar(const rife_hip_t* r, const rife_hip_semiplanar_t* in0, const rife_hip_semiplanar_t* in1, float timestep,
+                                           const rife_hip_semiplanar_t* out, void* hip_stream);
 
 const char* rife_hip_last_error(void);
 

@@ -170,6 +170,18 @@ int rife_hip_op_packed_to_rgb10(int gpuid, const rife_hip_packed_t* img, uint32_
  * the vector form ran, 0 for the scalar form.  The rules of the packed calls and of the motion hold (-RIFE_HIP_EINVAL before anything is uploaded). */
 int rife_hip_op_apply_packed(int gpuid, const rife_hip_packed_t* p0, const rife_hip_packed_t* p1, const rife_hip_packed_t* out, const rife_hip_motion_t* host_motion,
                              int force_scalar);
+/* op_sp_to_rgb10: the semi-planar pre-processing kernel alone (csrc/hbd_semiplanar.h; include/rife_hip.h "semi-planar high bit depth"), ONE launch on a semi-planar
+ * image in HOST memory, both planes uploaded as op_apply uploads a plane (pitches and pointer alignment modulo 16 kept, so the form the host picks is the one it would
+ * pick for the caller's surface): out_padded takes the resident form, hp x wp dwords R | G << 10 | B << 20 (hp, wp = h, w rounded up to 32n), padding included.
+ * force_scalar: 0 = the host's choice, 1 = the scalar form.  Returns 1 where the vector form ran, 0 for the scalar form.  The rules of rife_hip_semiplanar_check hold
+ * (-RIFE_HIP_EINVAL before anything is uploaded). */
+int rife_hip_op_sp_to_rgb10(int gpuid, const rife_hip_semiplanar_t* img, uint32_t* out_padded, int force_scalar);
+/* op_apply_sp: the semi-planar blend alone (csrc/hbd_semiplanar.h), ONE launch on three semi-planar images and a motion of mw x mh = the luma size in HOST memory,
+ * uploaded as op_apply uploads them (both output planes come back with every byte the kernel did not write as it went in).  force_scalar: 0 = the host's choice, 1 = the
+ * one-chroma-pixel-per-lane form.  Returns 1 where the vector form ran, 0 for the scalar form.  The rules of the semi-planar calls and of the motion hold
+ * (-RIFE_HIP_EINVAL before anything is uploaded). */
+int rife_hip_op_apply_sp(int gpuid, const rife_hip_semiplanar_t* p0, const rife_hip_semiplanar_t* p1, const rife_hip_semiplanar_t* out, const rife_hip_motion_t* host_motion,
+                         int mw, int mh, int force_scalar);
 
 /* ---- the generic layer-wise graph executor (csrc/graph_exec.h, graph_run.h, graph_kernels.h: the v1 family) on any .param / .bin pair, one graph_run per call.
  * graph_plan needs no device: it parses <base>.param as rife_hip_graph_check does and writes what the loader settled on, one line per layer, tab-separated:

@@ -40,6 +40,7 @@ C_ABI_SYMBOLS = [
     "rife_hip_apply_set_check", "rife_hip_apply_device_motion_sets", "rife_hip_apply_motion_sets", "rife_hip_process_apply_sets", "rife_hip_process_device_apply_sets",
     "rife_hip_hbd_check", "rife_hip_process_hbd", "rife_hip_process_device_hbd",
     "rife_hip_packed_check", "rife_hip_process_hbd_packed", "rife_hip_process_device_hbd_packed",
+    "rife_hip_semiplanar_check", "rife_hip_process_hbd_semiplanar", "rife_hip_process_device_hbd_semiplanar",
 ]
 # include/rife_hip.h RIFE_HIP_PRECISION_*: FULL = two f16 products per weight tap of the residual trunks (fp32-equivalent), FAST = one, the skip at full precision
 PRECISION_FULL, PRECISION_FAST = 0, 1
@@ -70,7 +71,7 @@ TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_h
                     "rife_hip_v4_extract_flow_px", "rife_hip_v4_tap_px", "rife_hip_op_yuv_to_rgb10", "rife_hip_op_rgb10_to_yuv",
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
                     "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply", "rife_hip_op_apply_scaled", "rife_hip_op_hbd_to_rgb10", "rife_hip_op_apply_yuv",
-                    "rife_hip_op_packed_to_rgb10", "rife_hip_op_apply_packed",
+                    "rife_hip_op_packed_to_rgb10", "rife_hip_op_apply_packed", "rife_hip_op_sp_to_rgb10", "rife_hip_op_apply_sp",
                     "rife_hip_graph_plan", "rife_hip_graph_eval"]
 # rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
 TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
@@ -100,6 +101,13 @@ class rife_hip_planes(ctypes.Structure):
 class rife_hip_packed(ctypes.Structure):
     """rife_hip_packed_t of include/rife_hip.h: h rows of w pixels of `channels` (3, 4) interleaved u16 samples of `depth` bits, a pointer and a pitch in BYTES."""
     _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("channels", ctypes.c_int), ("depth", ctypes.c_int), ("data", ctypes.c_void_p), ("pitch", ctypes.c_ssize_t)]
+
+
+class rife_hip_semiplanar(ctypes.Structure):
+    """rife_hip_semiplanar_t of include/rife_hip.h: a Y plane and one plane of interleaved Cb, Cr pairs, codes of `depth` bits in the HIGH bits of u16; chroma 1 = 4:2:0,
+    2 = 4:2:2; a pointer and a pitch in BYTES per plane."""
+    _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("chroma", ctypes.c_int), ("csp", ctypes.c_int), ("depth", ctypes.c_int), ("y", ctypes.c_void_p),
+                ("pitch_y", ctypes.c_ssize_t), ("cbcr", ctypes.c_void_p), ("pitch_c", ctypes.c_ssize_t)]
 
 
 class rife_hip_apply_set(ctypes.Structure):
@@ -196,6 +204,10 @@ def _load(path, with_test_surface):
     L.rife_hip_packed_check.argtypes = [kp]
     L.rife_hip_process_hbd_packed.argtypes = [vp, kp, kp, cf, kp]
     L.rife_hip_process_device_hbd_packed.argtypes = [vp, kp, kp, cf, kp, vp]
+    qp = ctypes.POINTER(rife_hip_semiplanar)
+    L.rife_hip_semiplanar_check.argtypes = [qp]
+    L.rife_hip_process_hbd_semiplanar.argtypes = [vp, qp, qp, cf, qp]
+    L.rife_hip_process_device_hbd_semiplanar.argtypes = [vp, qp, qp, cf, qp, vp]
     if with_test_surface:
         L.rife_hip_op_apply.argtypes = [ci, pp, pp, mp, ci, ci, pp, ci]
         L.rife_hip_op_apply_scaled.argtypes = [ci, sp, mp, ci, ci, ci]
@@ -203,6 +215,8 @@ def _load(path, with_test_surface):
         L.rife_hip_op_apply_yuv.argtypes = [ci, sp, sp, mp, ci, ci]
         L.rife_hip_op_packed_to_rgb10.argtypes = [ci, kp, vp, ci]
         L.rife_hip_op_apply_packed.argtypes = [ci, kp, kp, kp, mp, ci]
+        L.rife_hip_op_sp_to_rgb10.argtypes = [ci, qp, vp, ci]
+        L.rife_hip_op_apply_sp.argtypes = [ci, qp, qp, qp, mp, ci, ci, ci]
         L.rife_hip_op_image_to_resident.argtypes = [ci, ip, ci, vp]
         L.rife_hip_op_resident_to_image.argtypes = [ci, vp, ip, ci]
         L.rife_hip_v4_extract_flow.argtypes = [vp, vp, vp, ci, ci, cf, ci, vp, ci, vp]
@@ -514,6 +528,39 @@ def packed_check(arr, depth):
     rife_hip_packed descriptor (packed_desc()) - whose samples carry `depth` bits, 10..16."""
     d = arr if isinstance(arr, rife_hip_packed) or arr is None else packed_of(arr, depth)
     _check(lib().rife_hip_packed_check(ctypes.byref(d) if d is not None else None), "packed_check")
+
+
+def semiplanar_desc(w, h, chroma, depth, y, pitch_y, cbcr, pitch_c, csp=0):
+    """A rife_hip_semiplanar from raw addresses (ints; device memory for process_device_hbd_semiplanar(), or any of the C calls) and pitches in bytes."""
+    return rife_hip_semiplanar(int(w), int(h), int(chroma), int(csp), int(depth), int(y) or None, int(pitch_y), int(cbcr) or None, int(pitch_c))
+
+
+def semiplanar_of(y, cbcr, depth, chroma, csp=0, what="surface", writable=False):
+    """The descriptor of a semi-planar surface WITHOUT copying it: an (h, w) uint16 luma array and a (ch, 2 * cw) uint16 array of interleaved Cb, Cr pairs (cw = (w + 1)
+    // 2; ch = (h + 1) // 2 for chroma 1, h for chroma 2), `depth`-bit codes in the HIGH bits, rows contiguous - tight arrays, crops or arrays with padded rows.  Raises
+    ValueError."""
+    ok = all(isinstance(a, np.ndarray) and a.dtype == np.uint16 and a.ndim == 2 and a.size > 0 and _rows_strided(a) and (not writable or a.flags.writeable) for a in (y, cbcr))
+    if ok:
+        h, w = y.shape
+        ok = chroma in (1, 2) and cbcr.shape == ((h + 1) // 2 if chroma == 1 else h, 2 * ((w + 1) // 2))
+    if not ok:
+        raise ValueError("%s: a%s uint16 array of shape (h, w) and one of shape (ch, 2 * cw) whose rows are contiguous, chroma 1 (ch = (h + 1) // 2) or 2 (ch = h)"
+                         % (what, " writable" if writable else ""))
+    d = semiplanar_desc(w, h, chroma, depth, y.ctypes.data, _pitch(y), cbcr.ctypes.data, _pitch(cbcr), csp)
+    d._keep = (y, cbcr)      # the descriptor holds raw addresses: the arrays live as long as it does
+    return d
+
+
+def semiplanar_check(y, cbcr=None, w=None, h=None, chroma=1, depth=10, csp=0):
+    """rife_hip_semiplanar_check (host only): raises RifeError with the fault of a semi-planar surface - two uint16 arrays as semiplanar_of() takes them (w, h, when
+    given, must be their size), or a rife_hip_semiplanar descriptor (semiplanar_desc()) as the only argument."""
+    if isinstance(y, rife_hip_semiplanar) or y is None:
+        d = y
+    else:
+        d = semiplanar_of(y, cbcr, depth, chroma, csp)
+        if (w is not None and int(w) != d.w) or (h is not None and int(h) != d.h):
+            raise ValueError("surface: the luma array is not (h, w) = (%s, %s)" % (h, w))
+    _check(lib().rife_hip_semiplanar_check(ctypes.byref(d) if d is not None else None), "semiplanar_check")
 
 
 def _plane_tuple(planes):
@@ -1082,6 +1129,27 @@ class RIFE:
         _check(self._L.rife_hip_process_device_hbd_packed(self._h, ctypes.byref(img0), ctypes.byref(img1), float(timestep), ctypes.byref(out), stream),
                "process_device_hbd_packed", self._L)
 
+    def process_hbd_semiplanar(self, in0, in1, timestep, depth, chroma, csp=0, out=None):
+        """rife_hip_process_hbd_semiplanar (include/rife_hip.h "semi-planar high bit depth"): two decoder surfaces (y, cbcr) - an (h, w) uint16 luma array and a
+        (ch, 2 * cw) uint16 array of interleaved Cb, Cr pairs, `depth`-bit codes (10..16) in the HIGH bits; chroma 1 = 4:2:0 (P010 / P012 / P016), 2 = 4:2:2 (P210 /
+        P212 / P216); views and row-padded arrays are taken without a copy.  The motion is estimated on a ten-bit proxy made on the device and applied to the surfaces
+        themselves.  out: a (y, cbcr) pair of writable arrays to fill, or None; returns the output pair."""
+        for name, s in (("in0", in0), ("in1", in1)) + ((("out", out),) if out is not None else ()):
+            if not isinstance(s, (tuple, list)) or len(s) != 2:
+                raise ValueError("%s: a pair (y, cbcr) of uint16 arrays" % name)
+        a = semiplanar_of(in0[0], in0[1], depth, chroma, csp, "in0"); b = semiplanar_of(in1[0], in1[1], depth, chroma, csp, "in1")
+        if out is None:
+            out = (np.empty(in0[0].shape, np.uint16), np.empty(in0[1].shape, np.uint16))
+        o = semiplanar_of(out[0], out[1], depth, chroma, csp, "out", writable=True)
+        _check(self._L.rife_hip_process_hbd_semiplanar(self._h, ctypes.byref(a), ctypes.byref(b), float(timestep), ctypes.byref(o)), "process_hbd_semiplanar", self._L)
+        return tuple(out)
+
+    def process_device_hbd_semiplanar(self, img0, img1, timestep, out, stream=None):
+        """rife_hip_process_device_hbd_semiplanar: three rife_hip_semiplanar descriptors of DEVICE surfaces (semiplanar_desc(w, h, chroma, depth, y, pitch_y, cbcr,
+        pitch_c, csp)), read and written in place; enqueues on `stream` (hipStream_t as int; None = the engine's own stream, synchronised before returning)."""
+        _check(self._L.rife_hip_process_device_hbd_semiplanar(self._h, ctypes.byref(img0), ctypes.byref(img1), float(timestep), ctypes.byref(out), stream),
+               "process_device_hbd_semiplanar", self._L)
+
     def process_device(self, d_in0, d_in1, w, h, timestep, d_out, stream=None, pixfmt=PIX_RGB8):
         """Device pointers (ints) to tightly packed u8 HWC RGB frames (or frames of `pixfmt`); enqueues on `stream` (hipStream_t as int)."""
         if pixfmt not in _PIX_LAYOUT and pixfmt not in _RGBP_DTYPE:
@@ -1483,6 +1551,29 @@ def op_apply_packed(in0, in1, flow, mask, out, depth, force_scalar=0, gpuid=0):
     rc = testlib().rife_hip_op_apply_packed(int(gpuid), ctypes.byref(d0), ctypes.byref(d1), ctypes.byref(do), ctypes.byref(m), int(force_scalar))
     if rc < 0:
         _check(rc, "op_apply_packed", testlib())
+    return rc == 1
+
+
+def op_sp_to_rgb10(y, cbcr, depth, chroma, csp=0, force_scalar=0, gpuid=0):
+    """rife_hip_op_sp_to_rgb10 (test build): the semi-planar pre-processing kernel alone on a HOST surface (as semiplanar_of takes it, uploaded with its pitches and
+    alignment) -> (the resident form, (hp, wp) uint32; True where the vector form ran).  force_scalar=1: the scalar form."""
+    d = semiplanar_of(y, cbcr, depth, chroma, csp)
+    out = np.empty(((d.h + 31) // 32 * 32, (d.w + 31) // 32 * 32), np.uint32)
+    rc = testlib().rife_hip_op_sp_to_rgb10(int(gpuid), ctypes.byref(d), _p(out), int(force_scalar))
+    if rc < 0:
+        _check(rc, "op_sp_to_rgb10", testlib())
+    return out, rc == 1
+
+
+def op_apply_sp(in0, in1, flow, mask, out, depth, chroma, force_scalar=0, gpuid=0):
+    """rife_hip_op_apply_sp (test build): ONE launch of the semi-planar blend on HOST surfaces (y, cbcr) (as semiplanar_of takes them) and host motion flow (h, w, 4),
+    mask (h, w); the `out` pair is written in place - every byte the kernel did not write keeps its value.  Returns True where the vector form ran."""
+    d0 = semiplanar_of(in0[0], in0[1], depth, chroma, 0, "in0"); d1 = semiplanar_of(in1[0], in1[1], depth, chroma, 0, "in1")
+    do = semiplanar_of(out[0], out[1], depth, chroma, 0, "out", writable=True)
+    m = _motion_in(d0.w, d0.h, flow, mask)
+    rc = testlib().rife_hip_op_apply_sp(int(gpuid), ctypes.byref(d0), ctypes.byref(d1), ctypes.byref(do), ctypes.byref(m), d0.w, d0.h, int(force_scalar))
+    if rc < 0:
+        _check(rc, "op_apply_sp", testlib())
     return rc == 1
 
 

@@ -53,6 +53,8 @@
 #include "apply_yuv.h"
 #include "hbd_packed.h"
 #include "packed_check.h"
+#include "hbd_semiplanar.h"
+#include "semiplanar_check.h"
 #include "elementwise_v2.h"
 #include "stem_fused.h"
 #include "stem_fused_v2.h"
@@ -83,3 +85,4 @@
 #include "engine_apply_sets.h"
 #include "engine_hbd.h"
 #include "engine_hbd_packed.h"
+#include "engine_hbd_semiplanar.h"

@@ -496,6 +496,13 @@ static int run_v4(const rife_hip& E, Ctx& c, const uint8_t* d_in0, const uint8_t
             launch_preproc_packed(st, in.p[0], in.pitch[0], hbd->packed, c.w, c.h, i ? c.img1 : c.img0, c.wp, c.hp, hbd->depth);
             HIPCHK(hipGetLastError());
         }
+    } else if (hbd && hbd->semiplanar) {      // a semi-planar call (engine_hbd_semiplanar.h): one launch per input, a profiler class of its own
+        for (int i = 0; i < 2; i++) {
+            const PlaneSet& in = i ? hbd->in1 : hbd->in0;
+            Timed t(E.prof, "preproc_sp", 0, st);
+            launch_preproc_sp(st, SpPlanes{in.p[0], in.p[1], (unsigned)in.pitch[0], (unsigned)in.pitch[1]}, c.w, c.h, i ? c.img1 : c.img0, c.wp, c.hp, c.pixfmt, hbd->depth);
+            HIPCHK(hipGetLastError());
+        }
     } else {
         Timed t(E.prof, "preproc", 0, st);
         if (hbd) {

@@ -156,6 +156,7 @@ struct HbdIO {
     PlaneSet in0, in1;
     int depth;
     int packed = 0;      // 3 / 4: in0.p[0], in1.p[0] are packed frames of that many interleaved samples per pixel (hbd_packed.h); 0: planes
+    int semiplanar = 0;  // 1: p[0] is the Y plane and p[1] the plane of interleaved Cb, Cr pairs, codes in the HIGH bits (hbd_semiplanar.h); 0: planar, codes in the low bits
 };
 
 }  // namespace rife

@@ -273,6 +273,23 @@ int RIFE::process_hbd_packed(const rife_hip_packed_t& in0, const rife_hip_packed
     return ret;
 }
 
+// weak like the hbd call
+extern "C" int rife_hip_process_hbd_semiplanar(const rife_hip_t* r, const rife_hip_semiplanar_t* in0, const rife_hip_semiplanar_t* in1, float timestep,
+                                               const rife_hip_semiplanar_t* out) __attribute__((weak));
+
+int RIFE::process_hbd_semiplanar(const rife_hip_semiplanar_t& in0, const rife_hip_semiplanar_t& in1, float timestep, const rife_hip_semiplanar_t& out) const
+{
+    if (!engine) return -RIFE_HIP_ENODEV;
+    if (!rife_hip_process_hbd_semiplanar)
+    {
+        fprintf(stderr, "RIFE::process_hbd_semiplanar: this engine has no semi-planar high bit depth call\n");
+        return -RIFE_HIP_ENOSYS;
+    }
+    int ret = rife_hip_process_hbd_semiplanar(engine, &in0, &in1, timestep, &out);
+    if (ret) fprintf(stderr, "RIFE::process_hbd_semiplanar: %s\n", rife_hip_last_error());
+    return ret;
+}
+
 rife_hip_frame* RIFE::upload_yuv(const void* frame, int w, int h, int pixfmt) const
 {
     if (!engine || !frame) return 0;

@@ -76,6 +76,9 @@ public:
     // Packed 16-bit RGB / RGBA frames in one call (include/rife_hip.h "16-bit packed RGB and RGBA"): host frames of 3 or 4 interleaved u16 samples per pixel as
     // descriptors (an ncnn::Mat with elemsize 6, elempack 3 already means RGB10_U16 and is not overloaded); alpha is warped and blended with the colour.
     int process_hbd_packed(const rife_hip_packed_t& in0, const rife_hip_packed_t& in1, float timestep, const rife_hip_packed_t& out) const;
+    // Decoder surfaces in one call (include/rife_hip.h "semi-planar high bit depth"): host surfaces of a Y plane and one plane of interleaved Cb, Cr pairs, codes of
+    // 10..16 bits in the HIGH bits of u16 (P010 / P012 / P016, P210 / P212 / P216), as descriptors; nothing is de-interleaved or shifted on the host.
+    int process_hbd_semiplanar(const rife_hip_semiplanar_t& in0, const rife_hip_semiplanar_t& in1, float timestep, const rife_hip_semiplanar_t& out) const;
 
     // Extension, not in the reference (include/rife_hip.h "strides and planes"): frames as an AVFrame or a VapourSynth frame holds them - a pointer and a
     // pitch in BYTES per plane, any of the _px formats (planar RGB: R, G, B in plane[0..2]; ffmpeg's gbrp: permute them).  Host planes; plain pass-throughs to rife_hip_process_image / rife_hip_frame_upload_image (inline: a
