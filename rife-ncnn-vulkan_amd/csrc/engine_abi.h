@@ -211,7 +211,7 @@ static int process_common(const rife_hip* E, int w, int h, float timestep) {
     if ((long long)((w + pad - 1) / pad * pad) * ((h + pad - 1) / pad * pad) > (1ll << 27))      // element indices are ints and the widest full-resolution tensor has 16 channels; (stem_rs has its own gate, block_on_stem_rs)
         return fail(RIFE_HIP_EINVAL, "frame too large (more than 2^27 padded pixels)");
     (void)timestep;
-    if (E->uhd && !E->v4 && (((w + 31) / 32 * 32 / 2) % 32 || ((h + 31) / 32 * 32 / 2) % 32))
+    if (E->uhd && !E->v4 && ((align_up(w, 32) / 2) % 32 || (align_up(h, 32) / 2) % 32))
         return fail(RIFE_HIP_EINVAL, "UHD mode needs a padded frame whose half size is a multiple of 32 (the reference's graph mis-sizes otherwise)");
     return 0;
 }
@@ -223,11 +223,15 @@ static const char* not_plain_v46(const rife_hip* E) {
     return E->v1 ? "model family rife (v1: rife, rife-HD, rife-UHD, rife-anime)" : (!E->v4 && E->v3) ? "model family rife-v3.x" : !E->v4 ? "model family rife-v2.x"
            : E->v40 ? "model family rife-v4 (4.0)" : E->tta ? "TTA mode (-x)" : E->tta_temporal ? "temporal TTA mode (-z)" : E->uhd ? "UHD mode (-u)" : nullptr;
 }
+// 0, or the one refusal of everything the plain rife-v4.6 schedule alone serves (-RIFE_HIP_ENOSYS): "<subject> served for model family rife-v4.6 in plain mode only, not
+// for <family or mode>"; `subject` ends in its verb ("motion export is", "high bit depth planes are")
+static int plain_v46_only(const rife_hip* E, const std::string& subject) {
+    const char* what = not_plain_v46(E);
+    return what ? fail(RIFE_HIP_ENOSYS, subject + " served for model family rife-v4.6 in plain mode only, not for " + what) : 0;
+}
 static int pixfmt_supported(const rife_hip* E, int pixfmt) {
     if (pixfmt == RIFE_HIP_PIX_RGB8) return 0;
-    const char* what = not_plain_v46(E);
-    if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : pix_yuv(pixfmt) ? "YUV" : pix_rgbp(pixfmt) ? "planar RGB" : "10-bit") + " frames are served for model family rife-v4.6 in plain mode only, not for " + what);
+    return plain_v46_only(E, std::string(pixfmt == RIFE_HIP_PIX_RGBA8 ? "RGBA" : pix_yuv(pixfmt) ? "YUV" : pix_rgbp(pixfmt) ? "planar RGB" : "10-bit") + " frames are");
 }
 // argument checks of the _px entry points that need no engine; then "no HIP device at all" before anything looks at the engine
 // a pixfmt argument = format | colour description (include/rife_hip.h RIFE_HIP_CSP_*): both must be something the library knows
@@ -240,9 +244,7 @@ static int px_precheck(int pixfmt, bool ptrs_ok, int w, int h) {
     if ((rc = pixfmt_check(pixfmt))) return rc;
     if (!ptrs_ok) return fail(RIFE_HIP_EINVAL, "null pointer argument");
     if (w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "bad frame size");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RIFE_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    return 0;
+    return no_hip_device();
 }
 // timestep 0 / 1 at depth 10: the input frame in canonical form (samples clamped to 1023, alpha bits 3) - what a pass over identical frames would write
 // (YUV: the samples' codes - P010 low bits cleared, the planar 10-bit samples clamped to 1023, 8-bit frames unchanged; planar RGB: from10(to10(v)), planar_rgb.h)
@@ -287,11 +289,7 @@ static int copy_frame_device(hipStream_t st, const void* src, void* dst, int w, 
 
 // ---- motion export (include/rife_hip.h rife_hip_motion_t; the rules and their words: csrc/motion_check.h) ----
 // served by the plain rife-v4.6 schedule only; everything else is refused BEFORE anything is written or enqueued
-static int motion_supported(const rife_hip* E) {
-    const char* what = not_plain_v46(E);
-    if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string("motion export is served for model family rife-v4.6 in plain mode only, not for ") + what);
-}
+static int motion_supported(const rife_hip* E) { return plain_v46_only(E, "motion export is"); }
 static int motion_check(const rife_hip_motion_t* m, int w, int h) {
     std::string err;
     return rife_motion::check(m, w, h, err) ? fail(RIFE_HIP_EINVAL, "motion: " + err) : 0;
@@ -426,6 +424,39 @@ static void release_ctx(const rife_hip* E, std::unique_ptr<Ctx>& c) {
     }
 }
 
+extern "C++" {      // templates cannot have C linkage
+// The skeleton of a host call that runs a pass: a pool workspace sized for w x h frames of `pixfmt`, `body(workspace)` enqueues everything on its stream (0 or an rc), the
+// stream is drained whatever the body said (nothing may still run on the caller's buffers when the call returns; a failing drain is reported only where the body did not
+// fail first) and the workspace goes back to the pool.  A workspace whose tensors could not be allocated still returns its lease.
+template <typename F>
+static int with_leased_ctx(const rife_hip* E, int w, int h, int pixfmt, F&& body) {
+    std::unique_ptr<Ctx> c;
+    int rc = lease_ctx(E, c, w, h, 0, pixfmt);
+    if (!rc) rc = body(*c);
+    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
+    if (c) release_ctx(E, c);
+    return rc;
+}
+
+// Upload token (round 6, RIFE_HIP_H2D_TOKEN=0 in the test build: off): one caller uploads at a time and holds the token until its frames have landed.
+// Callers that run in lockstep - all copying over the one PCIe link at once, then all computing - fall out of phase by construction: B's upload rides
+// under A's pass (tools/host_path_bench2.py: 2 caller threads read anything between 272 and 446 frames/s at 4K without it, profiles/r6/ab_h2d_token.txt).
+// `enqueue()` issues the call's host-to-device copies on `st` and returns their hipError_t; with the token the stream is drained before the token is given up
+// (page-locked frames: the copies only enqueue).  0, or -RIFE_HIP_EHIP "H2D: ...".
+template <typename F>
+static int upload_with_token(const rife_hip* E, hipStream_t st, F&& enqueue) {
+    const bool token = process_switches().h2d_token;
+    hipError_t e;
+    {
+        std::unique_lock<std::mutex> g(E->h2d_mu, std::defer_lock);
+        if (token) g.lock();
+        e = enqueue();
+        if (e == hipSuccess && token) e = hipStreamSynchronize(st);
+    }
+    return e == hipSuccess ? 0 : fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
+}
+}  // extern "C++"
+
 // the pass of the engine's model family on workspace c (the caller has made it fit: lease_ctx / ensure_ctx*)
 // mo != null: a motion call (the caller has passed motion_supported: plain rife-v4.6) - the plain pass with the motion target; the graph replay does not apply
 static int run_pass(const rife_hip* E, Ctx& c, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out, const MotionArgs* mo = nullptr) {
@@ -440,27 +471,20 @@ static int run_pass(const rife_hip* E, Ctx& c, const uint8_t* in0, const uint8_t
     return rc;
 }
 
+// both tight frames of a host call into the workspace's staging, enqueued on its stream (inside upload_with_token)
+static hipError_t host_pair_upload(Ctx& c, const void* in0, const void* in1, size_t nbytes) {
+    const hipError_t e = hipMemcpyAsync(c.d_in0, in0, nbytes, hipMemcpyHostToDevice, c.stream);
+    return e != hipSuccess ? e : hipMemcpyAsync(c.d_in1, in1, nbytes, hipMemcpyHostToDevice, c.stream);
+}
 // H2D of both frames, the whole pass and the D2H of the result, all enqueued on the workspace's stream (no host wait)
 // hm != null: + the pass's motion into the workspace's tight buffers and their download into the caller's host buffers
 static int enqueue_host_pair(const rife_hip* E, Ctx& c, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out, const rife_hip_motion_t* hm = nullptr) {
     MotionArgs mo;
     if (hm) { if (int rc = motion_stage(c, *hm, mo)) return rc; }
     const size_t nbytes = frame_bytes(w, h, c.pixfmt);      // c.pixfmt: set by lease_ctx (deep colour: rife-v4.6 plain pass only, pixfmt_supported)
-    hipError_t e;
-    {
-        // Upload token (round 6, RIFE_HIP_H2D_TOKEN=0 in the test build: off): one caller uploads at a time and holds the token until its two frames have landed.
-        // Callers that run in lockstep - all copying over the one PCIe link at once, then all computing - fall out of phase by construction: B's upload rides
-        // under A's pass (tools/host_path_bench2.py: 2 caller threads read anything between 272 and 446 frames/s at 4K without it, profiles/r6/ab_h2d_token.txt).
-        const bool token = process_switches().h2d_token;
-        std::unique_lock<std::mutex> g(E->h2d_mu, std::defer_lock);
-        if (token) g.lock();
-        e = hipMemcpyAsync(c.d_in0, in0, nbytes, hipMemcpyHostToDevice, c.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c.d_in1, in1, nbytes, hipMemcpyHostToDevice, c.stream);
-        if (e == hipSuccess && token) e = hipStreamSynchronize(c.stream);      // page-locked frames: the copies above only enqueue
-    }
-    if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
+    if (int rc = upload_with_token(E, c.stream, [&] { return host_pair_upload(c, in0, in1, nbytes); })) return rc;
     if (int rc = run_pass(E, c, c.d_in0, c.d_in1, w, h, timestep, c.d_out, hm ? &mo : nullptr)) return rc;
-    e = hipMemcpyAsync(out, c.d_out, nbytes, hipMemcpyDeviceToHost, c.stream);
+    const hipError_t e = hipMemcpyAsync(out, c.d_out, nbytes, hipMemcpyDeviceToHost, c.stream);
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
     return hm ? motion_download(c, *hm, mo) : 0;
 }
@@ -480,12 +504,7 @@ static int rife_hip_process_impl(const rife_hip_t* E, const uint8_t* in0, const 
     if (timestep == 0.f) { std::memmove(out, in0, nbytes); return 0; }
     if (timestep == 1.f) { std::memmove(out, in1, nbytes); return 0; }
     if ((rc = check_device(E->gpuid))) return rc;
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, pixfmt);
-    if (!rc) rc = enqueue_host_pair(E, *c, in0, in1, w, h, timestep, out, hm);
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+    return with_leased_ctx(E, w, h, pixfmt, [&](Ctx& c) { return enqueue_host_pair(E, c, in0, in1, w, h, timestep, out, hm); });
 }
 int rife_hip_process(const rife_hip_t* E, const uint8_t* in0, const uint8_t* in1, int w, int h, float timestep, uint8_t* out) {
     return guarded("rife_hip_process", [&] { return rife_hip_process_impl(E, in0, in1, w, h, timestep, out); });
@@ -650,7 +669,7 @@ int rife_hip_process_batch(const rife_hip_t* E, int n, const uint8_t* const* in0
 // ---- stream mode: frames resident in device memory across calls (include/rife_hip.h) ----
 
 // a copy stream borrowed from E->upload_streams (a new one when the pool is empty), given back on every exit path; never the legacy stream
-struct CopyStreamLease {
+extern "C++" struct CopyStreamLease {
     const rife_hip* E;
     hipStream_t st = nullptr;
     hipError_t err = hipSuccess;
@@ -663,11 +682,15 @@ struct CopyStreamLease {
     }
     CopyStreamLease(const CopyStreamLease&) = delete;
     ~CopyStreamLease() { if (st) { std::lock_guard<std::mutex> g(E->mu); E->upload_streams.push_back(st); } }
-    hipError_t copy(void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) const {      // drained: the bytes have landed when it returns
+    template <typename F>
+    hipError_t run(F&& enqueue) const {                                  // `enqueue(stream)`, then drained: the bytes have landed when it returns
         hipError_t e = err;
-        if (e == hipSuccess) e = hipMemcpyAsync(dst, src, nbytes, kind, st);
+        if (e == hipSuccess) e = enqueue(st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         return e;
+    }
+    hipError_t copy(void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) const {
+        return run([&](hipStream_t s) { return hipMemcpyAsync(dst, src, nbytes, kind, s); });
     }
 };
 
@@ -726,23 +749,52 @@ static int rife_hip_process_frames_impl(const rife_hip_t* E, const rife_hip_fram
         if (hm) motion_fill_host(*hm, w, h, 1.f - timestep);
         return 0;
     }
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, pixfmt);
-    if (!rc) {
-        Ctx& C = *c;
+    return with_leased_ctx(E, w, h, pixfmt, [&](Ctx& C) {
+        int rc = 0;
         MotionArgs mo;
         if (hm) rc = motion_stage(C, *hm, mo);
         if (!rc) rc = run_pass(E, C, f0->d, f1->d, w, h, timestep, C.d_out, hm ? &mo : nullptr);
         if (!rc && hipMemcpyAsync(out, C.d_out, nbytes, hipMemcpyDeviceToHost, C.stream) != hipSuccess) rc = fail(RIFE_HIP_EHIP, "D2H failed");
         if (!rc && hm) rc = motion_download(C, *hm, mo);
-    }
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+        return rc;
+    });
 }
 int rife_hip_process_frames(const rife_hip_t* E, const rife_hip_frame_t* f0, const rife_hip_frame_t* f1, float timestep, uint8_t* out) {
     return guarded("rife_hip_process_frames", [&] { return rife_hip_process_frames_impl(E, f0, f1, timestep, out); });
 }
+
+// The workspace of a device call: the one of the caller's stream (NULL: of the engine's own stream, created here - never the legacy stream), found or made under E->mu
+// and held until the call returns.  rc != 0: no workspace, the error is set.
+namespace {      // file-local, like the functions around it: its constructor is no symbol of the library
+struct StreamWorkspace {
+    int rc = 0;
+    Ctx* c = nullptr;
+    std::unique_lock<std::mutex> use;
+    StreamWorkspace(const rife_hip* E, void* hip_stream) {
+        {
+            std::lock_guard<std::mutex> g(E->mu);
+            auto ps = E->part_streams.find(hip_stream);
+            if (ps != E->part_streams.end()) tl_cu_budget = ps->second;      // a stream of rife_hip_stream_create: persistent grids for its part of the chip
+            auto& slot = E->stream_ctx[hip_stream];
+            if (!slot) {
+                slot.reset(new Ctx);
+                if (hip_stream) slot->stream = (hipStream_t)hip_stream;
+                else if (hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking) == hipSuccess) slot->own_stream = true;
+                else {      // no workspace without a stream stays behind: the next call on this key would find it and run on the legacy stream
+                    E->stream_ctx.erase(hip_stream);
+                    rc = fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
+                    return;
+                }
+            }
+            c = slot.get();
+        }
+        // two host threads on the same stream (in particular NULL = the engine's own) share one workspace: the second waits here instead of
+        // racing on its (re)allocation and scratch tensors - work on one stream executes in order anyway
+        use = std::unique_lock<std::mutex>(c->use);
+    }
+    StreamWorkspace(const StreamWorkspace&) = delete;
+};
+}  // namespace
 
 static int rife_hip_process_device_impl(const rife_hip_t* E, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, void* hip_stream,
                                         int pixfmt = RIFE_HIP_PIX_RGB8, const rife_hip_motion_t* dm = nullptr) {
@@ -753,25 +805,9 @@ static int rife_hip_process_device_impl(const rife_hip_t* E, const void* d_in0, 
     if (dm && (rc = motion_supported(E))) return rc;
     const MotionArgs mo = dm ? motion_args(*dm) : MotionArgs();
     if ((rc = check_device(E->gpuid))) return rc;
-    Ctx* c;
-    {
-        std::lock_guard<std::mutex> g(E->mu);
-        auto ps = E->part_streams.find(hip_stream);
-        if (ps != E->part_streams.end()) tl_cu_budget = ps->second;      // a stream of rife_hip_stream_create: persistent grids for its part of the chip
-        auto& slot = E->stream_ctx[hip_stream];
-        if (!slot) {
-            slot.reset(new Ctx);
-            if (hip_stream) slot->stream = (hipStream_t)hip_stream;
-            else {
-                if (hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
-                slot->own_stream = true;
-            }
-        }
-        c = slot.get();
-    }
-    // two host threads on the same stream (in particular NULL = the engine's own) share one workspace: the second waits here instead of
-    // racing on its (re)allocation and scratch tensors - work on one stream executes in order anyway
-    std::lock_guard<std::mutex> use(c->use);
+    StreamWorkspace ws(E, hip_stream);
+    if (ws.rc) return ws.rc;
+    Ctx* const c = ws.c;
     if (timestep == 0.f || timestep == 1.f) {
         if ((rc = copy_frame_device(c->stream, timestep == 0.f ? d_in0 : d_in1, d_out, w, h, pixfmt))) return rc;
         if (dm && (rc = motion_fill_device(c->stream, *dm, w, h, 1.f - timestep))) return rc;
@@ -1551,6 +1587,37 @@ int rife_hip_op_warp(int gpuid, const float* image, const float* flow, int c, in
     return 0;
 }
 
+// ---- scaffolding of the single-kernel ops (here and in the engine_*.h sections that follow) ----
+extern "C++" {      // templates cannot have C linkage
+// a pre-processing kernel alone: a padded frame of wp x hp dwords filled with 0xa5 (the kernel writes the padding too), `launch(frame, wp, hp)`, the frame back to the host
+template <typename F>
+static hipError_t op_padded_rgb10(int w, int h, uint32_t* out_padded, F&& launch) {
+    const int wp = align_up(w, 32), hp = align_up(h, 32);
+    const size_t nout = (size_t)wp * hp * 4;
+    void* d_o = nullptr;
+    hipError_t e = hipMalloc(&d_o, nout);
+    if (e == hipSuccess) e = hipMemset(d_o, 0xa5, nout);
+    if (e == hipSuccess) {
+        launch(static_cast<uint32_t*>(d_o), wp, hp);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(out_padded, d_o, nout, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_o);
+    return e;
+}
+// a blend kernel alone: `launch(stream)` (its rc into lrc) on a non-blocking stream of its own, drained and destroyed before the planes are read back
+template <typename F>
+static hipError_t op_on_own_stream(int& lrc, F&& launch) {
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e != hipSuccess) return e;
+    lrc = launch(st);
+    e = hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    return e;
+}
+}  // extern "C++"
+
 // the YUV kernels alone (yuv.h), in the form the host would pick for a frame at an aligned address: planes -> zero-padded 10:10:10 dwords (hp x wp),
 // A2B10G10R10 (h x w) -> planes
 int rife_hip_op_yuv_to_rgb10(int gpuid, const void* yuv, int w, int h, int pixfmt, uint32_t* out_padded) {
@@ -1558,18 +1625,12 @@ int rife_hip_op_yuv_to_rgb10(int gpuid, const void* yuv, int w, int h, int pixfm
     if ((rc = pixfmt_check(pixfmt))) return rc;
     if (!pix_yuv(pixfmt) || !yuv || !out_padded || w <= 0 || h <= 0) return fail(RIFE_HIP_EINVAL, "op_yuv_to_rgb10: a YUV format, two arrays and a frame size");
     if ((rc = check_device(gpuid))) return rc;
-    const int wp = (w + 31) / 32 * 32, hp = (h + 31) / 32 * 32;
-    const size_t nin = frame_bytes(w, h, pixfmt), nout = (size_t)wp * hp * 4;
-    void *d_i = nullptr, *d_o = nullptr;
+    const size_t nin = frame_bytes(w, h, pixfmt);
+    void* d_i = nullptr;
     hipError_t e = hipMalloc(&d_i, nin);
-    if (e == hipSuccess) e = hipMalloc(&d_o, nout);
     if (e == hipSuccess) e = hipMemcpy(d_i, yuv, nin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_o, 0xa5, nout);                     // the kernel writes the padding too
-    if (e == hipSuccess) {
-        launch_preproc_yuv(0, d_i, w, h, static_cast<uint32_t*>(d_o), wp, hp, pixfmt);
-        e = hipMemcpy(out_padded, d_o, nout, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_i); (void)hipFree(d_o);
+    if (e == hipSuccess) e = op_padded_rgb10(w, h, out_padded, [&](uint32_t* d_o, int wp, int hp) { launch_preproc_yuv(0, d_i, w, h, d_o, wp, hp, pixfmt); });
+    (void)hipFree(d_i);
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_yuv_to_rgb10: ") + hipGetErrorString(e));
     return 0;
 }
@@ -1784,7 +1845,7 @@ int rife_hip_op_tail(int gpuid, int kernel, int pixfmt, int w, int h, const void
     if (pixfmt != RIFE_HIP_PIX_RGB8 && pixfmt != RIFE_HIP_PIX_RGB10_U16 && pixfmt != RIFE_HIP_PIX_A2B10G10R10 && pixfmt != RIFE_HIP_PIX_RGBA8)
         return fail(RIFE_HIP_EINVAL, "op_tail: one of the four packed RGB formats");
     if (w <= 0 || h <= 0 || cus < 0) return fail(RIFE_HIP_EINVAL, "op_tail: a frame size and a CU budget >= 0");
-    const long long wpl = ((long long)w + 31) / 32 * 32, hpl = ((long long)h + 31) / 32 * 32;
+    const long long wpl = align_up((long long)w, 32), hpl = align_up((long long)h, 32);
     if (wpl * hpl >= (1ll << 27)) return fail(RIFE_HIP_EINVAL, "op_tail: frames stay below 2^27 pixels (the kernels address F and the frame with 32-bit byte offsets)");
     const int wp = (int)wpl, hp = (int)hpl, Hq = hp / 4, Wq = wp / 4;
     size_t bytes = 0;
@@ -1871,7 +1932,7 @@ int rife_hip_op_tail_motion(int gpuid, int kernel, int pixfmt, int w, int h, con
     if (pixfmt != RIFE_HIP_PIX_RGB8 && pixfmt != RIFE_HIP_PIX_RGB10_U16 && pixfmt != RIFE_HIP_PIX_A2B10G10R10 && pixfmt != RIFE_HIP_PIX_RGBA8)
         return fail(RIFE_HIP_EINVAL, "op_tail: one of the four packed RGB formats");
     if (w <= 0 || h <= 0 || cus < 0) return fail(RIFE_HIP_EINVAL, "op_tail: a frame size and a CU budget >= 0");
-    const long long wpl = ((long long)w + 31) / 32 * 32, hpl = ((long long)h + 31) / 32 * 32;
+    const long long wpl = align_up((long long)w, 32), hpl = align_up((long long)h, 32);
     if (wpl * hpl >= (1ll << 27)) return fail(RIFE_HIP_EINVAL, "op_tail: frames stay below 2^27 pixels (the kernels address F and the frame with 32-bit byte offsets)");
     const int wp = (int)wpl, hp = (int)hpl, Hq = hp / 4, Wq = wp / 4;
     size_t bytes = 0;

@@ -12,16 +12,10 @@
 static int apply_precheck(const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_planes_t* out, const rife_hip_motion_t* m, bool with_motion, int wp, int hp) {
     std::string err;
     if (rife_apply::check_call(p0, p1, out, m, with_motion, wp, hp, err)) return fail(RIFE_HIP_EINVAL, "apply motion: " + err);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RIFE_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    return 0;
+    return no_hip_device();
 }
 // the combined calls are served where motion export is
-static int apply_supported(const rife_hip* E) {
-    const char* what = not_plain_v46(E);
-    if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string("process with apply motion is served for model family rife-v4.6 in plain mode only, not for ") + what);
-}
+static int apply_supported(const rife_hip* E) { return plain_v46_only(E, "process with apply motion is"); }
 // what the kernel gets, for planes and motion in DEVICE memory
 static ApplyArgs apply_args(const rife_hip_planes_t& p0, const rife_hip_planes_t& p1, const rife_hip_planes_t& out, const uint8_t* flow, size_t flow_pitch,
                             const uint8_t* mask, size_t mask_pitch, int format, int wp, int hp) {
@@ -60,10 +54,10 @@ static void apply_copy_host(const rife_hip_planes_t& src, const rife_hip_planes_
 }
 // tight device copies of the three plane sets of a host call in ONE buffer `base` (3 n planes of h rows of w samples): the descriptors, and the copies in and out
 struct ApplyStage { rife_hip_planes_t d0, d1, dout; };
-static size_t apply_stage_bytes(const rife_hip_planes_t& p) { return 3 * (size_t)p.n * (((size_t)p.h * rife_apply::row_bytes(p.w, p.sample) + 15) / 16 * 16); }
+static size_t apply_stage_bytes(const rife_hip_planes_t& p) { return 3 * (size_t)p.n * align_up((size_t)p.h * rife_apply::row_bytes(p.w, p.sample), 16); }
 static ApplyStage apply_stage(uint8_t* base, const rife_hip_planes_t& p) {
     ApplyStage s{p, p, p};
-    const size_t rb = rife_apply::row_bytes(p.w, p.sample), plane = ((size_t)p.h * rb + 15) / 16 * 16;
+    const size_t rb = rife_apply::row_bytes(p.w, p.sample), plane = align_up((size_t)p.h * rb, 16);
     rife_hip_planes_t* d[3] = {&s.d0, &s.d1, &s.dout};
     for (int i = 0; i < 3; i++)
         for (int k = 0; k < 4; k++) { d[i]->plane[k] = k < p.n ? base + ((size_t)i * p.n + k) * plane : nullptr; d[i]->pitch[k] = k < p.n ? (ptrdiff_t)rb : 0; }
@@ -100,7 +94,7 @@ static int rife_hip_apply_motion_impl(const rife_hip_t* E, const rife_hip_planes
     if ((rc = check_device(E->gpuid))) return rc;
     const int w = p0->w, h = p0->h;
     const size_t frow = rife_motion::flow_row_bytes(w, hm->format), mrow = rife_motion::mask_row_bytes(w, hm->format);
-    const size_t nplanes = apply_stage_bytes(*p0), nflow = ((size_t)h * frow + 15) / 16 * 16, nmask = (size_t)h * mrow;
+    const size_t nplanes = apply_stage_bytes(*p0), nflow = align_up((size_t)h * frow, 16), nmask = (size_t)h * mrow;
     uint8_t* d = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&d), nplanes + nflow + nmask) != hipSuccess) return fail(RIFE_HIP_EHIP, "apply motion: hipMalloc of the staging buffer failed");
     const ApplyStage s = apply_stage(d, *p0);
@@ -231,36 +225,55 @@ struct ApplyMirror {
         return hipSuccess;
     }
 };
+// the three plane sets of one apply set and a host motion in device memory, every buffer an ApplyMirror of its own (pitches and pointer alignment kept): what the blend
+// ops of this and the following sections launch on, and the output planes back
+namespace {
+struct ApplySetMirror {
+    ApplyMirror m0[4], m1[4], mo[4];
+    rife_hip_planes_t d0, d1, dout;
+    hipError_t upload(const rife_hip_planes_t& p0, const rife_hip_planes_t& p1, const rife_hip_planes_t& out) {
+        const size_t rb = rife_apply::row_bytes(p0.w, p0.sample);
+        d0 = p0; d1 = p1; dout = out;
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < p0.n && e == hipSuccess; k++) {
+            e = m0[k].upload(p0.plane[k], (size_t)p0.pitch[k], rb, p0.h); d0.plane[k] = m0[k].dev;
+            if (e == hipSuccess) { e = m1[k].upload(p1.plane[k], (size_t)p1.pitch[k], rb, p0.h); d1.plane[k] = m1[k].dev; }
+            if (e == hipSuccess) { e = mo[k].upload(out.plane[k], (size_t)out.pitch[k], rb, p0.h); dout.plane[k] = mo[k].dev; }
+        }
+        return e;
+    }
+    hipError_t download(const rife_hip_planes_t& out) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < out.n && e == hipSuccess; k++) e = mo[k].download(out.plane[k], (size_t)out.pitch[k], rife_apply::row_bytes(out.w, out.sample));
+        return e;
+    }
+};
+struct MotionMirror {
+    ApplyMirror flow, mask;
+    hipError_t upload(const rife_hip_motion_t& hm, int mw, int mh) {
+        const hipError_t e = flow.upload(hm.flow, hm.flow_pitch, rife_motion::flow_row_bytes(mw, hm.format), mh);
+        return e != hipSuccess ? e : mask.upload(hm.mask, hm.mask_pitch, rife_motion::mask_row_bytes(mw, hm.format), mh);
+    }
+};
+}  // namespace
 int rife_hip_op_apply(int gpuid, const rife_hip_planes_t* p0, const rife_hip_planes_t* p1, const rife_hip_motion_t* hm, int wp, int hp, const rife_hip_planes_t* out, int force_scalar) {
     int rc;
     if ((rc = apply_precheck(p0, p1, out, hm, true, wp, hp))) return rc;
     if (force_scalar < 0 || force_scalar > 1) return fail(RIFE_HIP_EINVAL, "op_apply: force_scalar 0 or 1");
     if ((rc = check_device(gpuid))) return rc;
     return guarded("rife_hip_op_apply", [&] {
-        const int w = p0->w, h = p0->h, n = p0->n;
-        const size_t rb = rife_apply::row_bytes(w, p0->sample);
-        ApplyMirror m0[4], m1[4], mo[4], mf, mm;
-        rife_hip_planes_t d0 = *p0, d1 = *p1, dout = *out;
-        hipError_t e = hipSuccess;
-        for (int k = 0; k < n && e == hipSuccess; k++) {
-            e = m0[k].upload(p0->plane[k], (size_t)p0->pitch[k], rb, h); d0.plane[k] = m0[k].dev;
-            if (e == hipSuccess) { e = m1[k].upload(p1->plane[k], (size_t)p1->pitch[k], rb, h); d1.plane[k] = m1[k].dev; }
-            if (e == hipSuccess) { e = mo[k].upload(out->plane[k], (size_t)out->pitch[k], rb, h); dout.plane[k] = mo[k].dev; }
-        }
-        if (e == hipSuccess) e = mf.upload(hm->flow, hm->flow_pitch, rife_motion::flow_row_bytes(w, hm->format), h);
-        if (e == hipSuccess) e = mm.upload(hm->mask, hm->mask_pitch, rife_motion::mask_row_bytes(w, hm->format), h);
-        if (e == hipSuccess) {
-            hipStream_t st = nullptr;
-            e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-            if (e == hipSuccess) {
-                launch_apply(st, apply_args(d0, d1, dout, mf.dev, hm->flow_pitch, mm.dev, hm->mask_pitch, hm->format, wp, hp), p0->sample, force_scalar == 1);
-                e = hipGetLastError();
-                const hipError_t es = hipStreamSynchronize(st);
-                if (e == hipSuccess) e = es;
-                (void)hipStreamDestroy(st);
-            }
-        }
-        for (int k = 0; k < n && e == hipSuccess; k++) e = mo[k].download(out->plane[k], (size_t)out->pitch[k], rb);
+        ApplySetMirror m;
+        MotionMirror mm;
+        hipError_t e = m.upload(*p0, *p1, *out);
+        if (e == hipSuccess) e = mm.upload(*hm, p0->w, p0->h);
+        int lrc = 0;
+        if (e == hipSuccess) e = op_on_own_stream(lrc, [&](hipStream_t st) {      // a launch error goes before what the drain says, in the op's own words
+            launch_apply(st, apply_args(m.d0, m.d1, m.dout, mm.flow.dev, hm->flow_pitch, mm.mask.dev, hm->mask_pitch, hm->format, wp, hp), p0->sample, force_scalar == 1);
+            const hipError_t le = hipGetLastError();
+            return le == hipSuccess ? 0 : fail(RIFE_HIP_EHIP, std::string("op_apply: ") + hipGetErrorString(le));
+        });
+        if (lrc) return lrc;
+        if (e == hipSuccess) e = m.download(*out);
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_apply: ") + hipGetErrorString(e));
         return 0;
     });

@@ -7,7 +7,8 @@
 //   process_device_apply_sets  the motion pass with F32 motion into the workspace's tight motion buffers (motion_stage), then the launches on the same stream
 //   process_apply_sets         the same from host memory: frames and planes staged through workspace buffers (Ctx::ap_planes, allocated at the first such call)
 // The two combined calls of engine_apply.h (rife_hip_process_apply, rife_hip_process_device_apply) are these two with one set of shift 0, 0: there is ONE copy of the
-// workspace lookup, the upload token, the staging and the timestep 0 / 1 branch.
+// staging and the timestep 0 / 1 branch.  The workspace lookup, the lease, the upload token and the staging buffer are engine_abi.h's and engine_ctx.h's (StreamWorkspace,
+// with_leased_ctx, upload_with_token, apply_staging).
 // The rules and their words: csrc/apply_set_check.h.
 
 // 0, or -RIFE_HIP_EINVAL; then "no HIP device at all" (-RIFE_HIP_ENODEV) before anything looks at the engine
@@ -16,9 +17,7 @@ static int sets_precheck(int nsets, const rife_hip_apply_set_t* sets, const rife
     if (mw <= 0 || mh <= 0) return fail(RIFE_HIP_EINVAL, "apply motion: bad motion size");
     if (rife_apply::check_sets(nsets, sets, mw, mh, err)) return fail(RIFE_HIP_EINVAL, "apply motion: " + err);
     if (with_motion && rife_apply::check_sets_motion(m, mw, mh, err)) return fail(RIFE_HIP_EINVAL, "apply motion: " + err);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RIFE_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    return 0;
+    return no_hip_device();
 }
 // one set with planes and motion in DEVICE memory; `prof`: null in the single-kernel test call
 static int apply_set_launch(Profiler* prof, hipStream_t st, const rife_hip_planes_t& p0, const rife_hip_planes_t& p1, const rife_hip_planes_t& out, const rife_hip_apply_set_t& s,
@@ -97,7 +96,7 @@ static int rife_hip_apply_motion_sets_impl(const rife_hip_t* E, int nsets, const
     if (!E) return fail(RIFE_HIP_EINVAL, "null engine");
     if ((rc = check_device(E->gpuid))) return rc;
     const size_t frow = rife_motion::flow_row_bytes(mw, hm->format), mrow = rife_motion::mask_row_bytes(mw, hm->format);
-    const size_t nplanes = sets_stage_bytes(nsets, sets), nflow = ((size_t)mh * frow + 15) / 16 * 16, nmask = (size_t)mh * mrow;
+    const size_t nplanes = sets_stage_bytes(nsets, sets), nflow = align_up((size_t)mh * frow, 16), nmask = (size_t)mh * mrow;
     uint8_t* d = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&d), nplanes + nflow + nmask) != hipSuccess) return fail(RIFE_HIP_EHIP, "apply motion: hipMalloc of the staging buffer failed");
     ApplyStage sg[4];
@@ -149,37 +148,24 @@ static int rife_hip_process_apply_sets_impl(const rife_hip_t* E, const uint8_t* 
         return 0;
     }
     if ((rc = check_device(E->gpuid))) return rc;
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, pixfmt);
-    if (!rc) {
-        Ctx& C = *c;
+    return with_leased_ctx(E, w, h, pixfmt, [&](Ctx& C) {
         MotionArgs mo;
-        rc = apply_motion_stage(C, mo);
-        const size_t need = sets_stage_bytes(nsets, sets);
-        if (!rc && C.ap_bytes < need) { C.ap_planes = nullptr; C.ap_bytes = 0; if (!(rc = dalloc(C, C.ap_planes, need))) C.ap_bytes = need; }
-        hipError_t e = hipSuccess;
-        if (!rc) {
-            ApplyStage sg[4];
-            sets_stage(C.ap_planes, nsets, sets, sg);
-            {
-                const bool token = process_switches().h2d_token;      // the upload token of enqueue_host_pair
-                std::unique_lock<std::mutex> g(E->h2d_mu, std::defer_lock);
-                if (token) g.lock();
-                e = hipMemcpyAsync(C.d_in0, in0, nbytes, hipMemcpyHostToDevice, C.stream);
-                if (e == hipSuccess) e = hipMemcpyAsync(C.d_in1, in1, nbytes, hipMemcpyHostToDevice, C.stream);
-                if (e == hipSuccess) e = sets_upload(nsets, sets, sg, C.stream);
-                if (e == hipSuccess && token) e = hipStreamSynchronize(C.stream);
-            }
-            if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
-            if (!rc) rc = run_pass(E, C, C.d_in0, C.d_in1, w, h, timestep, C.d_out, &mo);
-            if (!rc) rc = sets_launch_staged(E, C.stream, nsets, sets, sg, mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32, w, h);
-            if (!rc && out && (e = hipMemcpyAsync(out, C.d_out, nbytes, hipMemcpyDeviceToHost, C.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
-            if (!rc && (e = sets_download(nsets, sets, sg, C.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
-        }
-    }
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+        int rc = apply_motion_stage(C, mo);
+        if (!rc) rc = apply_staging(C, sets_stage_bytes(nsets, sets));
+        if (rc) return rc;
+        ApplyStage sg[4];
+        sets_stage(C.ap_planes, nsets, sets, sg);
+        rc = upload_with_token(E, C.stream, [&] {
+            const hipError_t e = host_pair_upload(C, in0, in1, nbytes);
+            return e != hipSuccess ? e : sets_upload(nsets, sets, sg, C.stream);
+        });
+        if (!rc) rc = run_pass(E, C, C.d_in0, C.d_in1, w, h, timestep, C.d_out, &mo);
+        if (!rc) rc = sets_launch_staged(E, C.stream, nsets, sets, sg, mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32, w, h);
+        hipError_t e;
+        if (!rc && out && (e = hipMemcpyAsync(out, C.d_out, nbytes, hipMemcpyDeviceToHost, C.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
+        if (!rc && (e = sets_download(nsets, sets, sg, C.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
+        return rc;
+    });
 }
 
 static int rife_hip_process_device_apply_sets_impl(const rife_hip_t* E, const void* d_in0, const void* d_in1, int w, int h, float timestep, void* d_out, int pixfmt, int nsets,
@@ -189,23 +175,9 @@ static int rife_hip_process_device_apply_sets_impl(const rife_hip_t* E, const vo
     if ((rc = pixfmt_supported(E, pixfmt))) return rc;
     if ((rc = apply_supported(E))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
-    Ctx* c;
-    {      // the stream's workspace, as in rife_hip_process_device_impl
-        std::lock_guard<std::mutex> g(E->mu);
-        auto ps = E->part_streams.find(hip_stream);
-        if (ps != E->part_streams.end()) tl_cu_budget = ps->second;
-        auto& slot = E->stream_ctx[hip_stream];
-        if (!slot) {
-            slot.reset(new Ctx);
-            if (hip_stream) slot->stream = (hipStream_t)hip_stream;
-            else {
-                if (hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
-                slot->own_stream = true;
-            }
-        }
-        c = slot.get();
-    }
-    std::lock_guard<std::mutex> use(c->use);
+    StreamWorkspace ws(E, hip_stream);
+    if (ws.rc) return ws.rc;
+    Ctx* const c = ws.c;
     if (timestep == 0.f || timestep == 1.f) {
         if ((rc = copy_frame_device(c->stream, timestep == 0.f ? d_in0 : d_in1, d_out, w, h, pixfmt))) return rc;
         for (int k = 0; k < nsets; k++)
@@ -260,32 +232,16 @@ int rife_hip_op_apply_scaled(int gpuid, const rife_hip_apply_set_t* set, const r
     if (force_scalar < 0 || force_scalar > 1) return fail(RIFE_HIP_EINVAL, "op_apply_scaled: force_scalar 0 or 1");
     if ((rc = check_device(gpuid))) return rc;
     return guarded("rife_hip_op_apply_scaled", [&] {
-        const rife_hip_planes_t *p0 = set->p0, *p1 = set->p1, *out = set->out;
-        const int h = p0->h, n = p0->n;
-        const size_t rb = rife_apply::row_bytes(p0->w, p0->sample);
-        ApplyMirror m0[4], m1[4], mo[4], mf, mm;
-        rife_hip_planes_t d0 = *p0, d1 = *p1, dout = *out;
-        hipError_t e = hipSuccess;
-        for (int k = 0; k < n && e == hipSuccess; k++) {
-            e = m0[k].upload(p0->plane[k], (size_t)p0->pitch[k], rb, h); d0.plane[k] = m0[k].dev;
-            if (e == hipSuccess) { e = m1[k].upload(p1->plane[k], (size_t)p1->pitch[k], rb, h); d1.plane[k] = m1[k].dev; }
-            if (e == hipSuccess) { e = mo[k].upload(out->plane[k], (size_t)out->pitch[k], rb, h); dout.plane[k] = mo[k].dev; }
-        }
-        if (e == hipSuccess) e = mf.upload(hm->flow, hm->flow_pitch, rife_motion::flow_row_bytes(mw, hm->format), mh);
-        if (e == hipSuccess) e = mm.upload(hm->mask, hm->mask_pitch, rife_motion::mask_row_bytes(mw, hm->format), mh);
+        ApplySetMirror m;
+        MotionMirror mm;
+        hipError_t e = m.upload(*set->p0, *set->p1, *set->out);
+        if (e == hipSuccess) e = mm.upload(*hm, mw, mh);
         int lrc = 0;
-        if (e == hipSuccess) {
-            hipStream_t st = nullptr;
-            e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-            if (e == hipSuccess) {
-                lrc = apply_set_launch(nullptr, st, d0, d1, dout, *set, mf.dev, hm->flow_pitch, mm.dev, hm->mask_pitch, hm->format, mw, mh, force_scalar == 1);
-                const hipError_t es = hipStreamSynchronize(st);
-                e = es;
-                (void)hipStreamDestroy(st);
-            }
-        }
+        if (e == hipSuccess) e = op_on_own_stream(lrc, [&](hipStream_t st) {
+            return apply_set_launch(nullptr, st, m.d0, m.d1, m.dout, *set, mm.flow.dev, hm->flow_pitch, mm.mask.dev, hm->mask_pitch, hm->format, mw, mh, force_scalar == 1);
+        });
         if (lrc) return lrc;
-        for (int k = 0; k < n && e == hipSuccess; k++) e = mo[k].download(out->plane[k], (size_t)out->pitch[k], rb);
+        if (e == hipSuccess) e = m.download(*set->out);
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_apply_scaled: ") + hipGetErrorString(e));
         return 0;
     });

@@ -117,6 +117,19 @@ static int dalloc(Ctx& c, T*& p, size_t n) {
     p = (T*)v;
     return 0;
 }
+// x rounded up to a multiple of a (frame padding to 32n, 16-byte plane and staging offsets) in x's own type
+template <typename T>
+static constexpr T align_up(T x, int a) { return (x + (a - 1)) / a * a; }
+// the tight staging of the host apply / hbd / packed / semi-planar calls, Ctx::ap_planes, grown to `need` bytes by the first call that needs more (the smaller buffer
+// stays among the workspace's allocations until the workspace dies)
+static int apply_staging(Ctx& C, size_t need) {
+    if (C.ap_bytes < need) {
+        C.ap_planes = nullptr; C.ap_bytes = 0;
+        if (int rc = dalloc(C, C.ap_planes, need)) return rc;
+        C.ap_bytes = need;
+    }
+    return 0;
+}
 
 }  // namespace rife
 

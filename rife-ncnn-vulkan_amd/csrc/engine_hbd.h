@@ -6,8 +6,8 @@
 // make_sets), except that the proxy never exists: the pre-processing kernels of hbd.h reduce the caller's samples on their way into the resident frames, the pass
 // leaves its ten-bit frame in the workspace, and the apply launches of engine_apply_sets.h blend the same planes - for a subsampled image ONE launch of k_apply_yuv
 // (apply_yuv.h) where its stores are aligned, with the same bytes (hbd_apply_launch).
-//   process_device_hbd   the stream's workspace; pre-processing, pass and apply launches on the caller's device planes, in place
-//   process_hbd          host planes staged ONCE, 2 bytes per sample, in the workspace's apply staging (Ctx::ap_planes): the staged planes feed the pre-processing and
+//   process_device_hbd   the stream's workspace (StreamWorkspace); pre-processing, pass and apply launches on the caller's device planes, in place
+//   process_hbd          a pool workspace (with_leased_ctx); host planes staged ONCE, 2 bytes per sample, in its apply staging (Ctx::ap_planes, apply_staging): the staged planes feed the pre-processing and
 //                        the blend; the output planes come back with 2-D copies
 // The rules and their words: csrc/hbd_check.h.
 
@@ -15,16 +15,10 @@
 static int hbd_precheck(const rife_hip_image_t* in0, const rife_hip_image_t* in1, const rife_hip_image_t* out, int depth) {
     std::string err;
     if (rife_hbd::check_call(in0, in1, out, depth, err)) return fail(RIFE_HIP_EINVAL, "high bit depth: " + err);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RIFE_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    return 0;
+    return no_hip_device();
 }
 // served where the combined apply calls are
-static int hbd_supported(const rife_hip* E) {
-    const char* what = not_plain_v46(E);
-    if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string("high bit depth planes are served for model family rife-v4.6 in plain mode only, not for ") + what);
-}
+static int hbd_supported(const rife_hip* E) { return plain_v46_only(E, "high bit depth planes are"); }
 // the sets of the definition, checked by the rules of the sets calls (nothing hbd_check let through fails them; a fault here is reported, not assumed away)
 static int hbd_sets(rife_hbd::Sets& S, const rife_hip_image_t& in0, const rife_hip_image_t& in1, const rife_hip_image_t& out, int depth) {
     rife_hbd::make_sets(S, in0, in1, out, depth);
@@ -83,36 +77,22 @@ static int rife_hip_process_hbd_impl(const rife_hip_t* E, const rife_hip_image_t
         return 0;
     }
     if ((rc = check_device(E->gpuid))) return rc;
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, pixfmt);
-    if (!rc) {
-        Ctx& C = *c;
+    return with_leased_ctx(E, w, h, pixfmt, [&](Ctx& C) {
         MotionArgs mo;
-        rc = apply_motion_stage(C, mo);
-        const size_t need = sets_stage_bytes(S.n, S.sets);
-        if (!rc && C.ap_bytes < need) { C.ap_planes = nullptr; C.ap_bytes = 0; if (!(rc = dalloc(C, C.ap_planes, need))) C.ap_bytes = need; }
-        hipError_t e = hipSuccess;
-        if (!rc) {
-            ApplyStage sg[2] = {};
-            sets_stage(C.ap_planes, S.n, S.sets, sg);
-            {
-                const bool token = process_switches().h2d_token;      // the upload token of enqueue_host_pair
-                std::unique_lock<std::mutex> g(E->h2d_mu, std::defer_lock);
-                if (token) g.lock();
-                e = sets_upload(S.n, S.sets, sg, C.stream);
-                if (e == hipSuccess && token) e = hipStreamSynchronize(C.stream);
-            }
-            if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
-            const HbdIO io{hbd_plane_set(S.n, sg[0].d0, S.n == 2 ? &sg[1].d0 : nullptr), hbd_plane_set(S.n, sg[0].d1, S.n == 2 ? &sg[1].d1 : nullptr), depth};
-            if (!rc) rc = run_v4(*E, C, nullptr, nullptr, timestep, nullptr, nullptr, nullptr, &mo, &io);
-            const HbdDev dv[2] = {{&sg[0].d0, &sg[0].d1, &sg[0].dout}, {&sg[1].d0, &sg[1].d1, &sg[1].dout}};      // [1]: addresses only, read when S.n == 2
-            if (!rc) rc = hbd_apply_launch(&E->prof, C.stream, S.n, S.sets, dv, mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32, w, h, read_switches().apply_yuv);
-            if (!rc && (e = sets_download(S.n, S.sets, sg, C.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
-        }
-    }
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+        int rc = apply_motion_stage(C, mo);
+        if (!rc) rc = apply_staging(C, sets_stage_bytes(S.n, S.sets));
+        if (rc) return rc;
+        ApplyStage sg[2] = {};
+        sets_stage(C.ap_planes, S.n, S.sets, sg);
+        rc = upload_with_token(E, C.stream, [&] { return sets_upload(S.n, S.sets, sg, C.stream); });
+        const HbdIO io{hbd_plane_set(S.n, sg[0].d0, S.n == 2 ? &sg[1].d0 : nullptr), hbd_plane_set(S.n, sg[0].d1, S.n == 2 ? &sg[1].d1 : nullptr), depth};
+        if (!rc) rc = run_v4(*E, C, nullptr, nullptr, timestep, nullptr, nullptr, nullptr, &mo, &io);
+        const HbdDev dv[2] = {{&sg[0].d0, &sg[0].d1, &sg[0].dout}, {&sg[1].d0, &sg[1].d1, &sg[1].dout}};      // [1]: addresses only, read when S.n == 2
+        if (!rc) rc = hbd_apply_launch(&E->prof, C.stream, S.n, S.sets, dv, mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32, w, h, read_switches().apply_yuv);
+        hipError_t e;
+        if (!rc && (e = sets_download(S.n, S.sets, sg, C.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
+        return rc;
+    });
 }
 
 static int rife_hip_process_device_hbd_impl(const rife_hip_t* E, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out, int depth,
@@ -124,23 +104,9 @@ static int rife_hip_process_device_hbd_impl(const rife_hip_t* E, const rife_hip_
     rife_hbd::Sets S;
     if ((rc = hbd_sets(S, *in0, *in1, *out, depth))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
-    Ctx* c;
-    {      // the stream's workspace, as in rife_hip_process_device_impl
-        std::lock_guard<std::mutex> g(E->mu);
-        auto ps = E->part_streams.find(hip_stream);
-        if (ps != E->part_streams.end()) tl_cu_budget = ps->second;
-        auto& slot = E->stream_ctx[hip_stream];
-        if (!slot) {
-            slot.reset(new Ctx);
-            if (hip_stream) slot->stream = (hipStream_t)hip_stream;
-            else {
-                if (hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
-                slot->own_stream = true;
-            }
-        }
-        c = slot.get();
-    }
-    std::lock_guard<std::mutex> use(c->use);
+    StreamWorkspace ws(E, hip_stream);
+    if (ws.rc) return ws.rc;
+    Ctx* const c = ws.c;
     if (timestep == 0.f || timestep == 1.f) {
         for (int k = 0; k < S.n; k++)
             if ((rc = apply_copy_device(c->stream, timestep == 0.f ? *S.sets[k].p0 : *S.sets[k].p1, *S.sets[k].out))) return rc;
@@ -183,19 +149,11 @@ int rife_hip_op_hbd_to_rgb10(int gpuid, const rife_hip_image_t* img, int depth, 
     if (!out_padded || force_scalar < 0 || force_scalar > 1) return fail(RIFE_HIP_EINVAL, "op_hbd_to_rgb10: an output array and force_scalar 0 or 1");
     if ((rc = check_device(gpuid))) return rc;
     return guarded("rife_hip_op_hbd_to_rgb10", [&] {
-        const int w = img->w, h = img->h, wp = (w + 31) / 32 * 32, hp = (h + 31) / 32 * 32;
-        const size_t nout = (size_t)wp * hp * 4;
         ImageMirror m;
-        void* d_o = nullptr;
         hipError_t e = m.upload(*img);
-        if (e == hipSuccess) e = hipMalloc(&d_o, nout);
-        if (e == hipSuccess) e = hipMemset(d_o, 0xa5, nout);                 // the kernel writes the padding too
-        if (e == hipSuccess) {
-            launch_preproc_hbd(0, plane_set(m.dev), w, h, static_cast<uint32_t*>(d_o), wp, hp, img->pixfmt, depth, force_scalar == 1);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpy(out_padded, d_o, nout, hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(d_o);
+        if (e == hipSuccess) e = op_padded_rgb10(img->w, img->h, out_padded, [&](uint32_t* d_o, int wp, int hp) {
+            launch_preproc_hbd(0, plane_set(m.dev), img->w, img->h, d_o, wp, hp, img->pixfmt, depth, force_scalar == 1);
+        });
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_hbd_to_rgb10: ") + hipGetErrorString(e));
         return 0;
     });
@@ -210,37 +168,19 @@ int rife_hip_op_apply_yuv(int gpuid, const rife_hip_apply_set_t* luma_set, const
         return fail(RIFE_HIP_EINVAL, "op_apply_yuv: a luma set of shift (0, 0) and a chroma set of shift (-1, -1) or (-1, 0)");
     if ((rc = check_device(gpuid))) return rc;
     return guarded("rife_hip_op_apply_yuv", [&] {
-        ApplyMirror m0[2][4], m1[2][4], mo[2][4], mf, mm;
-        rife_hip_planes_t d0[2], d1[2], dout[2];
+        ApplySetMirror m[2];
+        MotionMirror mm;
         hipError_t e = hipSuccess;
-        for (int s = 0; s < 2; s++) {
-            const rife_hip_planes_t *p0 = two[s].p0, *p1 = two[s].p1, *out = two[s].out;
-            const size_t rb = rife_apply::row_bytes(p0->w, p0->sample);
-            d0[s] = *p0; d1[s] = *p1; dout[s] = *out;
-            for (int k = 0; k < p0->n && e == hipSuccess; k++) {
-                e = m0[s][k].upload(p0->plane[k], (size_t)p0->pitch[k], rb, p0->h); d0[s].plane[k] = m0[s][k].dev;
-                if (e == hipSuccess) { e = m1[s][k].upload(p1->plane[k], (size_t)p1->pitch[k], rb, p0->h); d1[s].plane[k] = m1[s][k].dev; }
-                if (e == hipSuccess) { e = mo[s][k].upload(out->plane[k], (size_t)out->pitch[k], rb, p0->h); dout[s].plane[k] = mo[s][k].dev; }
-            }
-        }
-        if (e == hipSuccess) e = mf.upload(hm->flow, hm->flow_pitch, rife_motion::flow_row_bytes(mw, hm->format), mh);
-        if (e == hipSuccess) e = mm.upload(hm->mask, hm->mask_pitch, rife_motion::mask_row_bytes(mw, hm->format), mh);
+        for (int s = 0; s < 2 && e == hipSuccess; s++) e = m[s].upload(*two[s].p0, *two[s].p1, *two[s].out);
+        if (e == hipSuccess) e = mm.upload(*hm, mw, mh);
         int lrc = 0;
         bool fused = false;
-        if (e == hipSuccess) {
-            hipStream_t st = nullptr;
-            e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-            if (e == hipSuccess) {
-                const HbdDev dv[2] = {{&d0[0], &d1[0], &dout[0]}, {&d0[1], &d1[1], &dout[1]}};
-                lrc = hbd_apply_launch(nullptr, st, 2, two, dv, mf.dev, hm->flow_pitch, mm.dev, hm->mask_pitch, hm->format, mw, mh, read_switches().apply_yuv, &fused);
-                e = hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-        }
+        if (e == hipSuccess) e = op_on_own_stream(lrc, [&](hipStream_t st) {
+            const HbdDev dv[2] = {{&m[0].d0, &m[0].d1, &m[0].dout}, {&m[1].d0, &m[1].d1, &m[1].dout}};
+            return hbd_apply_launch(nullptr, st, 2, two, dv, mm.flow.dev, hm->flow_pitch, mm.mask.dev, hm->mask_pitch, hm->format, mw, mh, read_switches().apply_yuv, &fused);
+        });
         if (lrc) return lrc;
-        for (int s = 0; s < 2; s++)
-            for (int k = 0; k < two[s].out->n && e == hipSuccess; k++)
-                e = mo[s][k].download(two[s].out->plane[k], (size_t)two[s].out->pitch[k], rife_apply::row_bytes(two[s].out->w, two[s].out->sample));
+        for (int s = 0; s < 2 && e == hipSuccess; s++) e = m[s].download(*two[s].out);
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_apply_yuv: ") + hipGetErrorString(e));
         return fused ? 1 : 0;
     });

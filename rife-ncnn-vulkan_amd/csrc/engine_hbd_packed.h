@@ -4,8 +4,8 @@
 // A packed call IS the combined sets call on the RGBP10 proxy of the colour channels with ONE set of `channels` planes at shift (0, 0), edge semantics - except that
 // neither the proxy nor the planes exist: k_preproc_packed (hbd_packed.h) reduces the caller's interleaved samples on their way into the resident frames, the pass
 // leaves its motion in the workspace, and ONE launch of k_apply_packed blends all channels of the packed frames.
-//   process_device_hbd_packed   the stream's workspace; pre-processing, pass and blend on the caller's device frames, in place
-//   process_hbd_packed          host frames staged ONCE, 2 bytes per sample, tight, in the workspace's apply staging (Ctx::ap_planes); the result comes back with one
+//   process_device_hbd_packed   the stream's workspace (StreamWorkspace); pre-processing, pass and blend on the caller's device frames, in place
+//   process_hbd_packed          a pool workspace (with_leased_ctx); host frames staged ONCE, 2 bytes per sample, tight, in its apply staging (apply_staging); the result comes back with one
 //                               2-D copy
 // The rules and their words: csrc/packed_check.h.
 
@@ -13,15 +13,9 @@
 static int packed_precheck(const rife_hip_packed_t* in0, const rife_hip_packed_t* in1, const rife_hip_packed_t* out) {
     std::string err;
     if (rife_packed::check_call(in0, in1, out, err)) return fail(RIFE_HIP_EINVAL, "high bit depth: " + err);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RIFE_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    return 0;
+    return no_hip_device();
 }
-static int packed_supported(const rife_hip* E) {
-    const char* what = not_plain_v46(E);
-    if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string("high bit depth packed frames are served for model family rife-v4.6 in plain mode only, not for ") + what);
-}
+static int packed_supported(const rife_hip* E) { return plain_v46_only(E, "high bit depth packed frames are"); }
 // what k_apply_packed gets, for frames and motion in DEVICE memory: plane 0 of ApplyArgs holds the packed frames, the extent is the frame (edge semantics)
 static ApplyArgs packed_args(const rife_hip_packed_t& p0, const rife_hip_packed_t& p1, const rife_hip_packed_t& out, const uint8_t* flow, size_t flow_pitch,
                              const uint8_t* mask, size_t mask_pitch, int format) {
@@ -61,38 +55,27 @@ static int rife_hip_process_hbd_packed_impl(const rife_hip_t* E, const rife_hip_
         return 0;
     }
     if ((rc = check_device(E->gpuid))) return rc;
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, RIFE_HIP_PIX_RGBP10);
-    if (!rc) {
-        Ctx& C = *c;
+    return with_leased_ctx(E, w, h, RIFE_HIP_PIX_RGBP10, [&](Ctx& C) {
         MotionArgs mo;
-        rc = apply_motion_stage(C, mo);
-        const size_t rb = (size_t)w * in0->channels * 2, frame = ((size_t)h * rb + 15) / 16 * 16, need = 3 * frame;
-        if (!rc && C.ap_bytes < need) { C.ap_planes = nullptr; C.ap_bytes = 0; if (!(rc = dalloc(C, C.ap_planes, need))) C.ap_bytes = need; }
-        hipError_t e = hipSuccess;
-        if (!rc) {
-            rife_hip_packed_t d0 = *in0, d1 = *in1, dout = *out;          // the tight device copies
-            d0.data = C.ap_planes; d1.data = C.ap_planes + frame; dout.data = C.ap_planes + 2 * frame;
-            d0.pitch = d1.pitch = dout.pitch = (ptrdiff_t)rb;
-            {
-                const bool token = process_switches().h2d_token;      // the upload token of enqueue_host_pair
-                std::unique_lock<std::mutex> g(E->h2d_mu, std::defer_lock);
-                if (token) g.lock();
-                e = hipMemcpy2DAsync(d0.data, rb, in0->data, (size_t)in0->pitch, rb, (size_t)h, hipMemcpyHostToDevice, C.stream);
-                if (e == hipSuccess) e = hipMemcpy2DAsync(d1.data, rb, in1->data, (size_t)in1->pitch, rb, (size_t)h, hipMemcpyHostToDevice, C.stream);
-                if (e == hipSuccess && token) e = hipStreamSynchronize(C.stream);
-            }
-            if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
-            const HbdIO io = packed_io(d0, d1);
-            if (!rc) rc = run_v4(*E, C, nullptr, nullptr, timestep, nullptr, nullptr, nullptr, &mo, &io);
-            if (!rc) rc = packed_apply_launch(&E->prof, C.stream, packed_args(d0, d1, dout, mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32), in0->channels);
-            if (!rc && (e = hipMemcpy2DAsync(out->data, (size_t)out->pitch, dout.data, rb, rb, (size_t)h, hipMemcpyDeviceToHost, C.stream)) != hipSuccess)
-                rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
-        }
-    }
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+        int rc = apply_motion_stage(C, mo);
+        const size_t rb = (size_t)w * in0->channels * 2, frame = align_up((size_t)h * rb, 16);
+        if (!rc) rc = apply_staging(C, 3 * frame);
+        if (rc) return rc;
+        rife_hip_packed_t d0 = *in0, d1 = *in1, dout = *out;              // the tight device copies
+        d0.data = C.ap_planes; d1.data = C.ap_planes + frame; dout.data = C.ap_planes + 2 * frame;
+        d0.pitch = d1.pitch = dout.pitch = (ptrdiff_t)rb;
+        rc = upload_with_token(E, C.stream, [&] {
+            const hipError_t e = hipMemcpy2DAsync(d0.data, rb, in0->data, (size_t)in0->pitch, rb, (size_t)h, hipMemcpyHostToDevice, C.stream);
+            return e != hipSuccess ? e : hipMemcpy2DAsync(d1.data, rb, in1->data, (size_t)in1->pitch, rb, (size_t)h, hipMemcpyHostToDevice, C.stream);
+        });
+        const HbdIO io = packed_io(d0, d1);
+        if (!rc) rc = run_v4(*E, C, nullptr, nullptr, timestep, nullptr, nullptr, nullptr, &mo, &io);
+        if (!rc) rc = packed_apply_launch(&E->prof, C.stream, packed_args(d0, d1, dout, mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32), in0->channels);
+        hipError_t e;
+        if (!rc && (e = hipMemcpy2DAsync(out->data, (size_t)out->pitch, dout.data, rb, rb, (size_t)h, hipMemcpyDeviceToHost, C.stream)) != hipSuccess)
+            rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
+        return rc;
+    });
 }
 
 static int rife_hip_process_device_hbd_packed_impl(const rife_hip_t* E, const rife_hip_packed_t* in0, const rife_hip_packed_t* in1, float timestep, const rife_hip_packed_t* out,
@@ -102,23 +85,9 @@ static int rife_hip_process_device_hbd_packed_impl(const rife_hip_t* E, const ri
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if ((rc = packed_supported(E))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
-    Ctx* c;
-    {      // the stream's workspace, as in rife_hip_process_device_impl
-        std::lock_guard<std::mutex> g(E->mu);
-        auto ps = E->part_streams.find(hip_stream);
-        if (ps != E->part_streams.end()) tl_cu_budget = ps->second;
-        auto& slot = E->stream_ctx[hip_stream];
-        if (!slot) {
-            slot.reset(new Ctx);
-            if (hip_stream) slot->stream = (hipStream_t)hip_stream;
-            else {
-                if (hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
-                slot->own_stream = true;
-            }
-        }
-        c = slot.get();
-    }
-    std::lock_guard<std::mutex> use(c->use);
+    StreamWorkspace ws(E, hip_stream);
+    if (ws.rc) return ws.rc;
+    Ctx* const c = ws.c;
     if (timestep == 0.f || timestep == 1.f) {
         if ((rc = apply_copy_device(c->stream, rife_packed::as_plane(timestep == 0.f ? *in0 : *in1), rife_packed::as_plane(*out)))) return rc;
     } else {
@@ -159,20 +128,13 @@ int rife_hip_op_packed_to_rgb10(int gpuid, const rife_hip_packed_t* img, uint32_
     if (!out_padded || force_scalar < 0 || force_scalar > 1) return fail(RIFE_HIP_EINVAL, "op_packed_to_rgb10: an output array and force_scalar 0 or 1");
     if ((rc = check_device(gpuid))) return rc;
     return guarded("rife_hip_op_packed_to_rgb10", [&] {
-        const int w = img->w, h = img->h, wp = (w + 31) / 32 * 32, hp = (h + 31) / 32 * 32;
-        const size_t nout = (size_t)wp * hp * 4;
+        const int w = img->w, h = img->h;
         ApplyMirror m;
-        void* d_o = nullptr;
         bool vec = false;
         hipError_t e = m.upload(img->data, (size_t)img->pitch, (size_t)w * img->channels * 2, h);
-        if (e == hipSuccess) e = hipMalloc(&d_o, nout);
-        if (e == hipSuccess) e = hipMemset(d_o, 0xa5, nout);                 // the kernel writes the padding too
-        if (e == hipSuccess) {
-            vec = launch_preproc_packed(0, m.dev, (size_t)img->pitch, img->channels, w, h, static_cast<uint32_t*>(d_o), wp, hp, img->depth, force_scalar == 1);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpy(out_padded, d_o, nout, hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(d_o);
+        if (e == hipSuccess) e = op_padded_rgb10(w, h, out_padded, [&](uint32_t* d_o, int wp, int hp) {
+            vec = launch_preproc_packed(0, m.dev, (size_t)img->pitch, img->channels, w, h, d_o, wp, hp, img->depth, force_scalar == 1);
+        });
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_packed_to_rgb10: ") + hipGetErrorString(e));
         return vec ? 1 : 0;
     });
@@ -188,24 +150,18 @@ int rife_hip_op_apply_packed(int gpuid, const rife_hip_packed_t* p0, const rife_
     return guarded("rife_hip_op_apply_packed", [&] {
         const int w = p0->w, h = p0->h;
         const size_t rb = (size_t)w * p0->channels * 2;
-        ApplyMirror m0, m1, mo, mf, mm;
+        ApplyMirror m0, m1, mo;
+        MotionMirror mm;
         rife_hip_packed_t d0 = *p0, d1 = *p1, dout = *out;
         hipError_t e = m0.upload(p0->data, (size_t)p0->pitch, rb, h); d0.data = m0.dev;
         if (e == hipSuccess) { e = m1.upload(p1->data, (size_t)p1->pitch, rb, h); d1.data = m1.dev; }
         if (e == hipSuccess) { e = mo.upload(out->data, (size_t)out->pitch, rb, h); dout.data = mo.dev; }
-        if (e == hipSuccess) e = mf.upload(hm->flow, hm->flow_pitch, rife_motion::flow_row_bytes(w, hm->format), h);
-        if (e == hipSuccess) e = mm.upload(hm->mask, hm->mask_pitch, rife_motion::mask_row_bytes(w, hm->format), h);
+        if (e == hipSuccess) e = mm.upload(*hm, w, h);
         int lrc = 0;
         bool vec = false;
-        if (e == hipSuccess) {
-            hipStream_t st = nullptr;
-            e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-            if (e == hipSuccess) {
-                lrc = packed_apply_launch(nullptr, st, packed_args(d0, d1, dout, mf.dev, hm->flow_pitch, mm.dev, hm->mask_pitch, hm->format), p0->channels, force_scalar == 1, &vec);
-                e = hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-        }
+        if (e == hipSuccess) e = op_on_own_stream(lrc, [&](hipStream_t st) {
+            return packed_apply_launch(nullptr, st, packed_args(d0, d1, dout, mm.flow.dev, hm->flow_pitch, mm.mask.dev, hm->mask_pitch, hm->format), p0->channels, force_scalar == 1, &vec);
+        });
         if (lrc) return lrc;
         if (e == hipSuccess) e = mo.download(out->data, (size_t)out->pitch, rb);
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_apply_packed: ") + hipGetErrorString(e));

@@ -4,8 +4,8 @@
 // A semi-planar call IS the hbd call on split(img) - the planes Y >> s, Cb >> s, Cr >> s of layout I420P10 | csp / I422P10 | csp - joined back and shifted left,
 // except that the planes never exist: k_preproc_sp (hbd_semiplanar.h) shifts and reduces the caller's samples on their way into the resident frames, the pass leaves its
 // motion in the workspace, and ONE launch of k_apply_sp blends the luma plane and the interleaved chroma plane.
-//   process_device_hbd_semiplanar   the stream's workspace; pre-processing, pass and blend on the caller's device planes, in place
-//   process_hbd_semiplanar          host planes staged ONCE, 2 bytes per sample, tight, in the workspace's apply staging (Ctx::ap_planes); the result comes back with
+//   process_device_hbd_semiplanar   the stream's workspace (StreamWorkspace); pre-processing, pass and blend on the caller's device planes, in place
+//   process_hbd_semiplanar          a pool workspace (with_leased_ctx); host planes staged ONCE, 2 bytes per sample, tight, in its apply staging (apply_staging); the result comes back with
 //                                   two 2-D copies
 // The rules and their words: csrc/semiplanar_check.h.
 
@@ -13,15 +13,9 @@
 static int sp_precheck(const rife_hip_semiplanar_t* in0, const rife_hip_semiplanar_t* in1, const rife_hip_semiplanar_t* out) {
     std::string err;
     if (rife_sp::check_call(in0, in1, out, err)) return fail(RIFE_HIP_EINVAL, "high bit depth: " + err);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RIFE_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    return 0;
+    return no_hip_device();
 }
-static int sp_supported(const rife_hip* E) {
-    const char* what = not_plain_v46(E);
-    if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string("high bit depth semi-planar surfaces are served for model family rife-v4.6 in plain mode only, not for ") + what);
-}
+static int sp_supported(const rife_hip* E) { return plain_v46_only(E, "high bit depth semi-planar surfaces are"); }
 // what k_apply_sp gets, for surfaces and motion in DEVICE memory: the luma set and the chroma set of the hbd call (edge semantics: extent = the plane) on one motion
 static ApplySpArgs sp_args(const rife_hip_semiplanar_t& p0, const rife_hip_semiplanar_t& p1, const rife_hip_semiplanar_t& out, const uint8_t* flow, size_t flow_pitch,
                            const uint8_t* mask, size_t mask_pitch, int format) {
@@ -86,45 +80,35 @@ static int rife_hip_process_hbd_semiplanar_impl(const rife_hip_t* E, const rife_
         return 0;
     }
     if ((rc = check_device(E->gpuid))) return rc;
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, rife_sp::planar_pixfmt(in0->chroma, in0->csp));
-    if (!rc) {
-        Ctx& C = *c;
+    return with_leased_ctx(E, w, h, rife_sp::planar_pixfmt(in0->chroma, in0->csp), [&](Ctx& C) {
         MotionArgs mo;
-        rc = apply_motion_stage(C, mo);
+        int rc = apply_motion_stage(C, mo);
         const int ch = rife_sp::chroma_h(h, in0->chroma);
         const size_t rby = (size_t)w * 2, rbc = (size_t)rife_sp::chroma_w(w) * 4;
-        const size_t ly = ((size_t)h * rby + 15) / 16 * 16, lc = ((size_t)ch * rbc + 15) / 16 * 16, need = 3 * (ly + lc);
-        if (!rc && C.ap_bytes < need) { C.ap_planes = nullptr; C.ap_bytes = 0; if (!(rc = dalloc(C, C.ap_planes, need))) C.ap_bytes = need; }
-        hipError_t e = hipSuccess;
+        const size_t ly = align_up((size_t)h * rby, 16), lc = align_up((size_t)ch * rbc, 16);
+        if (!rc) rc = apply_staging(C, 3 * (ly + lc));
+        if (rc) return rc;
+        rife_hip_semiplanar_t d[3] = {*in0, *in1, *out};                  // the tight device copies
+        for (int i = 0; i < 3; i++) { d[i].y = C.ap_planes + i * (ly + lc); d[i].cbcr = C.ap_planes + i * (ly + lc) + ly; d[i].pitch_y = (ptrdiff_t)rby; d[i].pitch_c = (ptrdiff_t)rbc; }
+        rc = upload_with_token(E, C.stream, [&] {
+            const rife_hip_semiplanar_t* src[2] = {in0, in1};
+            hipError_t e = hipSuccess;
+            for (int i = 0; i < 2 && e == hipSuccess; i++) {
+                e = hipMemcpy2DAsync(d[i].y, rby, src[i]->y, (size_t)src[i]->pitch_y, rby, (size_t)h, hipMemcpyHostToDevice, C.stream);
+                if (e == hipSuccess) e = hipMemcpy2DAsync(d[i].cbcr, rbc, src[i]->cbcr, (size_t)src[i]->pitch_c, rbc, (size_t)ch, hipMemcpyHostToDevice, C.stream);
+            }
+            return e;
+        });
+        const HbdIO io = sp_io(d[0], d[1]);
+        if (!rc) rc = run_v4(*E, C, nullptr, nullptr, timestep, nullptr, nullptr, nullptr, &mo, &io);
+        if (!rc) rc = sp_apply_launch(&E->prof, C.stream, sp_args(d[0], d[1], d[2], mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32), in0->chroma);
         if (!rc) {
-            rife_hip_semiplanar_t d[3] = {*in0, *in1, *out};              // the tight device copies
-            for (int i = 0; i < 3; i++) { d[i].y = C.ap_planes + i * (ly + lc); d[i].cbcr = C.ap_planes + i * (ly + lc) + ly; d[i].pitch_y = (ptrdiff_t)rby; d[i].pitch_c = (ptrdiff_t)rbc; }
-            {
-                const bool token = process_switches().h2d_token;      // the upload token of enqueue_host_pair
-                std::unique_lock<std::mutex> g(E->h2d_mu, std::defer_lock);
-                if (token) g.lock();
-                const rife_hip_semiplanar_t* src[2] = {in0, in1};
-                for (int i = 0; i < 2 && e == hipSuccess; i++) {
-                    e = hipMemcpy2DAsync(d[i].y, rby, src[i]->y, (size_t)src[i]->pitch_y, rby, (size_t)h, hipMemcpyHostToDevice, C.stream);
-                    if (e == hipSuccess) e = hipMemcpy2DAsync(d[i].cbcr, rbc, src[i]->cbcr, (size_t)src[i]->pitch_c, rbc, (size_t)ch, hipMemcpyHostToDevice, C.stream);
-                }
-                if (e == hipSuccess && token) e = hipStreamSynchronize(C.stream);
-            }
-            if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
-            const HbdIO io = sp_io(d[0], d[1]);
-            if (!rc) rc = run_v4(*E, C, nullptr, nullptr, timestep, nullptr, nullptr, nullptr, &mo, &io);
-            if (!rc) rc = sp_apply_launch(&E->prof, C.stream, sp_args(d[0], d[1], d[2], mo.flow, mo.flow_pitch, mo.mask, mo.mask_pitch, RIFE_HIP_MOTION_F32), in0->chroma);
-            if (!rc) {
-                e = hipMemcpy2DAsync(out->y, (size_t)out->pitch_y, d[2].y, rby, rby, (size_t)h, hipMemcpyDeviceToHost, C.stream);
-                if (e == hipSuccess) e = hipMemcpy2DAsync(out->cbcr, (size_t)out->pitch_c, d[2].cbcr, rbc, rbc, (size_t)ch, hipMemcpyDeviceToHost, C.stream);
-                if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
-            }
+            hipError_t e = hipMemcpy2DAsync(out->y, (size_t)out->pitch_y, d[2].y, rby, rby, (size_t)h, hipMemcpyDeviceToHost, C.stream);
+            if (e == hipSuccess) e = hipMemcpy2DAsync(out->cbcr, (size_t)out->pitch_c, d[2].cbcr, rbc, rbc, (size_t)ch, hipMemcpyDeviceToHost, C.stream);
+            if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
         }
-    }
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+        return rc;
+    });
 }
 
 static int rife_hip_process_device_hbd_semiplanar_impl(const rife_hip_t* E, const rife_hip_semiplanar_t* in0, const rife_hip_semiplanar_t* in1, float timestep,
@@ -134,23 +118,9 @@ static int rife_hip_process_device_hbd_semiplanar_impl(const rife_hip_t* E, cons
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if ((rc = sp_supported(E))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
-    Ctx* c;
-    {      // the stream's workspace, as in rife_hip_process_device_impl
-        std::lock_guard<std::mutex> g(E->mu);
-        auto ps = E->part_streams.find(hip_stream);
-        if (ps != E->part_streams.end()) tl_cu_budget = ps->second;
-        auto& slot = E->stream_ctx[hip_stream];
-        if (!slot) {
-            slot.reset(new Ctx);
-            if (hip_stream) slot->stream = (hipStream_t)hip_stream;
-            else {
-                if (hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
-                slot->own_stream = true;
-            }
-        }
-        c = slot.get();
-    }
-    std::lock_guard<std::mutex> use(c->use);
+    StreamWorkspace ws(E, hip_stream);
+    if (ws.rc) return ws.rc;
+    Ctx* const c = ws.c;
     if (timestep == 0.f || timestep == 1.f) {
         if ((rc = sp_copy_device(c->stream, timestep == 0.f ? *in0 : *in1, *out))) return rc;
     } else {
@@ -191,22 +161,15 @@ int rife_hip_op_sp_to_rgb10(int gpuid, const rife_hip_semiplanar_t* img, uint32_
     if (!out_padded || force_scalar < 0 || force_scalar > 1) return fail(RIFE_HIP_EINVAL, "op_sp_to_rgb10: an output array and force_scalar 0 or 1");
     if ((rc = check_device(gpuid))) return rc;
     return guarded("rife_hip_op_sp_to_rgb10", [&] {
-        const int w = img->w, h = img->h, wp = (w + 31) / 32 * 32, hp = (h + 31) / 32 * 32;
-        const size_t nout = (size_t)wp * hp * 4;
+        const int w = img->w, h = img->h;
         ApplyMirror my, mc;
-        void* d_o = nullptr;
         bool vec = false;
         hipError_t e = my.upload(img->y, (size_t)img->pitch_y, (size_t)w * 2, h);
         if (e == hipSuccess) e = mc.upload(img->cbcr, (size_t)img->pitch_c, (size_t)rife_sp::chroma_w(w) * 4, rife_sp::chroma_h(h, img->chroma));
-        if (e == hipSuccess) e = hipMalloc(&d_o, nout);
-        if (e == hipSuccess) e = hipMemset(d_o, 0xa5, nout);                 // the kernel writes the padding too
-        if (e == hipSuccess) {
-            vec = launch_preproc_sp(0, SpPlanes{my.dev, mc.dev, (unsigned)img->pitch_y, (unsigned)img->pitch_c}, w, h, static_cast<uint32_t*>(d_o), wp, hp,
-                                    rife_sp::planar_pixfmt(img->chroma, img->csp), img->depth, force_scalar == 1);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpy(out_padded, d_o, nout, hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(d_o);
+        if (e == hipSuccess) e = op_padded_rgb10(w, h, out_padded, [&](uint32_t* d_o, int wp, int hp) {
+            vec = launch_preproc_sp(0, SpPlanes{my.dev, mc.dev, (unsigned)img->pitch_y, (unsigned)img->pitch_c}, w, h, d_o, wp, hp, rife_sp::planar_pixfmt(img->chroma, img->csp),
+                                    img->depth, force_scalar == 1);
+        });
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_sp_to_rgb10: ") + hipGetErrorString(e));
         return vec ? 1 : 0;
     });
@@ -224,7 +187,8 @@ int rife_hip_op_apply_sp(int gpuid, const rife_hip_semiplanar_t* p0, const rife_
     return guarded("rife_hip_op_apply_sp", [&] {
         const int w = p0->w, h = p0->h, ch = rife_sp::chroma_h(h, p0->chroma);
         const size_t rby = (size_t)w * 2, rbc = (size_t)rife_sp::chroma_w(w) * 4;
-        ApplyMirror my[3], mc[3], mf, mm;
+        ApplyMirror my[3], mc[3];
+        MotionMirror mm;
         const rife_hip_semiplanar_t* src[3] = {p0, p1, out};
         rife_hip_semiplanar_t d[3] = {*p0, *p1, *out};
         hipError_t e = hipSuccess;
@@ -232,19 +196,12 @@ int rife_hip_op_apply_sp(int gpuid, const rife_hip_semiplanar_t* p0, const rife_
             e = my[i].upload(src[i]->y, (size_t)src[i]->pitch_y, rby, h); d[i].y = my[i].dev;
             if (e == hipSuccess) { e = mc[i].upload(src[i]->cbcr, (size_t)src[i]->pitch_c, rbc, ch); d[i].cbcr = mc[i].dev; }
         }
-        if (e == hipSuccess) e = mf.upload(hm->flow, hm->flow_pitch, rife_motion::flow_row_bytes(mw, hm->format), mh);
-        if (e == hipSuccess) e = mm.upload(hm->mask, hm->mask_pitch, rife_motion::mask_row_bytes(mw, hm->format), mh);
+        if (e == hipSuccess) e = mm.upload(*hm, mw, mh);
         int lrc = 0;
         bool vec = false;
-        if (e == hipSuccess) {
-            hipStream_t st = nullptr;
-            e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-            if (e == hipSuccess) {
-                lrc = sp_apply_launch(nullptr, st, sp_args(d[0], d[1], d[2], mf.dev, hm->flow_pitch, mm.dev, hm->mask_pitch, hm->format), p0->chroma, force_scalar == 1, &vec);
-                e = hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-        }
+        if (e == hipSuccess) e = op_on_own_stream(lrc, [&](hipStream_t st) {
+            return sp_apply_launch(nullptr, st, sp_args(d[0], d[1], d[2], mm.flow.dev, hm->flow_pitch, mm.mask.dev, hm->mask_pitch, hm->format), p0->chroma, force_scalar == 1, &vec);
+        });
         if (lrc) return lrc;
         if (e == hipSuccess) e = my[2].download(out->y, (size_t)out->pitch_y, rby);
         if (e == hipSuccess) e = mc[2].download(out->cbcr, (size_t)out->pitch_c, rbc);

@@ -5,6 +5,7 @@
 //                  write the workspace's tight frame (Ctx::d_out) and k_store_rows moves it into the caller's pitch on the same stream
 //   host planes:   2-D copies per plane between the caller's planes and the tight staging buffers, then the path of the _px calls (same upload token)
 // An image whose planes are all tight IS the _px call and goes there.
+// The skeleton around them is engine_abi.h's: StreamWorkspace, with_leased_ctx, upload_with_token, CopyStreamLease, guarded.
 
 // 0, or -RIFE_HIP_EINVAL: the rules of rife_hip_image_check on every image of a call, and that they agree
 static int image_precheck(std::initializer_list<const rife_hip_image_t*> imgs) {
@@ -15,16 +16,10 @@ static int image_precheck(std::initializer_list<const rife_hip_image_t*> imgs) {
         if (first && rife_img::check_same(first, im, err)) return fail(RIFE_HIP_EINVAL, err);
         if (!first) first = im;
     }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RIFE_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    return 0;
+    return no_hip_device();
 }
 // strided images are served by the plain rife-v4.6 schedule only (RGB8 included: the other families' pre-processing reads tight frames)
-static int image_supported(const rife_hip* E) {
-    const char* what = not_plain_v46(E);      // engine_abi.h: the family or mode, named once for the _px formats and for images
-    if (!what) return 0;
-    return fail(RIFE_HIP_ENOSYS, std::string("strided and planar images are served for model family rife-v4.6 in plain mode only, not for ") + what);
-}
+static int image_supported(const rife_hip* E) { return plain_v46_only(E, "strided and planar images are"); }
 // byte offset of plane p in the tight frame of the _px calls
 static size_t image_tight_offset(int w, int h, int pixfmt, int p) {
     size_t off = 0;
@@ -85,25 +80,16 @@ static int rife_hip_process_image_impl(const rife_hip_t* E, const rife_hip_image
     if ((rc = image_supported(E))) return rc;
     if (timestep == 0.f || timestep == 1.f) { image_canon_host(*out, timestep == 0.f ? *in0 : *in1); return 0; }
     if ((rc = check_device(E->gpuid))) return rc;
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, pixfmt);
-    if (!rc) {
+    return with_leased_ctx(E, w, h, pixfmt, [&](Ctx& c) {
+        int rc = upload_with_token(E, c.stream, [&] {
+            const hipError_t e = image_copy_to_tight(c.d_in0, *in0, hipMemcpyHostToDevice, c.stream);
+            return e != hipSuccess ? e : image_copy_to_tight(c.d_in1, *in1, hipMemcpyHostToDevice, c.stream);
+        });
+        if (!rc) rc = run_v4_replay(*E, c, c.d_in0, c.d_in1, timestep, c.d_out);
         hipError_t e;
-        {
-            const bool token = process_switches().h2d_token;      // the upload token of enqueue_host_pair
-            std::unique_lock<std::mutex> g(E->h2d_mu, std::defer_lock);
-            if (token) g.lock();
-            e = image_copy_to_tight(c->d_in0, *in0, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = image_copy_to_tight(c->d_in1, *in1, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess && token) e = hipStreamSynchronize(c->stream);
-        }
-        if (e != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("H2D: ") + hipGetErrorString(e));
-        if (!rc) rc = run_v4_replay(*E, *c, c->d_in0, c->d_in1, timestep, c->d_out);
-        if (!rc && (e = image_copy_from_tight(*out, c->d_out, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
-    }
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+        if (!rc && (e = image_copy_from_tight(*out, c.d_out, hipMemcpyDeviceToHost, c.stream)) != hipSuccess) rc = fail(RIFE_HIP_EHIP, std::string("D2H: ") + hipGetErrorString(e));
+        return rc;
+    });
 }
 
 static int rife_hip_frame_upload_image_impl(const rife_hip_t* E, const rife_hip_image_t* img, rife_hip_frame_t** frame) {
@@ -120,15 +106,8 @@ static int rife_hip_frame_upload_image_impl(const rife_hip_t* E, const rife_hip_
     const size_t nbytes = frame_bytes(img->w, img->h, img->pixfmt);
     f->nbytes = nbytes; f->pool = E->frame_pool;
     if (!(f->d = f->pool->take(nbytes))) return fail(RIFE_HIP_EHIP, "hipMalloc of a resident frame failed");
-    hipStream_t st = nullptr;      // a copy on its own stream, drained here (rife_hip_frame_upload_impl)
-    {
-        std::lock_guard<std::mutex> g(E->mu);
-        if (!E->upload_streams.empty()) { st = E->upload_streams.back(); E->upload_streams.pop_back(); }
-    }
-    hipError_t e = st ? hipSuccess : hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = image_copy_to_tight(f->d, *img, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (st) { std::lock_guard<std::mutex> g(E->mu); E->upload_streams.push_back(st); }
+    // a copy on its own stream, drained here (rife_hip_frame_upload_impl)
+    const hipError_t e = CopyStreamLease(E).run([&](hipStream_t st) { return image_copy_to_tight(f->d, *img, hipMemcpyHostToDevice, st); });
     if (e != hipSuccess) { f->pool->give(f->d, nbytes); return fail(RIFE_HIP_EHIP, std::string("frame upload: ") + hipGetErrorString(e)); }
     *frame = f.release();
     return 0;
@@ -149,26 +128,16 @@ static int rife_hip_process_frames_image_impl(const rife_hip_t* E, const rife_hi
     if ((rc = image_supported(E))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
     if (timestep == 0.f || timestep == 1.f) {      // a copy stream of the pool, never the legacy stream; canonical form on the host, in place
-        hipStream_t st = nullptr;
-        {
-            std::lock_guard<std::mutex> g(E->mu);
-            if (!E->upload_streams.empty()) { st = E->upload_streams.back(); E->upload_streams.pop_back(); }
-        }
-        hipError_t e = st ? hipSuccess : hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        if (e == hipSuccess) e = image_copy_from_tight(*out, timestep == 0.f ? f0->d : f1->d, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (st) { std::lock_guard<std::mutex> g(E->mu); E->upload_streams.push_back(st); }
+        const hipError_t e = CopyStreamLease(E).run([&](hipStream_t st) { return image_copy_from_tight(*out, timestep == 0.f ? f0->d : f1->d, hipMemcpyDeviceToHost, st); });
         if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("frame download: ") + hipGetErrorString(e));
         image_canon_host(*out, *out);
         return 0;
     }
-    std::unique_ptr<Ctx> c;
-    rc = lease_ctx(E, c, w, h, 0, pixfmt);
-    if (!rc) rc = run_v4_replay(*E, *c, f0->d, f1->d, timestep, c->d_out);
-    if (!rc && image_copy_from_tight(*out, c->d_out, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(RIFE_HIP_EHIP, "D2H failed");
-    if (c && hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(RIFE_HIP_EHIP, "stream sync failed");
-    if (c) release_ctx(E, c);
-    return rc;
+    return with_leased_ctx(E, w, h, pixfmt, [&](Ctx& c) {
+        int rc = run_v4_replay(*E, c, f0->d, f1->d, timestep, c.d_out);
+        if (!rc && image_copy_from_tight(*out, c.d_out, hipMemcpyDeviceToHost, c.stream) != hipSuccess) rc = fail(RIFE_HIP_EHIP, "D2H failed");
+        return rc;
+    });
 }
 
 static int rife_hip_process_device_image_impl(const rife_hip_t* E, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out, void* hip_stream) {
@@ -180,23 +149,9 @@ static int rife_hip_process_device_image_impl(const rife_hip_t* E, const rife_hi
     if ((rc = process_common(E, w, h, timestep))) return rc;
     if ((rc = image_supported(E))) return rc;
     if ((rc = check_device(E->gpuid))) return rc;
-    Ctx* c;
-    {      // the stream's workspace, as in rife_hip_process_device_impl
-        std::lock_guard<std::mutex> g(E->mu);
-        auto ps = E->part_streams.find(hip_stream);
-        if (ps != E->part_streams.end()) tl_cu_budget = ps->second;
-        auto& slot = E->stream_ctx[hip_stream];
-        if (!slot) {
-            slot.reset(new Ctx);
-            if (hip_stream) slot->stream = (hipStream_t)hip_stream;
-            else {
-                if (hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking) != hipSuccess) return fail(RIFE_HIP_EHIP, "hipStreamCreate failed");
-                slot->own_stream = true;
-            }
-        }
-        c = slot.get();
-    }
-    std::lock_guard<std::mutex> use(c->use);
+    StreamWorkspace ws(E, hip_stream);
+    if (ws.rc) return ws.rc;
+    Ctx* const c = ws.c;
     if (timestep == 0.f || timestep == 1.f) {
         if ((rc = image_canon_device(c->stream, timestep == 0.f ? *in0 : *in1, *out))) return rc;
     } else {
@@ -222,24 +177,18 @@ int rife_hip_image_check(const rife_hip_image_t* img) {
 }
 size_t rife_hip_image_row_bytes(int w, int pixfmt, int plane) { return rife_img::row_bytes(w, pixfmt, plane); }
 
-// nothing may throw across the C boundary (std::bad_alloc)
-#define RIFE_IMAGE_ENTRY(name, call)                                                                        \
-    try { return call; }                                                                                    \
-    catch (const std::exception& e) { return fail(RIFE_HIP_EIO, std::string(name ": ") + e.what()); }       \
-    catch (...) { return fail(RIFE_HIP_EIO, name ": unknown exception"); }
 int rife_hip_process_image(const rife_hip_t* E, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out) {
-    RIFE_IMAGE_ENTRY("rife_hip_process_image", rife_hip_process_image_impl(E, in0, in1, timestep, out))
+    return guarded("rife_hip_process_image", [&] { return rife_hip_process_image_impl(E, in0, in1, timestep, out); });
 }
 int rife_hip_process_device_image(const rife_hip_t* E, const rife_hip_image_t* in0, const rife_hip_image_t* in1, float timestep, const rife_hip_image_t* out, void* hip_stream) {
-    RIFE_IMAGE_ENTRY("rife_hip_process_device_image", rife_hip_process_device_image_impl(E, in0, in1, timestep, out, hip_stream))
+    return guarded("rife_hip_process_device_image", [&] { return rife_hip_process_device_image_impl(E, in0, in1, timestep, out, hip_stream); });
 }
 int rife_hip_frame_upload_image(const rife_hip_t* E, const rife_hip_image_t* img, rife_hip_frame_t** frame) {
-    RIFE_IMAGE_ENTRY("rife_hip_frame_upload_image", rife_hip_frame_upload_image_impl(E, img, frame))
+    return guarded("rife_hip_frame_upload_image", [&] { return rife_hip_frame_upload_image_impl(E, img, frame); });
 }
 int rife_hip_process_frames_image(const rife_hip_t* E, const rife_hip_frame_t* f0, const rife_hip_frame_t* f1, float timestep, const rife_hip_image_t* out) {
-    RIFE_IMAGE_ENTRY("rife_hip_process_frames_image", rife_hip_process_frames_image_impl(E, f0, f1, timestep, out))
+    return guarded("rife_hip_process_frames_image", [&] { return rife_hip_process_frames_image_impl(E, f0, f1, timestep, out); });
 }
-#undef RIFE_IMAGE_ENTRY
 
 #ifdef RIFE_HIP_TEST_BUILD
 // ---- the pitched kernels alone (include/rife_hip_test.h) ----
@@ -255,7 +204,7 @@ struct ImageMirror {
         const int np = rife_img::planes(im.pixfmt);
         for (int p = 0; p < np; p++) {
             span[p] = (size_t)(rife_img::plane_rows(im.h, im.pixfmt, p) - 1) * (size_t)im.pitch[p] + rife_img::row_bytes(im.w, im.pixfmt, p);
-            off[p] = (cur + 15) / 16 * 16 + (reinterpret_cast<uintptr_t>(im.plane[p]) & 15);
+            off[p] = align_up(cur, 16) + (reinterpret_cast<uintptr_t>(im.plane[p]) & 15);
             cur = off[p] + span[p];
         }
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), cur + 16);
@@ -286,23 +235,17 @@ int rife_hip_op_image_to_resident(int gpuid, const rife_hip_image_t* img, int fo
     if (!out_padded || force_scalar < 0 || force_scalar > 2) return fail(RIFE_HIP_EINVAL, "op_image_to_resident: an output array and force_scalar 0, 1 or 2");
     if (force_scalar == 2 && !rife_img::is_tight(img)) return fail(RIFE_HIP_EINVAL, "op_image_to_resident: the tight kernels take a tight image");
     if ((rc = check_device(gpuid))) return rc;
-    const int w = img->w, h = img->h, wp = (w + 31) / 32 * 32, hp = (h + 31) / 32 * 32;
-    const size_t nout = (size_t)wp * hp * 4;
+    const int w = img->w, h = img->h;
     ImageMirror m;
-    void* d_o = nullptr;
     uint8_t* d_t = nullptr;                                                  // force_scalar == 2: the tight frame in ONE piece (the tight kernels find the chroma planes by arithmetic), at the host pointer's alignment modulo 16
     const size_t ntight = frame_bytes(w, h, img->pixfmt), toff = reinterpret_cast<uintptr_t>(img->plane[0]) & 15;
     hipError_t e = force_scalar == 2 ? hipMalloc(reinterpret_cast<void**>(&d_t), ntight + 16) : m.upload(*img);
     if (e == hipSuccess && force_scalar == 2) e = hipMemcpy(d_t + toff, img->plane[0], ntight, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&d_o, nout);
-    if (e == hipSuccess) e = hipMemset(d_o, 0xa5, nout);                     // the kernel writes the padding too
-    if (e == hipSuccess) {
-        if (force_scalar == 2) launch_preproc(0, d_t + toff, w, h, static_cast<uint32_t*>(d_o), wp, hp, img->pixfmt);
-        else launch_preproc_planes(0, plane_set(m.dev), w, h, static_cast<uint32_t*>(d_o), wp, hp, img->pixfmt, force_scalar == 1);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(out_padded, d_o, nout, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_o); (void)hipFree(d_t);
+    if (e == hipSuccess) e = op_padded_rgb10(w, h, out_padded, [&](uint32_t* d_o, int wp, int hp) {
+        if (force_scalar == 2) launch_preproc(0, d_t + toff, w, h, d_o, wp, hp, img->pixfmt);
+        else launch_preproc_planes(0, plane_set(m.dev), w, h, d_o, wp, hp, img->pixfmt, force_scalar == 1);
+    });
+    (void)hipFree(d_t);
     if (e != hipSuccess) return fail(RIFE_HIP_EHIP, std::string("op_image_to_resident: ") + hipGetErrorString(e));
     return 0;
 }

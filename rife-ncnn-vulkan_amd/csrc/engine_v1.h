@@ -294,9 +294,16 @@ static int load_v2(rife_hip* E, const std::string& dir) {
     return 0;
 }
 
-static int check_device(int gpuid) {
+// "no HIP device at all" (-RIFE_HIP_ENODEV): what every entry point answers after its argument checks and before anything looks at the engine; *count = the devices
+static int no_hip_device(int* count = nullptr) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RIFE_HIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    if (count) *count = n;
+    return 0;
+}
+static int check_device(int gpuid) {
+    int n = 0;
+    if (int rc = no_hip_device(&n)) return rc;
     if (gpuid < 0 || gpuid >= n) return fail(RIFE_HIP_ENODEV, "invalid gpu device");
     HIPCHK(hipSetDevice(gpuid));
     return 0;
