@@ -183,6 +183,45 @@ int rife_hip_op_sp_to_rgb10(int gpuid, const rife_hip_semiplanar_t* img, uint32_
 int rife_hip_op_apply_sp(int gpuid, const rife_hip_semiplanar_t* p0, const rife_hip_semiplanar_t* p1, const rife_hip_semiplanar_t* out, const rife_hip_motion_t* host_motion,
                          int mw, int mh, int force_scalar);
 
+/* ---- the rife-v2.x / v3.x schedule's own kernels alone (csrc/elementwise_v2.h, stem_fused_v2.h, conv_img.h, and the two-tensor / second-destination forms of
+ * launch_conv; csrc/engine_v2_ops.h), ONE launch of the kernel under test per call - the launches of run_v2_ifnet / run_v2_flow / run_v2_synth with their grids.
+ * Host arrays in device layout go in and out; every OUTPUT buffer is uploaded as given and comes back whole, so a store outside the kernel's domain shows up in the
+ * caller's sentinels.  Layers are built by the product's layer upload with the flags rife_hip_load sets for the v2 family and launched by the product's launchers.
+ * What the product would not launch is -RIFE_HIP_EINVAL before anything is uploaded.
+ * Frames: wp x hp, multiples of 32, below 2^27 pixels.  imgf4 = 0: resident dwords R | G << 8 | B << 16 (ImgU8); imgf4 = 1: float4 per pixel (ImgF4, the half frames of
+ * UHD mode: multiples of 16).  acc: the running flow, [hp / 2][wp / 2][4].
+ * op_v2_assemble: first != 0: k2_assemble0<S, IMG> (S = 8, 4; acc unused) -> out [hp / S][wp / S][8]; else k2_assemble<S, IMG, FSCALE> (S = 4, 2, 1; fscale: S = 2 only)
+ * -> out [hp / S][wp / S][16], pad channels included. */
+int rife_hip_op_v2_assemble(int gpuid, int S, int first, int fscale, int imgf4, const void* img0, const void* img1, int wp, int hp, const float* acc, float* out);
+/* op_v2_stem: the 10 -> cout (4n <= 96) stride-2 convolution + PReLU on that block input, S = 1, 2.  weight [cout][10][3][3] (exactly fp16), bias, slope [cout];
+ * out [hp / 2S][wp / 2S][out_ld].  route = RIFE_HIP_V2_STEM_PRODUCT: stem2_fusable + launch_stem2_fused, the R64 form where the product picks it; _NO_R64: the R64 form
+ * off, as RIFE_HIP_V2_STEM_R64=0; _UNFUSED: k2_assemble, then launch_conv on conv_h2s2_kernel, as RIFE_HIP_V2_FUSED_STEM=0. */
+enum { RIFE_HIP_V2_STEM_PRODUCT = 0, RIFE_HIP_V2_STEM_NO_R64 = 1, RIFE_HIP_V2_STEM_UNFUSED = 2 };
+int rife_hip_op_v2_stem(int gpuid, int route, int S, int fscale, int imgf4, const void* img0, const void* img1, int wp, int hp, const float* acc, const float* weight,
+                        const float* bias, const float* slope, int cout, int out_ld, float* out);
+/* op_v2_flow_accum: k2_flow_accum<S, FIRST, MUL> for the triples run_v2_ifnet launches - (8, 1, 0), (4, 0, 0), (2, 0, 0), (1, 0, 0) and, rife-v3.x, (4, 1, 1), (2, 0, 1).
+ * D [hh / S][wh / S][4]; acc [hh][wh][4] goes in and comes out; wh, hh multiples of 16. */
+int rife_hip_op_v2_flow_accum(int gpuid, int S, int first, int mul, const float* D, int wh, int hh, float* acc);
+/* op_v2_ctx_warps: the k2_flow_half<true> / <false> chains of both frames, then batch = 0: the four-plus-four k2_warp_nhwc launches, batch = 1: the one k2_warp_nhwc_batch
+ * launch, with the out_ld / out_coff table of run_v2_synth.  feat[4 frame + level]: [hp >> (level + 2)][wp >> (level + 2)][32 << level]; fl[4 frame + level]: the flow
+ * pyramids, [..][..][2], in and out; cat[level]: the concat buffers B1..B4, [..][..][128 << level], in and out. */
+int rife_hip_op_v2_ctx_warps(int gpuid, int batch, const float* acc, int wp, int hp, const float* const* feat, float* const* fl, float* const* cat);
+/* op_v2_final: float_form = 0: k2_final, the u8 RGB frame of w x h from the padded inputs (wp, hp = w, h rounded up to 32n); 1: k2_final_float, [hp][wp] float4.
+ * head [hp][wp][4] (the sigmoid head's output).  out: RIFE_HIP_TAIL_GUARD bytes, the frame, RIFE_HIP_TAIL_GUARD bytes. */
+int rife_hip_op_v2_final(int gpuid, int float_form, const uint32_t* img0, const uint32_t* img1, int w, int h, const float* acc, const float* head, void* out);
+/* op_v2_uhd: what = 0: k2_image_half, a resident frame wp x hp -> float4 [hp / 2][wp / 2]; what = 1: k2_flow_up2_double, float4 [hp / 2][wp / 2] -> [hp][wp] (16n). */
+int rife_hip_op_v2_uhd(int gpuid, int what, const void* in, int wp, int hp, float* out);
+/* op_v2_conv_img: conv_img_s2_kernel, the ContextNet's 3 -> 32 stride-2 convolution + PReLU straight from the resident frame.  two = 0: one frame, gridDim.y = 1; 1: both
+ * frames, gridDim.y = 2.  The grid is capped as run_v2_synth caps it (8 / 4 workgroups per CU); cus > 0: that many compute units instead of the chip's.
+ * weight [32][3][3][3] (exactly fp16); out0, out1 [hp / 2][wp / 2][32]. */
+int rife_hip_op_v2_conv_img(int gpuid, int two, int cus, const uint32_t* img0, const uint32_t* img1, int wp, int hp, const float* weight, const float* bias, const float* slope,
+                            float* out0, float* out1);
+/* op_conv_pair: launch_conv on a cin (16n) -> cout (4n) layer, 3x3 stride 1 | 2 or (deconv) 4x4 stride-2 transposed, with x1 / y1 non-null: the second tensor pair of the
+ * launch; y2 non-null (one tensor, stride 1): the second destination view.  x [H][W][cin]; y0, y1 [Ho][Wo][y_ld] with the layer's channels at y_coff; y2 [Ho][Wo][y2_ld] at
+ * y2_coff.  A second destination where run_v2_synth would copy the skip instead (its dual_ok), and either form on a transposed layer: -RIFE_HIP_EINVAL. */
+int rife_hip_op_conv_pair(int gpuid, int cin, int cout, int stride, int deconv, int H, int W, const float* weight, const float* bias, const float* slope, const float* x0,
+                          const float* x1, float* y0, float* y1, int y_ld, int y_coff, float* y2, int y2_ld, int y2_coff);
+
 /* ---- the generic layer-wise graph executor (csrc/graph_exec.h, graph_run.h, graph_kernels.h: the v1 family) on any .param / .bin pair, one graph_run per call.
  * graph_plan needs no device: it parses <base>.param as rife_hip_graph_check does and writes what the loader settled on, one line per layer, tab-separated:
  *   <layer name> <kind> fold=<the layer that executes this one | -> out=<the blob the launch writes | -> class=<g_conv3x3 | g_conv3x3_s2 | g_conv5x5 | g_deconv4x4 | direct | ->

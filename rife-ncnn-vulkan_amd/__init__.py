@@ -72,7 +72,11 @@ TEST_ABI_SYMBOLS = ["rife_hip_v4_extract_flow", "rife_hip_v4_flow_dims", "rife_h
                     "rife_hip_op_image_to_resident", "rife_hip_op_resident_to_image", "rife_hip_op_s16_geom", "rife_hip_op_trunk", "rife_hip_v4_process_injected_px",
                     "rife_hip_op_trunk_prec", "rife_hip_op_stem1_s16", "rife_hip_op_head_ps", "rife_hip_op_tail", "rife_hip_op_tail_motion", "rife_hip_op_apply", "rife_hip_op_apply_scaled", "rife_hip_op_hbd_to_rgb10", "rife_hip_op_apply_yuv",
                     "rife_hip_op_packed_to_rgb10", "rife_hip_op_apply_packed", "rife_hip_op_sp_to_rgb10", "rife_hip_op_apply_sp",
-                    "rife_hip_graph_plan", "rife_hip_graph_eval"]
+                    "rife_hip_graph_plan", "rife_hip_graph_eval",
+                    "rife_hip_op_v2_assemble", "rife_hip_op_v2_stem", "rife_hip_op_v2_flow_accum", "rife_hip_op_v2_ctx_warps", "rife_hip_op_v2_final", "rife_hip_op_v2_uhd",
+                    "rife_hip_op_v2_conv_img", "rife_hip_op_conv_pair"]
+# rife_hip_op_v2_stem: which launches run the stem (include/rife_hip_test.h RIFE_HIP_V2_STEM_*)
+V2_STEM_PRODUCT, V2_STEM_NO_R64, V2_STEM_UNFUSED = 0, 1, 2
 # rife_hip_op_tail: which kernel writes the frame (include/rife_hip_test.h RIFE_HIP_TAIL_*), and the guard bytes on either side of the frame
 TAIL_RS, TAIL_HEAD_S16, TAIL_HEAD_F32, TAIL_UNFUSED = 0, 1, 2, 3
 TAIL_GUARD = 256
@@ -241,6 +245,14 @@ def _load(path, with_test_surface):
         L.rife_hip_op_tail_motion.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t]
         L.rife_hip_graph_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
         L.rife_hip_graph_eval.argtypes = [ci, ctypes.c_char_p, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci]
+        L.rife_hip_op_v2_assemble.argtypes = [ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp]
+        L.rife_hip_op_v2_stem.argtypes = [ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, ci, vp]
+        L.rife_hip_op_v2_flow_accum.argtypes = [ci, ci, ci, ci, vp, ci, ci, vp]
+        L.rife_hip_op_v2_ctx_warps.argtypes = [ci, ci, vp, ci, ci, vp, vp, vp]
+        L.rife_hip_op_v2_final.argtypes = [ci, ci, vp, vp, ci, ci, vp, vp, vp]
+        L.rife_hip_op_v2_uhd.argtypes = [ci, ci, vp, ci, ci, vp]
+        L.rife_hip_op_v2_conv_img.argtypes = [ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        L.rife_hip_op_conv_pair.argtypes = [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci]
     return L
 
 
@@ -1606,3 +1618,125 @@ def op_rgb10_to_yuv(packed, pixfmt, gpuid=0):
     out = np.empty(yuv_frame_bytes(w, h, pixfmt) // np.dtype(yuv_dtype(pixfmt)).itemsize, yuv_dtype(pixfmt))
     _check(testlib().rife_hip_op_rgb10_to_yuv(gpuid, _p(a), w, h, int(pixfmt), _p(out)), "op_rgb10_to_yuv", testlib())
     return out
+
+
+# ---- the rife-v2.x / v3.x schedule's own kernels alone (include/rife_hip_test.h, csrc/engine_v2_ops.h): arrays in DEVICE layout (NHWC float32, resident uint32 frames);
+# every `out` argument goes to the device as given and the whole buffer after the launch is returned as a new array ----
+def _v2_frames(img0, img1):
+    """Two frames of one form: (hp, wp) uint32 resident dwords (ImgU8) or (hp, wp, 4) float32 (ImgF4).  Returns (imgf4, img0, img1, wp, hp)."""
+    f4 = np.asarray(img0).dtype != np.uint32
+    a = np.ascontiguousarray(img0, np.float32 if f4 else np.uint32); b = np.ascontiguousarray(img1, np.float32 if f4 else np.uint32)
+    if a.shape != b.shape or a.ndim != (3 if f4 else 2) or (f4 and a.shape[2] != 4):
+        raise ValueError("two (hp, wp) uint32 frames or two (hp, wp, 4) float32 frames")
+    return int(f4), a, b, a.shape[1], a.shape[0]
+
+
+def _v2_out(out, shape, dtype=np.float32):
+    o = np.array(out, dtype)                           # a copy: the call writes into it
+    if o.shape != tuple(shape):
+        raise ValueError("out must be %s" % (tuple(shape),))
+    return o
+
+
+def op_v2_assemble(S, img0, img1, acc, out, first=False, fscale=False, gpuid=0):
+    """k2_assemble0<S> (first; acc unused) -> (hp / S, wp / S, 8), or k2_assemble<S, FSCALE> -> (hp / S, wp / S, 16), pad channels included."""
+    f4, a, b, wp, hp = _v2_frames(img0, img1)
+    acc = None if acc is None else np.ascontiguousarray(acc, np.float32)
+    if acc is not None and acc.shape != (hp // 2, wp // 2, 4):
+        raise ValueError("acc must be (hp / 2, wp / 2, 4)")
+    o = _v2_out(out, (hp // S, wp // S, 8 if first else 16))
+    _check(testlib().rife_hip_op_v2_assemble(gpuid, int(S), int(first), int(fscale), f4, _p(a), _p(b), wp, hp, _p(acc), _p(o)), "op_v2_assemble", testlib())
+    return o
+
+
+def op_v2_stem(route, S, img0, img1, acc, weight, bias, slope, out, fscale=False, gpuid=0):
+    """The 10 -> cout stride-2 stem on the block input at scale S through `route` (V2_STEM_PRODUCT / _NO_R64 / _UNFUSED).  weight (cout, 10, 3, 3); out (hp / 2S, wp / 2S, out_ld)."""
+    f4, a, b, wp, hp = _v2_frames(img0, img1)
+    acc = np.ascontiguousarray(acc, np.float32); weight = np.ascontiguousarray(weight, np.float32)
+    bias = np.ascontiguousarray(bias, np.float32); slope = np.ascontiguousarray(slope, np.float32)
+    cout = weight.shape[0]
+    if acc.shape != (hp // 2, wp // 2, 4) or weight.shape != (cout, 10, 3, 3) or bias.shape != (cout,) or slope.shape != (cout,):
+        raise ValueError("acc (hp / 2, wp / 2, 4), weight (cout, 10, 3, 3), bias (cout) and slope (cout)")
+    o = np.array(out, np.float32)
+    if o.ndim != 3 or o.shape[:2] != (hp // S // 2, wp // S // 2):
+        raise ValueError("out must be (hp / 2S, wp / 2S, out_ld)")
+    _check(testlib().rife_hip_op_v2_stem(gpuid, int(route), int(S), int(fscale), f4, _p(a), _p(b), wp, hp, _p(acc), _p(weight), _p(bias), _p(slope), cout, o.shape[2], _p(o)),
+           "op_v2_stem", testlib())
+    return o
+
+
+def op_v2_flow_accum(S, D, acc, first=False, mul=False, gpuid=0):
+    """k2_flow_accum<S, FIRST, MUL>: D (hh / S, wh / S, 4) into acc (hh, wh, 4); returns acc after the launch."""
+    D = np.ascontiguousarray(D, np.float32)
+    a = np.array(acc, np.float32)
+    if a.ndim != 3 or a.shape[2] != 4 or D.shape != (a.shape[0] // S, a.shape[1] // S, 4):
+        raise ValueError("acc (hh, wh, 4) and D (hh / S, wh / S, 4)")
+    _check(testlib().rife_hip_op_v2_flow_accum(gpuid, int(S), int(first), int(mul), _p(D), a.shape[1], a.shape[0], _p(a)), "op_v2_flow_accum", testlib())
+    return a
+
+
+def op_v2_ctx_warps(acc, feats, fl, cat, batch=False, gpuid=0):
+    """The ContextNet's flow pyramids and warps (batch: the one k2_warp_nhwc_batch launch).  feats / fl: eight arrays [4 frame + level], (h_l, w_l, 32 << level) /
+    (h_l, w_l, 2); cat: B1..B4, (h_l, w_l, 128 << level).  Returns (fl, cat) after the launches."""
+    acc = np.ascontiguousarray(acc, np.float32)
+    hp, wp = 2 * acc.shape[0], 2 * acc.shape[1]
+    dims = [(hp >> (l + 2), wp >> (l + 2)) for l in range(4)]
+    feats = [np.ascontiguousarray(f, np.float32) for f in feats]
+    fl = [_v2_out(f, dims[z & 3] + (2,)) for z, f in enumerate(fl)]
+    cat = [_v2_out(c, dims[l] + (128 << l,)) for l, c in enumerate(cat)]
+    if len(feats) != 8 or len(fl) != 8 or len(cat) != 4 or any(f.shape != dims[z & 3] + (32 << (z & 3),) for z, f in enumerate(feats)):
+        raise ValueError("eight feature tensors (h_l, w_l, 32 << level), eight flow levels and four concat buffers")
+    pf = (ctypes.c_void_p * 8)(*[f.ctypes.data for f in feats]); pl = (ctypes.c_void_p * 8)(*[f.ctypes.data for f in fl]); pc = (ctypes.c_void_p * 4)(*[c.ctypes.data for c in cat])
+    _check(testlib().rife_hip_op_v2_ctx_warps(gpuid, int(batch), _p(acc), wp, hp, pf, pl, pc), "op_v2_ctx_warps", testlib())
+    return fl, cat
+
+
+def op_v2_final(img0, img1, w, h, acc, head, out, float_form=False, gpuid=0):
+    """k2_final (uint8 buffer: TAIL_GUARD + w * h * 3 + TAIL_GUARD bytes) / k2_final_float (TAIL_GUARD + hp * wp * 16 + TAIL_GUARD bytes); returns the whole buffer."""
+    _, a, b, wp, hp = _v2_frames(np.asarray(img0, np.uint32), np.asarray(img1, np.uint32))
+    acc = np.ascontiguousarray(acc, np.float32); head = np.ascontiguousarray(head, np.float32)
+    if (wp, hp) != ((w + 31) // 32 * 32, (h + 31) // 32 * 32) or acc.shape != (hp // 2, wp // 2, 4) or head.shape != (hp, wp, 4):
+        raise ValueError("frames (hp, wp), acc (hp / 2, wp / 2, 4) and head (hp, wp, 4) of the frame padded to 32n")
+    buf = _v2_out(np.asarray(out, np.uint8).reshape(-1), (2 * TAIL_GUARD + (hp * wp * 16 if float_form else w * h * 3),), np.uint8)
+    _check(testlib().rife_hip_op_v2_final(gpuid, int(float_form), _p(a), _p(b), int(w), int(h), _p(acc), _p(head), _p(buf)), "op_v2_final", testlib())
+    return buf
+
+
+def op_v2_uhd(x, out, gpuid=0):
+    """k2_image_half ((hp, wp) uint32 -> (hp / 2, wp / 2, 4)) or k2_flow_up2_double ((hp / 2, wp / 2, 4) float32 -> (hp, wp, 4)), by the input's type."""
+    what = int(np.asarray(x).dtype != np.uint32)
+    a = np.ascontiguousarray(x, np.float32 if what else np.uint32)
+    hp, wp = (2 * a.shape[0], 2 * a.shape[1]) if what else a.shape
+    o = _v2_out(out, (hp, wp, 4) if what else (hp // 2, wp // 2, 4))
+    _check(testlib().rife_hip_op_v2_uhd(gpuid, what, _p(a), wp, hp, _p(o)), "op_v2_uhd", testlib())
+    return o
+
+
+def op_v2_conv_img(img0, img1, weight, bias, slope, out0, out1=None, cus=0, gpuid=0):
+    """conv_img_s2_kernel on one frame (img1, out1 None: gridDim.y = 1) or on both (gridDim.y = 2).  weight (32, 3, 3, 3); out (hp / 2, wp / 2, 32).  Returns out0 or (out0, out1)."""
+    two = img1 is not None
+    a = np.ascontiguousarray(img0, np.uint32); b = np.ascontiguousarray(img1, np.uint32) if two else None
+    hp, wp = a.shape
+    weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32); slope = np.ascontiguousarray(slope, np.float32)
+    if weight.shape != (32, 3, 3, 3) or bias.shape != (32,) or slope.shape != (32,) or (two and (b.shape != a.shape or out1 is None)):
+        raise ValueError("weight (32, 3, 3, 3), bias (32), slope (32); two frames of one size need two outputs")
+    o0 = _v2_out(out0, (hp // 2, wp // 2, 32)); o1 = _v2_out(out1, (hp // 2, wp // 2, 32)) if two else None
+    _check(testlib().rife_hip_op_v2_conv_img(gpuid, int(two), int(cus), _p(a), _p(b), wp, hp, _p(weight), _p(bias), _p(slope), _p(o0), _p(o1)), "op_v2_conv_img", testlib())
+    return (o0, o1) if two else o0
+
+
+def op_conv_pair(weight, bias, slope, x0, y0, x1=None, y1=None, y_coff=0, y2=None, y2_coff=0, stride=1, deconv=False, gpuid=0):
+    """launch_conv with a second tensor pair (x1, y1) or a second destination view (y2).  weight (cout, cin, 3, 3) or, deconv, (cout, cin, 4, 4); x (H, W, cin); y0 / y1
+    (Ho, Wo, y_ld) with the layer's channels at y_coff; y2 (Ho, Wo, y2_ld) at y2_coff.  Returns the destinations that were given, in that order."""
+    weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32); slope = np.ascontiguousarray(slope, np.float32)
+    cout, cin = weight.shape[:2]
+    x0 = np.ascontiguousarray(x0, np.float32); x1 = None if x1 is None else np.ascontiguousarray(x1, np.float32)
+    H, W = x0.shape[:2]
+    if x0.shape != (H, W, cin) or (x1 is not None and x1.shape != x0.shape) or bias.shape != (cout,) or slope.shape != (cout,):
+        raise ValueError("x (H, W, cin), bias (cout) and slope (cout)")
+    o0 = np.array(y0, np.float32); o1 = None if y1 is None else np.array(y1, np.float32); o2 = None if y2 is None else np.array(y2, np.float32)
+    if o0.ndim != 3 or (o1 is not None and o1.shape != o0.shape) or (o2 is not None and (o2.ndim != 3 or o2.shape[:2] != o0.shape[:2])):
+        raise ValueError("destinations are (Ho, Wo, ld) arrays of one pixel grid")
+    _check(testlib().rife_hip_op_conv_pair(gpuid, cin, cout, int(stride), int(deconv), H, W, _p(weight), _p(bias), _p(slope), _p(x0), _p(x1), _p(o0), _p(o1), o0.shape[2], int(y_coff),
+                                           _p(o2), 0 if o2 is None else o2.shape[2], int(y2_coff)), "op_conv_pair", testlib())
+    return tuple(o for o in (o0, o1, o2) if o is not None)

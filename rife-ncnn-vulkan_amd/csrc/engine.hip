@@ -80,6 +80,7 @@
 #include "engine_v2.h"
 #include "engine_v1.h"
 #include "engine_abi.h"
+#include "engine_v2_ops.h"      // test build only: the rife-v2 / v3 schedule's kernels one launch at a time (empty in the product)
 #include "engine_image.h"
 #include "engine_apply.h"
 #include "engine_apply_sets.h"
